@@ -32,7 +32,8 @@ sys.path.insert(0, ROOT)
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (snp, indel, mixed, wgs, gvcf; ms_per_step = their mean); baq times "
+                                                          "max(1, steps // 3) calls and keeps the fastest, pileup overlaps max(4, steps) regions")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--samples", type=int, default=1000)
     ap.add_argument("--depth", type=float, default=30.0)
@@ -59,7 +60,15 @@ def parse():
                          "(BASELINE configs[2] shape, 500 samples), reports DP cells/s of the realignment kernel.  "
                          "baq: bcfgpu_baq (sam_prob_realn) over the reads of the same synthetic columns.  "
                          "gvcf: bcfgpu_gvcf_blocks (gvcf_write) over the mpileup-stage planes of a tile resident in HBM")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="snp mode: after the timed steps, write what the last step computed to DIR/<name>.npy (float32/float64, "
+                         "at most 64 MB in all; the per-sample planes of a fixed, seeded sample of sites)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs is not None and a.mode != "snp":
+        ap.error("--dump-outputs: only the snp mode (the headline pipeline) writes its outputs")
+    return a
 
 
 def host_cores():
@@ -82,6 +91,81 @@ def algorithmic_bytes(n_sites, n_smpl, n_reads, A=2):
     b_in = n_reads * 6 + n_sites * n_smpl * 6
     b_out = n_sites * (n_smpl * (4 * G + 12 * A + 16) + 128)
     return b_in + b_out
+
+
+DUMP_BYTES = 60_000_000                                       # --dump-outputs: the arrays written, at most (64 MB with the files' headers)
+
+
+def _as_float(x):
+    """an integer or float array in the float type that holds every value exactly: float32 for 8/16-bit integers and float32,
+    float64 for the rest"""
+    x = np.asarray(x)
+    if x.dtype.kind == "f":
+        return x.astype(np.float64 if x.dtype.itemsize > 4 else np.float32)
+    return x.astype(np.float32 if x.dtype.itemsize <= 2 else np.float64)
+
+
+def _finite_parts(name, x):
+    """{name: x as a float array} for integers; for floats the values with 0 in place of the non-finite ones and
+    {name}_nonfinite: 0 finite, 1 NaN, 2 +inf, 3 -inf.  The site records hold HUGE_VAL where the reference leaves a statistic
+    out (bam2bcf.c:835-840, e.g. a rank-sum test with one side empty), and a dump holds finite numbers only."""
+    x = _as_float(x)
+    if x.dtype.kind != "f":
+        return {name: x}
+    fin = np.isfinite(x)
+    code = np.where(fin, 0, np.where(np.isnan(x), 1, np.where(x > 0, 2, 3))).astype(np.float32)
+    return {name: np.where(fin, x, 0).astype(x.dtype), name + "_nonfinite": code}
+
+
+def dump_outputs(d, seed, T, S, L, h, mbufs, csite, cgt, cpl, recbuf, n_bytes, n_rec):
+    """--dump-outputs: what a caller of bcfgpu_pipeline + bcfgpu_compact_calls_async receives from the last step, as DIR/<name>.npy.
+    The site records of both stages (one file per field), the per-sample planes of the mpileup and call stages at a fixed, seeded
+    sample of sites (the whole planes are gigabytes), and the first bytes of the compacted records with their counts.  Every value
+is finite: a float field's non-finite entries are written as 0 and classified in <name>_nonfinite.npy.  The sample
+    depends on --seed and the tile shape only, so two builds run with the same arguments write files that compare one to one."""
+    import torch
+    from bcftools_amd import host
+    from bcftools_amd.lib import check
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    out = {}
+    # ---- site records: bcfgpu_site (mpileup) and bcfgpu_call_site (call), every site if they fit half the budget ----
+    msite = np.zeros(T, host.SITE_DTYPE)
+    mbufs["site"].download(msite)
+    csite_h = csite.cpu().numpy().view(host.CALLSITE_DTYPE)
+    recs = {"mplp_site": msite, "call_site": csite_h}
+    per_site = sum(v.nbytes for r in recs.values() for f in r.dtype.names if f != "pad" for v in _finite_parts(f, r[f][:1]).values())
+    n = min(T, DUMP_BYTES // 2 // per_site)
+    sites = np.arange(T) if n == T else np.sort(rng.choice(T, n, replace=False))
+    out["site_index"] = sites.astype(np.float64)
+    for name, r in recs.items():
+        for f in r.dtype.names:
+            if f != "pad":
+                out.update(_finite_parts("%s_%s" % (name, f), r[f][sites]))
+    # ---- per-sample planes at a sample of sites: what the mpileup stage wrote (the planes this run asks for) and GT / PL of call ----
+    one = host.MplpResult(1, S)
+    mplanes = {k: getattr(one, k)[0] for k in mbufs if k != "site"}
+    cplanes = {"gt": cgt.view(T, 2, S), "pl": cpl.view(T, -1, S)}
+    per_site = sum(_as_float(v).nbytes for v in mplanes.values()) + 4 * cplanes["gt"][0].numel() + 8 * cplanes["pl"][0].numel()   # int8 -> f32, int32 -> f64
+    n = min(T, DUMP_BYTES // 3 // per_site)                       # (0 when a single site's planes are past the budget)
+    psites = np.sort(rng.choice(T, n, replace=False))
+    out["plane_site_index"] = psites.astype(np.float64)
+    for k, proto in mplanes.items():
+        got = np.zeros((n,) + proto.shape, proto.dtype)
+        for j, i in enumerate(psites):                            # a site's plane is one contiguous run of the [site][...][sample] array
+            check(L.bcfgpu_memcpy_d2h(h, got[j].ctypes.data, mbufs[k].ptr + int(i) * proto.nbytes, proto.nbytes))
+        out["mplp_" + k] = _as_float(got)
+    idx = torch.as_tensor(psites, dtype=torch.int64, device=cgt.device)
+    for k, v in cplanes.items():
+        out["call_" + k] = _as_float(v.index_select(0, idx).cpu().numpy())
+    # ---- the compacted records (the bytes call -mv's writer takes): as many of the first bytes as the rest of the budget holds ----
+    out["records_counts"] = np.array([n_bytes, n_rec], np.float64)
+    nb = max(0, min(int(n_bytes), (DUMP_BYTES - sum(v.nbytes for v in out.values())) // 4))
+    out["records_bytes"] = _as_float(recbuf[:nb].cpu().numpy())
+    assert sum(v.nbytes for v in out.values()) <= DUMP_BYTES and all(np.isfinite(v).all() for v in out.values())
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v))
+    return sum(v.nbytes for v in out.values())
 
 
 def main_indel(a):
@@ -888,7 +972,9 @@ def main():
     ctx = engine.Context(cfg)
     d_ploidy = d_grp = None
     if a.haploid_frac > 0:
-        d_ploidy = torch.where(torch.rand(S, device=dev) < a.haploid_frac, 1, 2).to(torch.uint8)
+        g = torch.Generator(device=dev)                         # a seed of its own from --seed (the tile's are --seed + rank)
+        g.manual_seed(a.seed + 1_000_003)
+        d_ploidy = torch.where(torch.rand(S, device=dev, generator=g) < a.haploid_frac, 1, 2).to(torch.uint8)
     if a.groups > 1:
         d_grp = (torch.arange(S, device=dev) * a.groups // S).to(torch.int32)
     L = ctx.L
@@ -898,6 +984,9 @@ def main():
                                             tile["rd"].data_ptr(), tile["epos"].data_ptr())
     # outputs (device)
     mo, mbufs, _ = ctx.alloc_mplp_out(T, ctx.flagged_planes())
+    for b in mbufs.values():                                   # planes the kernels skip for unused alleles read as zero, as in engine.pipeline
+        check(L.bcfgpu_memset(ctx.h, b.ptr, 0, b.nbytes))
+    check(L.bcfgpu_sync(ctx.h))                                # (before a rank's work moves to a stream of its own)
     co = abi.CallOut()
     csite = torch.zeros(T * C.sizeof(abi.CallSite), dtype=torch.uint8, device=dev)
     cgt = torch.zeros(T * 2 * S, dtype=torch.int8, device=dev)
@@ -917,8 +1006,9 @@ def main():
     # inside the timed loop.  N > 1: the gather of step i-1 runs on a side stream beside the kernels of step i -- the only
     # host wait is for step i-1's byte count, while the device works on step i (the two library calls
     # host/bcfgpu_mgpu.c makes, bcfgpu_compact_calls* and the ordered gather).
-    recbuf = [torch.empty(rec_cap, dtype=torch.uint8, device=dev) for _ in range(2 if world > 1 else 1)]
+    recbuf = [torch.zeros(rec_cap, dtype=torch.uint8, device=dev) for _ in range(2 if world > 1 else 1)]      # (zeros: the records' padding too)
     counts = [torch.zeros(4, dtype=torch.int64, device=dev) for _ in recbuf]
+    torch.cuda.synchronize()                                   # (the zeroed outputs are in place before the library's stream writes them)
     rehearse = world > 1 and os.environ.get("BCFGPU_BENCH_REHEARSE") == "1"
     gathered = torch.empty(rec_cap * world, dtype=torch.uint8, device=dev) if (world > 1 and rank == 0 and not rehearse) else None
     gathered_host = torch.empty(rec_cap * world, dtype=torch.uint8) if (rehearse and rank == 0) else None
@@ -983,6 +1073,9 @@ def main():
     tm = ctx.last_timing()
     check(L.bcfgpu_timing_enable(ctx.h, 0))
     check(L.bcfgpu_compact_counts(ctx.h, counts[(state["i"] - 1) % len(recbuf)].data_ptr(), C.byref(n_bytes), C.byref(n_rec)))   # (BCFGPU_E_RANGE on overflow)
+    if a.dump_outputs is not None and rank == 0:               # (outside the timed steps: the last step's outputs are still in place)
+        dump_outputs(a.dump_outputs, a.seed, T, S, L, ctx.h, mbufs, csite, cgt, cpl, recbuf[(state["i"] - 1) % len(recbuf)],
+                     n_bytes.value, n_rec.value)
 
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:

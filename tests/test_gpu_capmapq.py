@@ -14,7 +14,6 @@ from bcftools_amd.lib import check
 from tests.helpers import sam, vcf, orc, mplpdrv as M, mplpcmp as K
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def device_caps(ctx, reads, refseq, thres):
@@ -88,7 +87,7 @@ def test_random_reads(gpu_ctx_factory):
         assert (want < 0).any() and (want == thres).any() and ((want > 0) & (want < thres)).any()
 
 
-def test_c_driver_with_adjust_mq(golden_dir):
+def test_c_driver_with_adjust_mq(golden_dir, tmp_path):
     """`bcfgpu_sam -C 50` (BAQ on): every SNP record equals what the Python pipeline over the oracle gives with the same option
     (BAQ -> sam_cap_mapq -> -q / orphan filters -> overlaps -> pileup), and differs from the run without -C."""
     from tests.test_c_host import build_host, SAM_EXE
@@ -99,7 +98,7 @@ def test_c_driver_with_adjust_mq(golden_dir):
     out = subprocess.run([SAM_EXE, "-C", "50"] + base, check=True, capture_output=True, text=True).stdout
     plain = subprocess.run([SAM_EXE] + base, check=True, capture_output=True, text=True).stdout
     assert out != plain
-    tmp = os.path.join(ROOT, "gpurun_out", "capmapq.vcf") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else "/tmp/capmapq.vcf"
+    tmp = str(tmp_path / "capmapq.vcf")
     open(tmp, "w").write(out)
     got = vcf.Vcf(tmp)
     fmt_flag = abi.INFO_VDB | abi.INFO_RPB

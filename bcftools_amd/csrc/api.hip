@@ -36,7 +36,6 @@ struct bcfgpu_ctx {
     double call_theta_log = 0;
     // workspaces sized by cfg.max_sites / cfg.max_reads
     int *d_hist = nullptr, *d_err = nullptr;       // d_err: [0] error word, [1] cells past 255 usable reads, [2..4] counters of glfgen's deep-cell list, [5] WideRecs of the launch
-    uint16_t *d_keys = nullptr;                    // glfgen in two launches (BCFGPU_GLFGEN_SPLIT=1): 2 bytes per read between them
     int32_t *d_grp_rng = nullptr;                  // mcall: sample range of every -G group
     float *d_grp_q = nullptr; size_t grp_q_bytes = 0;   // mcall -G: the groups' frequency sums of a launch (grow-only)
     uint32_t *d_deep_list = nullptr; uint16_t *d_deep_keys = nullptr; uint32_t deep_cap = 0, deep_key_cap = 0, wide_cap = 0;
@@ -163,9 +162,6 @@ int bcfgpu_create(const bcfgpu_cfg *cfg, bcfgpu_ctx **out)
         }
         // glfgen's list of cells deeper than its LDS key window, and the scratch their keys go to (2 bytes per pileup entry):
         // up to 1024 such cells per tile, with at most 32 Mi entries between them (or the whole tile's, when it is smaller)
-#ifdef BCFGPU_DIAG      // the two-launch form of glfgen is a measurement variant (make DIAG=1), never the product path
-        if (const char *sp = getenv("BCFGPU_GLFGEN_SPLIT")) if (atoi(sp) && (rc = dev_alloc(c, (void**)&c->d_keys, ((size_t)cfg->max_reads + 64) * 2))) { bcfgpu_destroy(c); return rc; }
-#endif
         c->deep_cap = 1024;
         c->deep_key_cap = (uint32_t)std::min<uint64_t>((uint64_t)cfg->max_reads + 16 * 1024, 32u << 20);
         if ((rc = dev_alloc(c, (void**)&c->d_deep_list, (size_t)c->deep_cap * 8)) || (rc = dev_alloc(c, (void**)&c->d_deep_keys, (size_t)c->deep_key_cap * 2 + 64))) {
@@ -469,9 +465,6 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
         g.part_cols = pc;
     }
     g.n_reads = (uint32_t)tile->n_reads;
-#ifdef BCFGPU_DIAG
-    { const char *ab = getenv("BCFGPU_ABLATE"); g.ablate = ab ? atoi(ab) : 0; }
-#endif
     g.ref16 = tile->ref16; g.off = tile->plp_off; g.rd = tile->rd; g.epos = tile->epos; g.aux = tile->aux;
     g.fk = c->d_fk; g.beta = c->d_beta; g.lhet = c->d_lhet;
     g.crp = c->d_crp;
@@ -480,7 +473,6 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
     g.trunc = reinterpret_cast<unsigned int*>(c->d_err + 1);
     g.deep_list = c->d_deep_list; g.deep_ctr = reinterpret_cast<uint32_t*>(c->d_err + 2); g.deep_keys = c->d_deep_keys;
     g.deep_cap = c->deep_cap; g.deep_key_cap = c->deep_key_cap;
-    g.keys = c->d_keys;
     {   // the plan bcfgpu_errmod_plan made for this pass of this tile, if any: it serves this one launch
         const int kind = tile->is_indel ? 1 : 0;
         g.draw_bits = (c->draw.rd[kind] && c->draw.rd[kind] == tile->rd) ? c->draw.bits[kind] : nullptr;
@@ -488,19 +480,6 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
     }
     g.wide_ctr = reinterpret_cast<uint32_t*>(c->d_err + 5); g.wide_cap = c->wide_cap;
     HIPCHK(hipMemsetAsync(c->d_err + 2, 0, 4 * sizeof(int), c->stream));
-#ifdef BCFGPU_DIAG
-    {   // phase stamps of glfgen_kernel: totals of the previous launch are printed, then cleared
-        static unsigned long long *d_st = nullptr;
-        if (!d_st) { hipMalloc(&d_st, 16 * 8); hipMemset(d_st, 0, 16 * 8); }
-        if (getenv("BCFGPU_STAMPS")) {
-            unsigned long long h[16]; hipStreamSynchronize(c->stream); hipMemcpy(h, d_st, sizeof h, hipMemcpyDeviceToHost);
-            unsigned long long tot = 0; for (int i = 0; i < 10; ++i) tot += h[i];
-            if (tot) { fprintf(stderr, "[glfgen stamps %%]"); for (int i = 0; i < 10; ++i) fprintf(stderr, " %.1f", 100.0 * h[i] / tot); fprintf(stderr, "  (total %.3g wave-cycles)\n", (double)tot); }
-            hipMemset(d_st, 0, 16 * 8);
-            g.stamps = d_st;                          // the stamps cost atomics: only when asked for
-        }
-    }
-#endif
     HIPCHK(hipMemsetAsync(c->d_hist, 0, (size_t)tile->n_sites * H_SIZE * sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(c->d_site_sums, 0, (size_t)tile->n_sites * SITE_NSUM * 8, c->stream));
     hipEvent_t *ev = c->timing ? seq_events(c) : nullptr;
@@ -510,9 +489,6 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
     CombineParams k{};
     k.n_sites = tile->n_sites; k.n_smpl = S; k.is_indel = tile->is_indel; k.fmt_flag = c->cfg.fmt_flag;
     k.ref16 = tile->ref16; k.cr = c->cr; k.hist = c->d_hist; k.site_sums = c->d_site_sums; k.mw = c->d_mw; k.out = *out;
-#ifdef BCFGPU_DIAG
-    { const char *ab = getenv("BCFGPU_ABLATE"); k.ablate = ab ? atoi(ab) : 0; }
-#endif
     launch_combine(k, c->stream);
     if (ev) hipEventRecord(ev[2], c->stream);
     HIPCHK(hipGetLastError());
@@ -578,9 +554,6 @@ int bcfgpu_mcall(bcfgpu_ctx *c, const bcfgpu_call_in *in, const bcfgpu_call_out 
     m.ploidy = in->ploidy; m.grp = c->cfg.n_grp > 1 ? in->grp : nullptr; m.prior_an = in->prior_an; m.prior_ac = in->prior_ac; m.i16 = in->i16;
     m.out = *out; m.out_n_gt_max = in->n_gt_max; m.err = c->d_err;
     if (c->timing == 1) hipEventRecord(c->ev[2], c->stream);
-#ifdef BCFGPU_DIAG
-    { const char *ab = getenv("BCFGPU_ABLATE"); m.ablate = ab ? atoi(ab) : 0; }
-#endif
     launch_mcall(m, c->stream);
     if (c->timing == 1) { hipEventRecord(c->ev[3], c->stream); hipEventSynchronize(c->ev[3]);
         bcfgpu_timing t{}; hipEventElapsedTime(&t.mcall_ms, c->ev[2], c->ev[3]); t.total_ms = t.mcall_ms; c->last = t; }
@@ -612,9 +585,6 @@ int bcfgpu_pipeline(bcfgpu_ctx *c, const bcfgpu_tile *tile, const uint8_t *ploid
     if (c->cfg.n_grp > 1 && !m.grp_q) return set_err(BCFGPU_E_NOMEM, "call -G: workspace of the groups' frequency sums");
     m.ploidy = ploidy; m.grp = c->cfg.n_grp > 1 ? grp : nullptr;
     m.out = *cout; m.out_n_gt_max = BCFGPU_MAX_PL; m.err = c->d_err;
-#ifdef BCFGPU_DIAG
-    { const char *ab = getenv("BCFGPU_ABLATE"); m.ablate = ab ? atoi(ab) : 0; }
-#endif
     launch_mcall(m, c->stream);
     if (c->timing == 1) hipEventRecord(c->ev[3], c->stream);
     else if (c->timing == 2) { hipEventRecord(c->pool[c->pool_used - 1], c->stream); c->pool_call.back() = 1; }

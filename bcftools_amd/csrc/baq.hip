@@ -507,9 +507,6 @@ __device__ __forceinline__ void baq_fb_reg(const BaqParams &P, int job, const Ba
         // even row from the odd row below it while it forms that row's posterior.  Unscaled, because the row above needs D of
         // this one, which is not stored: D' is the recurrence D'[p] = m2 M'[p-1] + m8 D'[p-1] over the UNSCALED M' -- re-run
         // in the same order it gives the same bits, and the scaled row is re-formed by the same multiplication as here.
-#ifdef BAQ_EXP_NOSTORE       // experiment: the forward rows are not written (never true at run time)
-        if (P.n_jobs < 0)
-#endif
         if (i & 1) {
             #pragma unroll
             for (int p = 1; p <= W; ++p) {
@@ -538,9 +535,6 @@ __device__ __forceinline__ void baq_fb_reg(const BaqParams &P, int job, const Ba
     #pragma unroll
     for (int p = 1; p <= W; ++p) s_end += M[p] * sM + I[p] * sI;
     SC(l_query + 1) = s_end;
-#if defined(BAQ_EXP_PHASE) && BAQ_EXP_PHASE == 1   // experiment: the forward pass only
-    if (l_query > 0) { qw[lane] = (uint8_t)M[1]; return; }
-#endif
     // ---- backward with the posterior maximum of every row ----
     // Iteration i: b[i] from b[i+1] (not for the last row), then the posterior of row i.  The window is the forward pass's: the
     // step's emission is that of (row i+1, column k+1) = the forward window of row i+1 at the same position; then it moves one
@@ -647,9 +641,6 @@ __device__ __forceinline__ void baq_fb_reg(const BaqParams &P, int job, const Ba
                 z = fI * I[p]; if (z > max) { max = z; best = p << 2 | 1; } sum += z;
             }
             // the stored row the next two posteriors work from: row i - 2 (row i - 1 is re-formed from it, then it is its own)
-#ifdef BAQ_EXP_NOLOAD       // experiment: the forward rows are not read back (never true at run time): the backward pass on stale values
-            if (P.n_jobs < 0)
-#endif
             if (i >= 3) fr_request(i - 2);
         } else {
             // an even row: re-formed cell by cell from the stored row below (fr = row i - 1, unscaled) exactly as the forward pass
@@ -858,9 +849,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BAQ_WAVES(BW
         baq_fb_lds<LANES>(P, job, j, ref, seq, iqual, state, q, s_rows + threadIdx.x, s_rows + rw + threadIdx.x, s_rows + 2 * rw + threadIdx.x,
                           reinterpret_cast<uint8_t*>(s_rows + 3 * rw) + threadIdx.x);
     } else baq_fb_scratch(P, job, j, ref, seq, iqual, state, q);
-#if !defined(BAQ_EXP_PHASE) || BAQ_EXP_PHASE == 0
     baq_cap(P, j, iqual, state, q, left, pst, qout, zout);
-#endif
 }
 
 // ---- the same stage on the pool bcfgpu_pool_upload left in HBM: the host half above as a kernel ----
@@ -1076,15 +1065,10 @@ extern "C" int bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const char *r
     // (long indels), run separately with both matrices in scratch and their own row width
     auto eff_bw = [](const BaqJob &j) { int b = j.l_ref > j.l_query ? j.l_ref : j.l_query; if (b > j.bw) b = j.bw;
                                         if (b < std::abs(j.l_ref - j.l_query)) b = std::abs(j.l_ref - j.l_query); return b; };
-#ifdef BCFGPU_DIAG
-    const bool force_scratch = [] { const char *ab = getenv("BCFGPU_ABLATE"); return ab && (atoi(ab) & 512); }();
-#else
-    const bool force_scratch = false;
-#endif
     std::vector<BaqJob> cls[4];
     int cls_bw[4] = {1, 1, 1, 1};
     for (const BaqJob &j : jobs) {
-        const int b = j.ret < 0 ? 1 : eff_bw(j), c = force_scratch ? 2 : b <= BAQ_BWM ? 0 : b <= BAQ_BWM2 ? 1 : b <= BAQ_BWM3 ? 3 : 2;
+        const int b = j.ret < 0 ? 1 : eff_bw(j), c = b <= BAQ_BWM ? 0 : b <= BAQ_BWM2 ? 1 : b <= BAQ_BWM3 ? 3 : 2;
         cls[c].push_back(j);
         if (b > cls_bw[c]) cls_bw[c] = b;
     }

@@ -310,7 +310,7 @@ __device__ __forceinline__ void sample_planes(const CombineParams &P, SampleTota
         #pragma unroll
         for (int v = 0; v < V; ++v) any_wide |= misc[v];
         any_wide &= CR_WIDE;
-        if (NAL > 0 && !BCFGPU_ABL(P, 512)) {
+        if (NAL > 0) {
             uint16_t *DP4 = P.out.dp4 + (size_t)is * 4 * Ss + s;
             uint32_t b[V];
             #pragma unroll
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
         }
         __syncthreads();
         if (base + HC < S) fetch_qs(base + HC);
-        if (tid < 4 && !BCFGPU_ABL(P, 8192)) myq = seq_sum_f32(myq, s_frt + tid * HC, cn);
+        if (tid < 4) myq = seq_sum_f32(myq, s_frt + tid * HC, cn);
     }
     if (tid < 4) s_q[tid] = myq;
     __syncthreads();
@@ -514,8 +514,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
     for (int base = 0; base < S; base += CHUNK) {
         const int cn = min(CHUNK, S - base);
         __syncthreads();
-        const bool live = !dead && !BCFGPU_ABL(P, 256);
-        #define PLANES(V_) switch (live ? nal : 0) { \
+        #define PLANES(V_) switch (dead ? 0 : nal) { \
             case 1: sample_planes<1, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
             case 2: sample_planes<2, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
             case 3: sample_planes<3, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
@@ -528,7 +527,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
         // bam2bcf.c:642, sum_min += the sample's smallest likelihood, in sample order.  A cell whose reads all show one base has
         // a zero there (nine in ten do): x + 0.0 is x, so only the other terms are added, in their order -- found by the whole
         // wavefront 64 samples at a time, added by the scalar walk over the ballot (every lane computes the same sum).
-        if (!dead && !BCFGPU_ABL(P, 8192)) {
+        if (!dead) {
             double acc = sh.sum_min;
             for (int b0 = 0; b0 < cn; b0 += WG) {
                 const double v = b0 + tid < cn ? s_min[b0 + tid] : 0.0;
@@ -549,7 +548,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
         int as5[5];
         #pragma unroll
         for (int j = 0; j < 5; ++j) as5[j] = as[j];
-        fix_wide_cells(P, T, as5, nal, !dead && !BCFGPU_ABL(P, 256), is, c0, tid);
+        fix_wide_cells(P, T, as5, nal, !dead, is, c0, tid);
         __syncthreads();                                          // the SP / SGB passes below read the DP4 planes
     }
     // FMT/SP (bam2bcf.c:867-885): a Fisher exact test per sample, in its own pass -- its loops over the table's margins
@@ -586,7 +585,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
     // ---- calc_SegBias (bam2bcf.c:494-530): tree-reduced sum of per-sample terms ----
     const double an0 = (double)sh.tot[13], an1 = (double)sh.tot[14], an2 = (double)sh.tot[15], an3 = (double)sh.tot[16];
     const int nr = (int)(an2 + an3);
-    if (nr && !dead && !BCFGPU_ABL(P, 2048)) {
+    if (nr && !dead) {
         const int avg_dp = (int)((an0 + an1 + nr) / S);
         double M = floor((double)nr / avg_dp + 0.5);
         if (M > S) M = S;
@@ -651,7 +650,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
         for (int i = tid; i < H_SIZE; i += WG) s_h[i] = h[i];
     }
     __syncthreads();
-    if (!dead && !BCFGPU_ABL(P, 4096)) {
+    if (!dead) {
         const int *h = s_h;
         // the four Mann-Whitney tests: bin sums by the whole wavefront, the closed forms in lanes 1..4; lane 0 the VDB
         int na_t = 0, nb_t = 0; double U_t = 0;
@@ -700,7 +699,7 @@ void launch_combine(const CombineParams &p, hipStream_t s)
     CombineParams q = p;
     // four samples per lane need every site's row of every plane to start on a 16-byte (u8 planes: 4-byte) boundary
     auto al = [](const void *ptr, uintptr_t a) { return ptr == nullptr || reinterpret_cast<uintptr_t>(ptr) % a == 0; };
-    q.vec4 = (p.n_smpl % 4 == 0) && !BCFGPU_ABL(p, 1024) &&
+    q.vec4 = (p.n_smpl % 4 == 0) &&
              al(p.cr.p15, 16) && al(p.cr.pa, 16) && al(p.cr.cnt4, 16) && al(p.cr.adf, 16) && al(p.cr.adr, 16) && al(p.cr.misc, 16) && al(p.cr.qs64, 8) &&
              al(p.out.pl, 4) && al(p.out.dp4, 8) && al(p.out.scr, 8) && al(p.out.adf, 8) && al(p.out.adr, 8) && al(p.out.qs, 16);
     if (q.vec4) hipLaunchKernelGGL(combine_kernel<4>, dim3(q.n_sites), dim3(WG), 0, s, q);

@@ -27,17 +27,6 @@
 
 namespace bcfgpu {
 
-// Diagnostics build: cycles (s_memtime) every wavefront spends between the kernel's phase boundaries, summed into
-// P.stamps[0..8] (0: prologue up to phase A, 1: phase A, 2: barrier, 3: partial sums + slice set-up, 4: pass 1,
-// 5: walk of the primary base, 6: other bases, 7: epilogue, 8: flush, 9: slot fill of the primary base); tools/stamps.sh prints them.
-#ifdef BCFGPU_DIAG
-#define GLF_STAMP_DECL unsigned long long stamp_t_ = __builtin_amdgcn_s_memtime();
-#define GLF_STAMP(i_) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); if ((threadIdx.x & 63) == 0 && P.stamps) atomicAdd(&P.stamps[i_], now_ - stamp_t_); stamp_t_ = now_; }
-#else
-#define GLF_STAMP_DECL
-#define GLF_STAMP(i_)
-#endif
-
 #define WG 256
 #ifndef GLF_WAVES
 #define GLF_WAVES 5          // wavefronts per SIMD the register budget is held to
@@ -96,30 +85,15 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 #ifndef WR
 #define WR 2            // reads of a run taken per step of the errmod walk
 #endif
-#ifndef GLF_WIDE_KEYS
-#define GLF_WIDE_KEYS 0      // the counting pass and pass 1 read four keys as one (unaligned) 8-byte LDS read instead of four 2-byte ones
-#endif
 // the sources of count_runs(): key7 of the j-th element or -1 -- the reads of the primary base (rejected reads are zeros), or those
 // of the lane's other reads that show base b
 struct PrimSrc {
     const uint16_t *kpp;
     __device__ __forceinline__ int operator()(int j) const { const uint32_t k = kpp[j]; return k ? (int)(k & 0x7f) : -1; }
-    __device__ __forceinline__ void quad(int j, int n, int (&k4)[4]) const
-    {
-        uint64_t w; __builtin_memcpy(&w, kpp + j, 8);
-        #pragma unroll
-        for (int u = 0; u < 4; ++u) { const uint32_t k = (uint32_t)(w >> (16 * u)) & 0xffffu; k4[u] = (j + u < n && k) ? (int)(k & 0x7f) : -1; }
-    }
 };
 struct BaseSrc {
     const uint16_t *kp; int b;
     __device__ __forceinline__ int operator()(int i) const { const uint32_t k = kp[i]; return (int)KEY_B(k) == b ? (int)(k & 0x7f) : -1; }
-    __device__ __forceinline__ void quad(int j, int n, int (&k4)[4]) const
-    {
-        uint64_t w; __builtin_memcpy(&w, kp + j, 8);
-        #pragma unroll
-        for (int u = 0; u < 4; ++u) { const uint32_t k = (uint32_t)(w >> (16 * u)) & 0xffffu; k4[u] = (j + u < n && (int)KEY_B(k) == b) ? (int)(k & 0x7f) : -1; }
-    }
 };
 template <bool FIRST, class Src>
 __device__ __forceinline__ uint32_t count_runs(uint32_t *s_slot, uint64_t qm, int tid, Src src, int nsrc)
@@ -130,13 +104,8 @@ __device__ __forceinline__ uint32_t count_runs(uint32_t *s_slot, uint64_t qm, in
     // FU source elements per trip: their reads are in flight before the first count is added
     for (int j = 0; __any(j < nsrc); j += FU) {
         int k4[FU];
-#if GLF_WIDE_KEYS
-        static_assert(FU == 4, "the four keys of a trip are one 8-byte read");
-        src.quad(j, nsrc, k4);
-#else
         #pragma unroll
         for (int u = 0; u < FU; ++u) k4[u] = j + u < nsrc ? src(j + u) : -1;
-#endif
         #pragma unroll
         for (int u = 0; u < FU; ++u) {
             const int key = k4[u], q = (key >> 1) & 63;
@@ -169,7 +138,7 @@ __device__ __forceinline__ uint32_t count_runs(uint32_t *s_slot, uint64_t qm, in
 // `brow`: byte offset of beta[0][0][n] (stored q, k, n: tables.cpp; the q = 0 row is all zeros).
 template <class Src>
 __device__ __forceinline__ double walk_runs(uint32_t *s_slot, uint64_t qm, const double *s_fk, const char *bbase, int tid,
-                                            uint32_t brow, Src src, int nsrc, uint32_t &rev_out, uint32_t &qs_out, int ab = 0)
+                                            uint32_t brow, Src src, int nsrc, uint32_t &rev_out, uint32_t &qs_out)
 {
     double bs = 0;
     uint32_t qs = 0;
@@ -205,10 +174,8 @@ __device__ __forceinline__ double walk_runs(uint32_t *s_slot, uint64_t qm, const
         koff += took << 11;
         return __any(left != 0);
     };
-    // (diagnostics build: `ab` switches the table gather to one line (512), off (1024), the fk read off (2048))
     #define WALK_LOAD(B, F, off_, wi_) do { _Pragma("unroll") for (int u_ = 0; u_ < WR; ++u_) { \
-        B[u_] = (ab & 1024) ? 1.0 : *reinterpret_cast<const double*>(bbase + ((ab & 512) ? (off_)[u_] & 0x1f8u : (off_)[u_])); \
-        F[u_] = (ab & 2048) ? (double)(wi_)[u_] : s_fk[(wi_)[u_]]; } } while (0)
+        B[u_] = *reinterpret_cast<const double*>(bbase + (off_)[u_]); F[u_] = s_fk[(wi_)[u_]]; } } while (0)
     #define WALK_ADD(B, F) do { _Pragma("unroll") for (int u_ = 0; u_ < WR; ++u_) bs += F[u_] * B[u_]; } while (0)
     bool first = true;
     while (__any(qm != 0)) {                                              // a round: the next NRANK qualities of every lane
@@ -248,127 +215,6 @@ __device__ __forceinline__ double walk_runs(uint32_t *s_slot, uint64_t qm, const
     return bs;
 }
 
-// ---- the walk with one read per step and the step number in a scalar register (GLF_WALK == 2) ----
-// count_ends(): count_runs() whose rank dwords end up as  quality << 19 | end_fwd << 8 | end_rev : the lane's reads of the round in
-// walking order are numbered 0 .. nr - 1; those of rank r are [end_fwd of rank r - 1, end_fwd), its reverse-strand reads first, up
-// to end_rev.  walk_ends() then takes step t in every lane at once: the k row of the table is (reads of earlier rounds + t), the
-// same for the whole wavefront but for a per-lane constant, the descriptor is used up when t reaches its end_fwd, the read is a
-// reverse-strand one while t < end_rev, and the forward strand's running count is t minus the reverse strand's.  A step is then
-// two compares and a handful of selects instead of the run bookkeeping of walk_runs() (which lets a lane take up to WR reads
-// of its current run and so needs a step count of its own per lane).
-template <bool FIRST, class Src>
-__device__ __forceinline__ uint32_t count_ends(uint32_t *s_slot, uint64_t qm, int tid, Src src, int nsrc, uint32_t &nr)
-{
-    #pragma unroll
-    for (int k = 0; k < NRANK; ++k) s_slot[k * WG + tid] = 0;
-    const uint64_t qm1 = qm >> 1;
-    for (int j = 0; __any(j < nsrc); j += FU) {
-        int k4[FU];
-#if GLF_WIDE_KEYS
-        static_assert(FU == 4, "the four keys of a trip are one 8-byte read");
-        src.quad(j, nsrc, k4);
-#else
-        #pragma unroll
-        for (int u = 0; u < FU; ++u) k4[u] = j + u < nsrc ? src(j + u) : -1;
-#endif
-        #pragma unroll
-        for (int u = 0; u < FU; ++u) {
-            const int key = k4[u], q = (key >> 1) & 63;
-            if (key >= 0 && (FIRST || ((qm >> q) & 1ull))) {
-                const int r = __popcll(qm1 >> q);
-                if (r < NRANK) atomicAdd(&s_slot[r * WG + tid], (key & 1) ? 1u : 0x100u);
-            }
-        }
-    }
-    uint32_t qs = 0, acc = 0;
-    uint64_t m = qm;
-    for (int r = 0; r < NRANK && __any(m != 0); ++r) {
-        const int q = 63 - __clzll((long long)(m | 1ull));
-        const uint32_t c = s_slot[r * WG + tid];
-        if (m != 0) {
-            const uint32_t er = acc + (c & 0xffu);
-            acc = er + (c >> 8);
-            qs += (uint32_t)q * (acc - (er - (c & 0xffu)));
-            s_slot[r * WG + tid] = (uint32_t)q << 19 | acc << 8 | er;
-        }
-        m &= ~(1ull << q);
-    }
-    nr = acc;
-    return qs;
-}
-#ifndef GLF_PD
-#define GLF_PD 2            // steps of the walk in flight
-#endif
-template <class Src>
-__device__ __forceinline__ double walk_ends(uint32_t *s_slot, uint64_t qm, const double *s_fk, const char *bbase, int tid,
-                                            uint32_t brow, Src src, int nsrc, uint32_t &rev_out, uint32_t &qs_out, int ab = 0)
-{
-    double bs = 0;
-    uint32_t qs = 0;
-    uint32_t wr = 0;          // reverse-strand reads walked so far
-    uint32_t tl = 0;          // reads walked in earlier rounds
-    uint32_t vrow = brow;     // brow + tl << 11: the lane's part of the k row
-    bool first = true;
-    while (__any(qm != 0)) {
-        uint32_t nr;
-        qs += first ? count_ends<true>(s_slot, qm, tid, src, nsrc, nr) : count_ends<false>(s_slot, qm, tid, src, nsrc, nr);
-        first = false;
-        // the deepest lane's reads: the steps of the round
-        uint32_t T = nr;
-        #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) T = max(T, (uint32_t)__shfl_xor((int)T, o));
-        T = (uint32_t)__builtin_amdgcn_readfirstlane((int)T);
-        uint32_t d = s_slot[tid], ridx = 1, d_nx = s_slot[WG + tid];
-        const uint32_t tb = tl;
-        auto step = [&](const uint32_t t, uint32_t &voff, uint32_t &wi) {
-            const bool pop = t == ((d >> 8) & 0xffu);                  // the rank's reads are walked: the next one's descriptor
-            d = pop ? d_nx : d;
-            ridx += pop ? 1u : 0u;
-            d_nx = s_slot[min(ridx, (uint32_t)NRANK - 1u) * WG + tid];
-            const bool act = t < nr, rev = t < (d & 0xffu);
-            const uint32_t w = rev ? wr : t + tb - wr;
-            wr += (act && rev) ? 1u : 0u;
-            wi = act ? w : 256u;
-            voff = act ? (d & 0x1f80000u) + vrow : brow;
-        };
-        #define WALK2_LOAD(B, F, t_, voff_, wi_) do { \
-            B = (ab & 1024) ? 1.0 : *reinterpret_cast<const double*>(bbase + ((size_t)(t_) << 11) + (voff_)); \
-            F = (ab & 2048) ? (double)(wi_) : s_fk[(wi_)]; } while (0)
-        double bx[GLF_PD], fx[GLF_PD];
-        #pragma unroll
-        for (int u = 0; u < GLF_PD; ++u) { uint32_t voff, wi; step((uint32_t)u, voff, wi); WALK2_LOAD(bx[u], fx[u], (uint32_t)u, voff, wi); }
-        for (uint32_t t = GLF_PD; t < T + GLF_PD; t += GLF_PD) {        // (steps past every lane's reads add +0 times a finite entry of the q = 0 rows)
-            #pragma unroll
-            for (int u = 0; u < GLF_PD; ++u) {
-                bs += fx[u] * bx[u];
-                uint32_t voff, wi;
-                step(t + (uint32_t)u, voff, wi);
-                WALK2_LOAD(bx[u], fx[u], t + (uint32_t)u, voff, wi);
-            }
-        }
-        #pragma unroll
-        for (int u = 0; u < GLF_PD; ++u) bs += fx[u] * bx[u];
-        #undef WALK2_LOAD
-        tl += nr; vrow += nr << 11;
-        if (__any(__popcll(qm) > NRANK)) {
-            uint64_t m = qm;
-            for (int k = 0; k < NRANK && m; ++k) m &= ~(1ull << (63 - __clzll((long long)m)));
-            qm = m;
-        } else qm = 0;
-    }
-    rev_out = wr; qs_out = qs;
-    return bs;
-}
-#ifndef GLF_FETCH_GLOBAL
-#define GLF_FETCH_GLOBAL 0
-#endif
-#ifndef GLF_WALK
-#define GLF_WALK 1
-#endif
-#if GLF_WALK == 2
-#define walk_runs walk_ends
-#endif
-
 // per-lane partial sums of phase A (one site segment of one staging round)
 struct ReadSums {
     uint32_t t_bq, t_bq2, t_mq, t_mq2, t_md, t_md2;    // all accepted reads: baseQ, mapQ, min_dist and their squares
@@ -386,20 +232,12 @@ struct WaveCounts {
 // not worked on here: it is listed (P.deep_*), and the launch that follows (DEEP = true) gives each listed cell a workgroup
 // of its own -- phase A over the cell's reads with all 256 lanes, the keys in a global scratch array instead of LDS, phase B
 // by the one lane that owns the cell.
-// PHASE = 0: both phases in one kernel (the keys never leave LDS).  PHASE = 1 / 2: the two phases as kernels of their own --
-// phase A streams the reads once and leaves the keys in HBM (P.keys, 2 bytes per read) with nothing but the site
-// histograms in LDS, at the occupancy its registers allow; phase B copies its span's keys into LDS with coalesced loads
-// and keeps keys + fk + run counters there (no histograms: the rare take-back of a truncated cell goes to global memory).
-#ifndef GLF_WAVES_A
-#define GLF_WAVES_A 6
-#endif
-template <bool INDEL, bool LDS_HIST, bool DEEP, int PHASE>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ? GLF_WAVES_A : GLF_WAVES, PHASE == 1 ? GLF_WAVES_A : GLF_WAVES))) void glfgen_kernel(const GlfgenParams P)
+template <bool INDEL, bool LDS_HIST, bool DEEP>
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, GLF_WAVES))) void glfgen_kernel(const GlfgenParams P)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     if (DEEP && (blockIdx.x >= P.deep_ctr[0] || P.deep_list[2 * blockIdx.x] == 0xffffffffu)) return;
-    constexpr bool KEYS_GLOBAL = PHASE == 1 || (PHASE == 2 && DEEP);       // the key of read i at P.keys[i]
-    const int cap = (DEEP || PHASE == 1) ? 0x7ffffff0 : P.lds_cap;
+    const int cap = DEEP ? 0x7ffffff0 : P.lds_cap;
     double   *s_fk  = reinterpret_cast<double*>(smem + LDS_FK);
     uint32_t *s_cnt = reinterpret_cast<uint32_t*>(smem + LDS_CNT);
     int      *s_hist = reinterpret_cast<int*>(smem + LDS_HIST_OFF);
@@ -408,12 +246,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
     // before phase B takes the region
     uint32_t *s_part = s_cnt;
     const int pcol = P.part_cols;                    // columns per value: a power of two, NPART * slots * pcol <= 2048
-    uint16_t *s_key = KEYS_GLOBAL ? P.keys : DEEP ? P.deep_keys + P.deep_list[2 * blockIdx.x + 1]
-                                                  : reinterpret_cast<uint16_t*>(s_tot + (size_t)P.hist_slots * SITE_NSUM);
+    uint16_t *s_key = DEEP ? P.deep_keys + P.deep_list[2 * blockIdx.x + 1]
+                           : reinterpret_cast<uint16_t*>(s_tot + (size_t)P.hist_slots * SITE_NSUM);
     __shared__ unsigned int s_next, s_skip;
 
     const int tid = threadIdx.x;
-    GLF_STAMP_DECL
     const int S = P.n_smpl;
     const long ncells = (long)P.n_sites * S;
     const long cell0 = DEEP ? (long)P.deep_list[2 * blockIdx.x] : (long)blockIdx.x * WG;
@@ -424,10 +261,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
     const long cell = cell0 + tid;
     const bool active = cell < cell_end;
 
-    if (PHASE != 1) {
-        s_fk[tid] = P.fk[tid];
-        if (tid < 8) s_fk[256 + tid] = 0.0;           // [256]: the factor of a lane that sits a chunk element out
-    }
+    s_fk[tid] = P.fk[tid];
+    if (tid < 8) s_fk[256 + tid] = 0.0;               // [256]: the factor of a lane that sits a chunk element out
     if (LDS_HIST) {
         for (int i = tid; i < P.hist_slots * HP_SIZE; i += WG) s_hist[i] = 0;
         for (int i = tid; i < P.hist_slots * SITE_NSUM; i += WG) s_tot[i] = 0;
@@ -460,7 +295,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
     // not is listed for the launch that follows, with room for its keys in the scratch array; the rounds here step over its
     // reads.  Only when the list or the scratch array is full is the tile refused.
     bool deep = false;
-    if (!DEEP && PHASE != 1 && active && end - beg > (uint32_t)cap - 3u) {
+    if (!DEEP && active && end - beg > (uint32_t)cap - 3u) {
         deep = true;
         const uint32_t need = (end - beg + 16u) & ~7u;           // keys of the cell, the slack of the 8-byte stores, a multiple of 8
         const uint32_t slot = atomicAdd(&P.deep_ctr[0], 1u), at = atomicAdd(&P.deep_ctr[1], need);
@@ -471,8 +306,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
     uint32_t base = p_off[cell0];
 
     for (;;) {
-        const uint32_t abase = KEYS_GLOBAL ? 0u : base & ~3u;    // key index 0 of this round
-        const uint32_t lim = (DEEP || PHASE == 1) ? span_end : min(abase + (uint32_t)cap, span_end);
+        const uint32_t abase = base & ~3u;                       // key index 0 of this round
+        const uint32_t lim = DEEP ? span_end : min(abase + (uint32_t)cap, span_end);
         if (tid == 0) { s_next = 0xffffffffu; s_skip = 0; }
         if (LDS_HIST) for (int i = tid; i < P.hist_slots * NPART * pcol; i += WG) s_part[i] = 0;
         __syncthreads();
@@ -483,16 +318,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
         const uint32_t rlim = min(nb, lim);                      // reads [base, rlim) belong to this round's cells
         const bool part = cand && end <= rlim;                   // this lane's cell is handled in this round (cells behind a listed cell wait)
 
-        GLF_STAMP(0)
-        if constexpr (PHASE == 2) {
-            // the keys phase A left in HBM: this round's window into LDS, 16 bytes per lane and trip (a listed cell reads its own
-            // from HBM: KEYS_GLOBAL)
-            if (!KEYS_GLOBAL) {
-                const uint32_t nk = (rlim > abase ? rlim - abase : 0u) + 8u;        // (one key past the last cell: phase B reads ahead)
-                for (uint32_t i = 8u * tid; i < nk; i += 8u * WG)
-                    *reinterpret_cast<uint4*>(s_key + i) = *reinterpret_cast<const uint4*>(P.keys + abase + i);
-            }
-        } else
         // ================= phase A: one lane per read =================
         for (int sg = site0; sg <= site_last; ++sg) {            // uniform: the site segments of the workgroup's span
             const long c_lo = max(cell0, (long)sg * S), c_hi = min(cell_end, (long)(sg + 1) * S);
@@ -563,30 +388,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
                         C.ref59 += (uint32_t)__popcll(b59 & bref); C.alt59 += (uint32_t)__popcll(b59 & ~bref);
                         C.rev59 += (uint32_t)__popcll(b59 & brev); C.fwd59 += (uint32_t)__popcll(b59 & ~brev);
                     }
-#ifdef GLF_AGG_BQ
-                    if (LDS_HIST) {
-                        // base-quality bins: binned qualities put the 64 reads of a wave instruction on a handful of counters; one
-                        // add per distinct value present, with the REF / ALT counts of its lanes (ballots), instead of 64 adds on
-                        // <= 8 addresses
-                        const uint32_t bin = min(bq, 59u);
-                        const unsigned long long bref2 = __ballot(isref);
-                        unsigned long long todo = b_ok;
-                        while (todo) {
-                            const int ldr = __builtin_ctzll(todo);
-                            const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)bin, ldr);
-                            const unsigned long long m = __ballot(bin == v) & todo;
-                            if ((int)(tid & 63) == ldr) atomicAdd(&hist[H_REF_BQ + v], (int)((uint32_t)__popcll(m & bref2) | (uint32_t)__popcll(m & ~bref2) << 16));
-                            todo &= ~m;
-                        }
-                    }
-#endif
-                    if (ok && !BCFGPU_ABL(P, 1)) {
+                    if (ok) {
                         if (LDS_HIST) {
                             const int inc = isref ? 1 : 0x10000;
                             atomicAdd(&hist[H_REF_POS + ((e4 >> (8 * u)) & 0xff)], inc);
-#ifndef GLF_AGG_BQ
                             atomicAdd(&hist[H_REF_BQ + min(bq, 59u)], inc);
-#endif
                             if (!m59) {
                                 atomicAdd(&hist[H_REF_MQ + mapQ], inc);
                                 atomicAdd(&hist[HP_MQS + mapQ], rev ? 0x10000 : 1);
@@ -601,9 +407,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
                             }
                         }
                     }
-#ifdef GLF_SCHED
-                    if ((u & (GLF_SCHED - 1)) == GLF_SCHED - 1) __builtin_amdgcn_sched_barrier(0);   // the lane masks of these reads end here
-#endif
                 }
                 #pragma unroll
                 for (int h = 0; h < 4; h += 2) {
@@ -629,23 +432,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
             const uint32_t g0 = rb & ~3u;
             uint4 w4n = make_uint4(0, 0, 0, 0), a4n = make_uint4(0, 0, 0, 0);
             uint32_t e4n = 0;
-            // (the pointers went through scalar registers as opaque values: said to be global memory again, the loads are global_load
-            // with a scalar base, not flat_load -- which also counts on the LDS counter and needs a 64-bit address per lane)
-#if GLF_FETCH_GLOBAL
-            typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-            typedef const __attribute__((address_space(1))) u32x4_t *g_u4;
-            typedef const __attribute__((address_space(1))) uint32_t *g_u32;
-#endif
             auto fetch = [&](uint32_t i4) {
                 if (i4 >= re) return;
-#if GLF_FETCH_GLOBAL
-                if (__all(i4 >= re || i4 + 3 < n_reads_tot)) {   // (wave-uniform: but for the wavefront that holds the tile's last reads)
-                    const u32x4_t wq = *(g_u4)(const void*)(p_rd + i4);
-                    w4n = make_uint4(wq.x, wq.y, wq.z, wq.w);
-                    if (want_epos) e4n = *(g_u32)(const void*)(p_epos + i4);
-                    if (INDEL) { const u32x4_t aq = *(g_u4)(const void*)(p_aux + i4); a4n = make_uint4(aq.x, aq.y, aq.z, aq.w); }
-                } else
-#endif
                 if (i4 + 3 < n_reads_tot) {
                     w4n = *reinterpret_cast<const uint4*>(p_rd + i4);
                     if (want_epos) e4n = *reinterpret_cast<const uint32_t*>(p_epos + i4);
@@ -663,7 +451,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
             };
             fetch(g0 + 4u * tid);
             const uint32_t ntrip = (re - g0 + 4u * WG - 1) / (4u * WG);       // uniform trip count: the ballots need whole waves
-            for (uint32_t it = 0; it < (BCFGPU_ABL(P, 32) ? 0u : ntrip); ++it) {
+            for (uint32_t it = 0; it < ntrip; ++it) {
                 const uint32_t i4 = g0 + 4u * tid + it * (4u * WG);
                 if (__all(i4 >= re)) break;                      // the wavefront is past the segment's last read (the last trip's upper waves)
                 const uint32_t wv[4] = { w4n.x, w4n.y, w4n.z, w4n.w };
@@ -716,9 +504,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
                 }
             }
         }
-        GLF_STAMP(1)
-        if (!BCFGPU_ABL(P, 16384)) __syncthreads();          // (diagnostics: 16384 times the kernel without the barriers between the phases; results are then wrong)
-        GLF_STAMP(2)
+        __syncthreads();
         if (LDS_HIST) {
             // the columns of every partial sum: four lanes per value
             const int nslot = min(P.hist_slots, P.n_sites - site0), q4 = pcol >> 2;
@@ -729,10 +515,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
                 x += __shfl_xor(x, 1); x += __shfl_xor(x, 2);
                 if ((i & 3) == 0 && x) { const int vi = i >> 2; s_tot[(vi / NPART) * SITE_NSUM + vi % NPART] += x; }
             }
-            if (!BCFGPU_ABL(P, 16384)) __syncthreads();
+            __syncthreads();
         }
-
-        if constexpr (PHASE == 1) break;                         // the keys are in HBM: phase B is the next launch
 
         // ================= phase B: one lane per cell =================
         uint16_t *kp_w = s_key + (part ? beg - abase : 0);       // the lane's keys
@@ -796,7 +580,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
                 misc_p[cell] = mark;             // read back where the cell's planes are stored (below)
             }
         }
-        GLF_STAMP(3)
         // pass 1: the quality mask of the primary base; the few other reads are gathered at the front of the slice
         uint64_t qmask = 0;          // qualities seen among the reads of the primary base
         uint32_t n_prim = 0, scr = 0;
@@ -805,20 +588,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
         uint32_t n_b4 = 0;           // reads showing neither A, C, G nor T
         uint32_t o_rev = 0, n_other = 0;
         {
-#if GLF_WIDE_KEYS
-            uint64_t kw = 0, kw_nx;                             // four keys per 8-byte read, the next four requested a group ahead
-            __builtin_memcpy(&kw_nx, kp, 8);                    // (up to seven keys past the slice: inside the key array's slack)
-#else
             uint32_t k_nx = kp[0];
-#endif
-            for (int i = 0; i < (BCFGPU_ABL(P, 4) ? 0 : cnt_raw); ++i) {
-#if GLF_WIDE_KEYS
-                if ((i & 3) == 0) { kw = kw_nx; __builtin_memcpy(&kw_nx, kp + i + 4, 8); } else kw >>= 16;
-                const uint32_t k = (uint32_t)kw & 0xffffu;
-#else
+            for (int i = 0; i < cnt_raw; ++i) {
                 const uint32_t k = k_nx;
                 k_nx = kp[i + 1];                               // one past the slice stays inside the key array's slack
-#endif
                 const uint32_t pb = (k >> 11) & 1u;             // KEY_PRIM
                 qmask |= (uint64_t)pb << KEY_Q(k);
                 n_prim += pb;
@@ -839,16 +612,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
         const char *bbase = reinterpret_cast<const char*>(P.beta);
         const uint32_t brow = n << 3;
 
-        GLF_STAMP(4)
         // ---- errmod_cal: descending walk per base ----
         double bsum[5] = {0, 0, 0, 0, 0};
         uint32_t prim_rev = 0, qs_prim = 0;
         // (a) the primary base
-        if (!BCFGPU_ABL(P, 2)) {
+        {
             const uint16_t *kpp = kp + n_other;               // primary-base keys and zeros (rejected reads)
             const PrimSrc psrc{kpp};
-            const double bs = walk_runs(s_cnt, qmask, s_fk, bbase, tid, brow, psrc, dead_cell ? 0 : cnt_raw - (int)n_other, prim_rev, qs_prim,
-                                        BCFGPU_ABL_MASK(P));
+            const double bs = walk_runs(s_cnt, qmask, s_fk, bbase, tid, brow, psrc, dead_cell ? 0 : cnt_raw - (int)n_other, prim_rev, qs_prim);
             #pragma unroll
             for (int b = 0; b < 5; ++b) if (b == primary) bsum[b] = bs;
         }
@@ -861,9 +632,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
         #pragma unroll
         for (int b = 0; b < 4; ++b) c[b] = (int)((ad64 >> (8 * b)) & 0xff) + (int)((ad64 >> (8 * b + 32)) & 0xff);
         c[4] = (int)n_b4;
-        GLF_STAMP(5)
         // (b) the other bases present in the wave
-        if (!BCFGPU_ABL(P, 2) && !BCFGPU_ABL(P, 32768) && __any(n_other > 0)) {    // (diagnostics: 32768 times the kernel without the other bases' walks)
+        if (__any(n_other > 0)) {
             #pragma unroll 1
             for (int b = 0; b < 5; ++b) {
                 int cb = b == 0 ? c[0] : b == 1 ? c[1] : b == 2 ? c[2] : b == 3 ? c[3] : c[4];
@@ -898,7 +668,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
         }
         const uint32_t n_rev = prim_rev + o_rev;
 
-        GLF_STAMP(6)
         // ---- epilogue of errmod_cal (m=5): float accumulators as in the reference ----
         uint32_t code = 0;
         // The planes' addresses are read here, from device memory, with loads the optimiser must leave in place: as kernel
@@ -912,7 +681,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
             cr.adr = reinterpret_cast<uint32_t*>(t[4]); cr.cnt4 = reinterpret_cast<uint32_t*>(t[5]);
             cr.misc = reinterpret_cast<uint32_t*>(t[6]);
         }
-        if (part && !BCFGPU_ABL(P, 64)) {
+        if (part) {
             const int nbases = (c[0] > 0) + (c[1] > 0) + (c[2] > 0) + (c[3] > 0) + (c[4] > 0);
             if (nbases <= 1) {
                 // one base b (or no read at all): every sum over "the other bases" is bsum[b] or nothing, see CallretPlanes
@@ -980,7 +749,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
         }
     }
 
-    GLF_STAMP(7)
     // ---- flush the workgroup's histograms and site totals ----
     if (LDS_HIST) {
         __syncthreads();
@@ -998,38 +766,22 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ?
             if (v) atomicAdd(&P.site_sums[(size_t)site0 * SITE_NSUM + i], v);
         }
     }
-    GLF_STAMP(8)
 }
 
 size_t glfgen_lds_bytes(int cap, int hist_slots)
 {
-#ifndef GLF_LDS_PAD
-#define GLF_LDS_PAD 0        // (occupancy experiments: bytes of LDS a workgroup asks for and does not use)
-#endif
-    return LDS_HIST_OFF + (size_t)hist_slots * (HP_SIZE * sizeof(int) + SITE_NSUM * 8) + ((size_t)cap + 8) * 2 + GLF_LDS_PAD;
+    return LDS_HIST_OFF + (size_t)hist_slots * (HP_SIZE * sizeof(int) + SITE_NSUM * 8) + ((size_t)cap + 8) * 2;
 }
 
 template <bool INDEL, bool LDS_HIST>
 static void launch_one(const GlfgenParams &p, hipStream_t s, int grid, size_t lds)
 {
-    if (p.keys) {
-        // the two phases as launches of their own: A with the histograms in LDS, B with the key window (and listed cells after it)
-        const size_t lds_a = glfgen_lds_bytes(0, p.hist_slots), lds_b = glfgen_lds_bytes(p.lds_cap, 0);
-        GlfgenParams pb = p;
-        pb.hist_slots = 0;                                  // phase B keeps no histograms: its LDS is fk + run counters + keys
-        if (lds_b > 48 * 1024)
-            hipFuncSetAttribute(reinterpret_cast<const void*>(glfgen_kernel<INDEL, false, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        hipLaunchKernelGGL((glfgen_kernel<INDEL, LDS_HIST, false, 1>), dim3(grid), dim3(WG), lds_a, s, p);
-        hipLaunchKernelGGL((glfgen_kernel<INDEL, false, false, 2>), dim3(grid), dim3(WG), lds_b, s, pb);
-        if (p.deep_cap) hipLaunchKernelGGL((glfgen_kernel<INDEL, false, true, 2>), dim3(p.deep_cap), dim3(WG), glfgen_lds_bytes(0, 0), s, pb);
-        return;
-    }
     if (lds > 48 * 1024)    // per launch, on the device the caller has bound: no process-wide state
-        hipFuncSetAttribute(reinterpret_cast<const void*>(glfgen_kernel<INDEL, LDS_HIST, false, 0>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(glfgen_kernel<INDEL, LDS_HIST, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((glfgen_kernel<INDEL, LDS_HIST, false, 0>), dim3(grid), dim3(WG), lds, s, p);
+    hipLaunchKernelGGL((glfgen_kernel<INDEL, LDS_HIST, false>), dim3(grid), dim3(WG), lds, s, p);
     // the cells the launch above listed (none, as a rule: the workgroups leave at once); no key window in LDS
-    if (p.deep_cap) hipLaunchKernelGGL((glfgen_kernel<INDEL, LDS_HIST, true, 0>), dim3(p.deep_cap), dim3(WG), glfgen_lds_bytes(0, p.hist_slots), s, p);
+    if (p.deep_cap) hipLaunchKernelGGL((glfgen_kernel<INDEL, LDS_HIST, true>), dim3(p.deep_cap), dim3(WG), glfgen_lds_bytes(0, p.hist_slots), s, p);
 }
 
 void launch_glfgen(const GlfgenParams &p, hipStream_t s)

@@ -408,7 +408,7 @@ __global__ __launch_bounds__(256) void probaln_jobs_kernel(const ProbalnParams P
     uint32_t cls = PROBALN_CLS_NONE;
     PJob pj{};
     if (!j.skip && j.l_ref > 0 && j.l_query > 0) {
-        if (j.eff > PROBALN_LDS16_MAX || j.l_ref > 65535 || j.l_query > 65535 || P.force_wide) {
+        if (j.eff > PROBALN_LDS16_MAX || j.l_ref > 65535 || j.l_query > 65535) {
             P.wide[atomicAdd(&P.tot->n_wide, 1u)] = job;
             atomicMax(&P.tot->max_eff, j.eff);
             cls = PROBALN_CLS_WIDE;

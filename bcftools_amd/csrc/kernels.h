@@ -5,18 +5,6 @@
 #include <stdint.h>
 #include "../../include/bcfgpu.h"
 
-// Diagnostics (tools/ablate_kernel.sh builds with -DBCFGPU_DIAG): parts of a kernel can be switched off to time the rest.
-// The product build has no such switch: BCFGPU_ABL() is a compile-time 0 and the parameter blocks carry no mask.
-#ifdef BCFGPU_DIAG
-#define BCFGPU_ABL(P, bit) (((P).ablate & (bit)) != 0)
-#define BCFGPU_ABL_MASK(P) ((P).ablate)
-#define BCFGPU_ABL_FIELD int ablate;
-#else
-#define BCFGPU_ABL(P, bit) false
-#define BCFGPU_ABL_MASK(P) 0
-#define BCFGPU_ABL_FIELD
-#endif
-
 namespace bcfgpu {
 
 // histogram layout of one site (bcf_callaux_t's bias-test arrays, bam2bcf.h:77)
@@ -70,7 +58,6 @@ struct GlfgenParams {
     int lds_cap;                    // read keys held in LDS per workgroup round (multiple of 16, <= 16384)
     int part_cols;                  // LDS columns per partial sum of phase A (power of two >= 4; 12 * hist_slots * part_cols <= 2048: the slot region)
     uint32_t n_reads;               // length of rd/epos (bounds of the vector loads)
-    BCFGPU_ABL_FIELD
     const int8_t   *ref16;
     const uint32_t *off;
     const uint32_t *rd;
@@ -90,10 +77,6 @@ struct GlfgenParams {
     uint32_t *deep_ctr;             // [0] cells listed, [1] keys handed out, [2] set when the list or the scratch ran out (zeroed before launch)
     uint16_t *deep_keys;            // [deep_key_cap] key scratch
     uint32_t deep_cap, deep_key_cap;
-    uint16_t *keys;                 // NULL: one fused kernel; else [n_reads + 64] the keys between the phase-A and the phase-B launch
-#ifdef BCFGPU_DIAG
-    unsigned long long *stamps;     // [16] cycle totals per kernel phase
-#endif
 };
 
 // errmod_cal's draw for over-deep cells (draw.hip): the generator's position, and the plan of the passes about to run
@@ -111,7 +94,6 @@ struct CombineParams {
     const int *hist;
     const unsigned long long *site_sums;   // [n_sites][SITE_NSUM] from glfgen_kernel
     const double *mw;               // [6][6][50]
-    BCFGPU_ABL_FIELD
     int vec4;                       // set by launch_combine: n_smpl % 4 == 0 and all planes 16-byte aligned
     bcfgpu_mplp_out out;
 };
@@ -139,7 +121,6 @@ struct McallParams {
     int out_n_gt_max;               // plane count of out.pl / out.gp
     int *err;                       // device error word
     int small_too;                  // mcall_kernel<5, 15, ...> also takes the sites of at most three alleles (launch_mcall)
-    BCFGPU_ABL_FIELD
 };
 
 // ---- the read pool of a region kept in HBM (bcfgpu_pool_upload; pileup.hip, baq.hip, overlap.hip, capmapq.hip) ----
@@ -240,7 +221,6 @@ struct ProbalnParams {
     int ncell;                                   // scratch cells per row (>= 3*(2*bw+1)+6 for the widest band)
     size_t scratch_stride;                       // jobs per chunk; scratch is [2][ncell][stride] doubles
     double *scratch;
-    int force_wide;                              // tests: every job through the rolling-row version
 };
 void launch_probaln_jobs(const ProbalnParams &p, hipStream_t s);
 void launch_probaln_bounds(const ProbalnParams &p, hipStream_t s);

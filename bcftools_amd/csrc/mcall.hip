@@ -209,11 +209,8 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 // single alleles in permuted order, 5.. the pairs, then the triples, then the row of the samples' normalisation sums; lane l
 // returns slot l >> 2.  HAP: haploid samples take f_a P(aa) + f_b P(bb) (+ f_c P(cc)) (mcall.c:643, 688), samples of ploidy 0
 // enter the single-allele rows only, and (dip_m, dip_e) is the normalisation product over the samples of ploidy 1 or 2.
-#ifndef MCALL_SCAN_INLINE
-#define MCALL_SCAN_INLINE __forceinline__
-#endif
 template <int NZ, bool HAP, int SPL>
-__device__ MCALL_SCAN_INLINE void sparse_scan(const McallParams &P, const uint8_t *plb, const int S, const int nals, const int g, const int ngrp,
+__device__ __forceinline__ void sparse_scan(const McallParams &P, const uint8_t *plb, const int S, const int nals, const int g, const int ngrp,
                                             const int s_first, const int s_last, const float *qf, const uint32_t permw, const double *s_p2, uint8_t *s_nz,
                                             const bool note_nz, double &out_m, int &out_e, double &dip_m, int &dip_e, bool &f_single, bool &f_pt)
 {
@@ -238,13 +235,8 @@ __device__ MCALL_SCAN_INLINE void sparse_scan(const McallParams &P, const uint8_
     // with a ploidy array, the pairs too) from the frequencies alone -- f_a (f_a P(aa) + f_b 2P(ab) + f_c 2P(ac)) + f_b (f_b P(bb) +
     // f_c 2P(bc)) + f_c f_c P(cc): twelve scalar values instead of twenty-four, and the haploid sum falls out of its first terms
     constexpr bool PDIRECT = !HAP;
-    #ifndef MCALL_TRIPLE_DIRECT
-    #define MCALL_TRIPLE_DIRECT 0
-    #endif
-    constexpr bool TDIRECT = !HAP && MCALL_TRIPLE_DIRECT;      // (24 more scalar registers: measured, profiles/r5_mcall_sparse.txt)
     double k_a2[NP > 0 ? NP : 1], k_b2[NP > 0 ? NP : 1], k_ab[NP > 0 ? NP : 1], k_pa[NP > 0 ? NP : 1], k_pb[NP > 0 ? NP : 1];
     double k_ta[NT > 0 ? NT : 1], k_tb[NT > 0 ? NT : 1], k_tc[NT > 0 ? NT : 1];
-    double k_t2[NT > 0 ? NT : 1][6];                             // TDIRECT: f_a^2, f_b^2, f_c^2, 2 f_a f_b, 2 f_a f_c, 2 f_b f_c
     {
         const double a2 = cfa * cfa, b2 = cfb * cfb, ab = 2 * cfa * cfb;
         #pragma unroll
@@ -253,12 +245,7 @@ __device__ MCALL_SCAN_INLINE void sparse_scan(const McallParams &P, const uint8_
             else { k_pa[i] = readlane_f64(cfa, i); k_pb[i] = readlane_f64(cfb, i); }
         }
         #pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            if (TDIRECT) {
-                k_t2[i][0] = readlane_f64(a2, 6 + i); k_t2[i][1] = readlane_f64(b2, 6 + i); k_t2[i][2] = readlane_f64(cfc * cfc, 6 + i);
-                k_t2[i][3] = readlane_f64(ab, 6 + i); k_t2[i][4] = readlane_f64(2 * cfa * cfc, 6 + i); k_t2[i][5] = readlane_f64(2 * cfb * cfc, 6 + i);
-            } else { k_ta[i] = readlane_f64(cfa, 6 + i); k_tb[i] = readlane_f64(cfb, 6 + i); k_tc[i] = readlane_f64(cfc, 6 + i); }
-        }
+        for (int i = 0; i < NT; ++i) { k_ta[i] = readlane_f64(cfa, 6 + i); k_tb[i] = readlane_f64(cfb, 6 + i); k_tc[i] = readlane_f64(cfc, 6 + i); }
     }
     double man[16]; int ex[16];
     #pragma unroll
@@ -273,7 +260,7 @@ __device__ MCALL_SCAN_INLINE void sparse_scan(const McallParams &P, const uint8_
     }
     // A lane takes SPL = four consecutive samples, one 4-byte word per plane: 256 samples a trip; SPL = 1 (a byte per plane) for a range of
     // at most 128 samples -- a small group: 38 samples of 1000 in 26 populations would keep ten lanes busy at four a lane.
-    for (int s0 = s_first; s0 < (BCFGPU_ABL(P, 16) ? 0 : s_last); s0 += SPL * WGS) {
+    for (int s0 = s_first; s0 < s_last; s0 += SPL * WGS) {
         const int sb = s0 + SPL * tid, rem = S - sb;
         const bool live = rem > 0 && sb < s_last;
         // permuted genotype slot c is loaded from the plane lane c of `offv` names (one v_readlane per plane and trip)
@@ -356,7 +343,6 @@ __device__ MCALL_SCAN_INLINE void sparse_scan(const McallParams &P, const uint8_
                     const bool dipl = !HAP || pd == 2;
                     // twice the heterozygous values (exact), for the forms built from the frequencies alone
                     double h2[10];
-                    if (!(PDIRECT && TDIRECT))
                     #pragma unroll
                     for (int x = 1; x < NZ; ++x)
                         #pragma unroll
@@ -377,12 +363,6 @@ __device__ MCALL_SCAN_INLINE void sparse_scan(const McallParams &P, const uint8_
                     #pragma unroll
                     for (int i = 0; i < NT; ++i) {
                         const int x = TX[i], y = TY[i], z = TW[i];
-                        if (TDIRECT) {
-                            man[5 + NP + i] *= __builtin_fma(k_t2[i][5], p[y * (y + 1) / 2 + z], __builtin_fma(k_t2[i][4], p[x * (x + 1) / 2 + z],
-                                               __builtin_fma(k_t2[i][3], p[x * (x + 1) / 2 + y], __builtin_fma(k_t2[i][2], p[z * (z + 3) / 2],
-                                               __builtin_fma(k_t2[i][1], p[y * (y + 3) / 2], k_t2[i][0] * p[x * (x + 3) / 2])))));
-                            continue;
-                        }
                         const double ta = k_ta[i] * p[x * (x + 3) / 2], tb = k_tb[i] * p[y * (y + 3) / 2], tc = k_tc[i] * p[z * (z + 3) / 2];
                         const double ua = __builtin_fma(k_tc[i], h2[x * (x - 1) / 2 + z], __builtin_fma(k_tb[i], h2[x * (x - 1) / 2 + y], ta));
                         const double ub = __builtin_fma(k_tc[i], h2[y * (y - 1) / 2 + z], tb);
@@ -478,7 +458,6 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
     // the instantiations share the grid: sites with <=3 alleles run in the small one, the rest in the general ones -- or, with
     // many samples (launch_mcall), in mcall_kernel<5, 15, ...> as well, and the small one is not launched
     if (P.small_too ? (nals <= 3 && NSUB == 25) : (nals <= 3) != (MAXA == 3)) return;
-    if (BCFGPU_ABL(P, 8)) return;
 
     // record-loop prologue of vcfcall.c:1112-1115: with -v a REF-only record never reaches mcall()
     if ((P.call_flag & BCFGPU_CALL_VARONLY) && (nals == 1 || (nals == 2 && unseen > 0))) {
@@ -830,7 +809,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
             const int s_first = (ngrp > 1 && P.grp_rng) ? (min(P.grp_rng[3 * g], s_last) & ~3) : 0;
             const int span = s_last - s_first;
             const int nq = span > 128 ? 4 : span > 64 ? 2 : 1;
-            for (int s0 = s_first; s0 < (BCFGPU_ABL(P, 16) ? 0 : s_last); s0 += 64 * nq) {
+            for (int s0 = s_first; s0 < s_last; s0 += 64 * nq) {
                 const int sb0 = s0 + 4 * nq * col;
                 uint32_t wq[4][4], pwq[4], gmq[4];
                 #pragma unroll
@@ -956,7 +935,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
         // (a group no sample belongs to keeps {INT_MAX, 0, 0}: an empty range, not a start that overflows when tid is added)
         const int g_last = (ngrp > 1 && P.grp_rng) ? P.grp_rng[3 * g + 1] : S;
         const int g_first = (ngrp > 1 && P.grp_rng) ? min(P.grp_rng[3 * g], g_last) : 0;
-        for (int s = g_first + tid; s < (BCFGPU_ABL(P, 16) ? 0 : g_last); s += WGS) {
+        for (int s = g_first + tid; s < g_last; s += WGS) {
             if (ngrp > 1 && GRP_OF(s) != g) continue;
             int pl[NG]; double pdg[NG];
             load_pl<NG>(P, is, s, ngts, pl);
@@ -1175,7 +1154,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
     // A site that stays REF-only (most of them) needs of its samples only "any data at all?" (mcall_set_ref_genotypes,
     // mcall.c:529-541): four samples a lane and a 4-byte store per GT plane, from the subset scan's notes or (sample groups)
     // from a 4-byte load per PL plane -- four trips to memory for 1000 samples where the general loop below makes sixteen
-    bool gt_done = BCFGPU_ABL(P, 32);
+    bool gt_done = false;
     if constexpr (FAST) {
         int8_t *gt0 = P.out.gt + (size_t)is * 2 * Ss;
         if (!gt_done && !is_variant && ref_only && !(S & 3) && !(((uintptr_t)plb2 | (uintptr_t)gt0) & 3)) {
@@ -1462,7 +1441,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
             if (chain && P.grp_rng[3 * cg + 2]) cspan = P.grp_rng[3 * cg + 1] - (P.grp_rng[3 * cg] & ~3);
             float gacc = 0.f;
             fetch_at(lane_s(0));
-            for (int r = 0; r < (BCFGPU_ABL(P, 128) ? 0 : rounds); ++r) {
+            for (int r = 0; r < rounds; ++r) {
                 __syncthreads();                                         // (the chains of the round before are through with s_fr)
                 int xc[5][4];
                 #pragma unroll
@@ -1522,7 +1501,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
             cur = -1;                                                     // (nothing left in the running-group register)
         } else {
         fetch_ad(0);
-        for (int base = 0; base < (BCFGPU_ABL(P, 128) ? 0 : S); base += SB) {
+        for (int base = 0; base < S; base += SB) {
             const int cn = min(SB, S - base);
             __syncthreads();
             int xc[5][4], gcur[4];
@@ -1669,7 +1648,7 @@ void launch_mcall(const McallParams &p_in, hipStream_t s)
         if (!p.small_too) hipLaunchKernelGGL((mcall_kernel<3, 7, FAST_, HAP_, GRP_>), dim3(p.n_sites), dim3(WGS), lds, s, p); \
         hipLaunchKernelGGL((mcall_kernel<5, 15, FAST_, HAP_, GRP_>), dim3(p.n_sites), dim3(WGS), lds, s, p); \
         hipLaunchKernelGGL((mcall_kernel<5, 25, FAST_, HAP_, GRP_>), dim3(p.n_sites), dim3(WGS), lds, s, p); } while (0)
-    if (p.pl_is_u8 && !BCFGPU_ABL(p, 64)) {
+    if (p.pl_is_u8) {
         // u8 PLs (the fused pipeline): the lane-per-sample subset scan (matrix cores for 25 subsets); the haploid forms only with a ploidy
         // array, the group handling only with more than one group
         if (p.ploidy) MCALL_LAUNCH3(true, true, true);

@@ -461,7 +461,7 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
         }
         g.lds_cap = cap;
         int pc = 64;
-        while (pc > 4 && 12 * std::max(g.hist_slots, 1) * pc > 2048) pc >>= 1;
+        while (pc > 4 && 17 * std::max(g.hist_slots, 1) * pc > 2048) pc >>= 1;      // glfgen.hip: NPART values per slot
         g.part_cols = pc;
     }
     g.n_reads = (uint32_t)tile->n_reads;

@@ -63,7 +63,10 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 // REF / ALT choice is the increment instead of an address.
 #define HP_SIZE 280
 #define HP_MQS  220
-#define NPART 12           // per-lane partial sums of phase A: the I16 site totals anno[4..15]
+// per-lane partial sums of phase A: the I16 site totals anno[4..15], ori_depth and mq0 (site_sums[0..13]), then the reads of
+// mapQ >= 59: all, REF base, reverse strand (the mapQ 59 bins of the four mapQ histograms).  csrc/api.hip sizes part_cols by it.
+#define NPART 17
+static_assert(NPART == SITE_NSUM + 3, "phase A's partial sums: the site totals and three mapQ >= 59 counts");
 
 // the u16 key phase A leaves for phase B
 #define KEY_PACK(rev, q, b, sc) ((uint32_t)(rev) | (uint32_t)(q) << 1 | (uint32_t)(b) << 7 | (uint32_t)(sc) << 10)
@@ -221,12 +224,30 @@ struct ReadSums {
     uint32_t d_bq, d_bq2, d_mq, d_mq2, d_md, d_md2;    // the "diff" reads among them (is_diff of bam2bcf.c:186,195)
     __device__ __forceinline__ void clear() { t_bq = t_bq2 = t_mq = t_mq2 = t_md = t_md2 = d_bq = d_bq2 = d_mq = d_mq2 = d_md = d_md2 = 0; }
 };
-typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
-// wave-uniform counts of phase A (ballots: scalar registers)
-struct WaveCounts {
-    uint32_t ori, mq0, ref59, alt59, fwd59, rev59;
-    __device__ __forceinline__ void clear() { ori = mq0 = ref59 = alt59 = fwd59 = rev59 = 0; }
+// per-lane counts of phase A (vector registers; added up with the partial sums once per site segment)
+struct ReadCounts {
+    uint32_t ori, mq0, m59, ref59, rev59;               // seen reads, mapQ 0, mapQ >= 59 (all / REF base / reverse strand)
+    __device__ __forceinline__ void clear() { ori = mq0 = m59 = ref59 = rev59 = 0; }
 };
+typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
+
+// Byte planes: the four reads of a lane side by side, read u in byte u of a dword.  Most of phase A works on the planes, a
+// byte or a 16-bit half per read and four or two reads per instruction; flags are bit 7 of a read's byte ("80 masks").
+__device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+#define SEL_EVEN 0x0c020c00u                   // plane -> reads 0 and 2 as the two u16 halves
+#define SEL_ODD  0x0c030c01u                   // plane -> reads 1 and 3
+#define SEL_JOIN 0x06020400u                   // perm(odd, even, SEL_JOIN): the two halves' low bytes back to a plane
+#define SEL_GE8  0x07030501u                   // perm(odd, even, SEL_GE8): bit 8 of every half -> bit 0 of the read's byte
+__device__ __forceinline__ v2u16 as_v2(uint32_t x) { return __builtin_bit_cast(v2u16, x); }
+__device__ __forceinline__ uint32_t as_u(v2u16 x) { return __builtin_bit_cast(uint32_t, x); }
+__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_min(as_v2(a), as_v2(b))); }
+__device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) { return as_u(__builtin_elementwise_max(as_v2(a), as_v2(b))); }
+// 0x80 in every byte that is not zero
+__device__ __forceinline__ uint32_t nonzero80(uint32_t x) { return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
+// an 80 mask widened to whole bytes
+__device__ __forceinline__ uint32_t bytes_of80(uint32_t m) { return m | (m - (m >> 7)); }
+// byte u of x (u a constant)
+__device__ __forceinline__ uint32_t byte_at(uint32_t x, int u) { return (x >> (8 * u)) & 0xffu; }
 
 // DEEP = false: the tile, 256 consecutive cells per workgroup.  A cell with more pileup entries than the LDS key window holds is
 // not worked on here: it is listed (P.deep_*), and the launch that follows (DEEP = true) gives each listed cell a workgroup
@@ -330,101 +351,115 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
             const unsigned long long tbl = (NT16_INT_TBL & ~0xfull) | (unsigned long long)ref4;
             int *hist = LDS_HIST ? s_hist + (sg - site0) * HP_SIZE : P.hist + (long)sg * H_SIZE;
             ReadSums A; A.clear();
-            WaveCounts C; C.clear();
+            ReadCounts C; C.clear();
+            // the constants of the planes: base 0..4 of a nt16 code by v_perm (codes 0..7 and 8..15, indexed by the low three
+            // bits), the byte test baseQ >= min_baseQ (K + baseQ has bit 8 set), the segment's codes in every byte
+            const uint32_t tlo_lo = 0x04010000u | ref4, tlo_hi = 0x04040402u, thi_lo = 0x04040403u, thi_hi = 0x04040404u;
+            const uint32_t kq = 0x01000100u - min(min_baseQ, 256u) * 0x00010001u;
+            const uint32_t cap2 = min(capQ, 0xffffu) * 0x00010001u;
+            const uint32_t refb4 = (uint32_t)(ref_base & 15) * 0x01010101u, prim4 = primq * 0x01010101u;
+            const uint32_t scm = want_scr ? 0x04040404u : 0u;
+            const bool all_diff = !INDEL && ref4 >= 4;
+            const bool no_ref = INDEL || ref_base < 0 || ref_base > 15;          // (isref below compares the nt16 codes)
 
-            // Four consecutive reads of every lane.  Called in wave-uniform control flow only (the ballots count whole waves
-            // into scalar registers).  CHECK: reads outside [rb, re) are masked (`vm`, one bit per read).
-            // The I16 sums take the reads in pairs: the fields of two reads side by side as u16, one v_dot2_u32_u16 per sum
-            // (a rejected read is a zero record and contributes zeros).
-            auto quad = [&](const uint32_t (&wv)[4], const uint32_t (&av)[4], uint32_t e4, uint32_t vm, uint32_t (&kv)[4]) {
-                uint32_t bqz[4], mqz[4], mdz[4];
-                bool dif[4];
+            // Four consecutive reads of the lane, `vm4`: 0xff in the bytes of the reads inside [rb, re).  Per-lane control
+            // flow only: any lane may run this on its own.
+            auto quad = [&](const uint4 &w4, const uint4 &a4, uint32_t e4, uint32_t vm4, uint32_t &k01, uint32_t &k23) {
+                // the rd words as byte planes: baseQ, mapQ, flags (nt16 | rev << 4 | sclip << 5 | DEL << 6 | SKIP << 7), min_dist
+                const uint32_t t0 = perm(w4.y, w4.x, 0x05010400u), t1 = perm(w4.y, w4.x, 0x07030602u);
+                const uint32_t t2 = perm(w4.w, w4.z, 0x05010400u), t3 = perm(w4.w, w4.z, 0x07030602u);
+                uint32_t B4 = perm(t2, t0, 0x05040100u);
+                const uint32_t M4 = perm(t2, t0, 0x07060302u);
+                const uint32_t F4 = (vm4 & perm(t3, t1, 0x05040100u)) | (~vm4 & 0x80808080u);     // a read outside the segment: SKIP
+                const uint32_t D4 = perm(t3, t1, 0x07060302u);
+                uint32_t QR4, BB4;                                // q before the mapQ cap, base 0..4
+                uint32_t ok80;
+                const uint32_t seen80 = (INDEL ? F4 : F4 | F4 << 1) & 0x80808080u ^ 0x80808080u;   // !SKIP (SNP: and !DEL)
+                if (INDEL) {
+                    // the aux words: baseQ | seqQ << 8 | base << 16 (bam2bcf_indel.c:449-456), a read at a time
+                    uint32_t qv[4], bv[4];
+                    const uint32_t av[4] = { a4.x, a4.y, a4.z, a4.w }, wv[4] = { w4.x, w4.y, w4.z, w4.w };
+                    #pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const uint32_t ax = av[u];
+                        uint32_t b = (ax >> 16) & 0xf, q = ax & 0xff;
+                        if (q < min_baseQ) { b = 0; q = wv[u] & 0xff; }
+                        bv[u] = min(b, 4u);
+                        qv[u] = min(q, (ax >> 8) & 0xff);
+                    }
+                    B4 = perm(perm(a4.w, a4.z, 0x04000c0cu), perm(a4.y, a4.x, 0x0c0c0400u), 0x07060100u);
+                    QR4 = qv[0] | qv[1] << 8 | qv[2] << 16 | qv[3] << 24;
+                    BB4 = bv[0] | bv[1] << 8 | bv[2] << 16 | bv[3] << 24;
+                    ok80 = seen80;
+                } else {
+                    const uint32_t ge = perm(perm(0, B4, SEL_ODD) + kq, perm(0, B4, SEL_EVEN) + kq, SEL_GE8);
+                    ok80 = seen80 & ge << 7;
+                    QR4 = B4;
+                    const uint32_t s = F4 & 0x07070707u;
+                    BB4 = perm(perm(thi_hi, thi_lo, s), perm(tlo_hi, tlo_lo, s), 0x03020100u | (F4 >> 1 & 0x04040404u));
+                }
+                const uint32_t OK4 = bytes_of80(ok80);
+                // mapQ: 255 -> DEF_MAPQ, then min(mapQ, capQ); two reads an instruction
+                const uint32_t me = perm(0, M4, SEL_EVEN), mo = perm(0, M4, SEL_ODD);
+                const uint32_t mfe = pk_min(me + (uint32_t)__mul24((int)perm(0, me + 0x00010001u, SEL_ODD), DEF_MAPQ - 255), cap2);
+                const uint32_t mfo = pk_min(mo + (uint32_t)__mul24((int)perm(0, mo + 0x00010001u, SEL_ODD), DEF_MAPQ - 255), cap2);
+                // q = clamp(min(q, mapQ), 4, 63)
+                const uint32_t qe = pk_max(pk_min(pk_min(perm(0, QR4, SEL_EVEN), mfe), 0x003f003fu), 0x00040004u);
+                const uint32_t qo = pk_max(pk_min(pk_min(perm(0, QR4, SEL_ODD), mfo), 0x003f003fu), 0x00040004u);
+                const uint32_t Q4 = perm(qo, qe, SEL_JOIN);
+                const uint32_t Mf4 = perm(mfo, mfe, SEL_JOIN);
+                const uint32_t Df4 = perm(pk_min(perm(0, D4, SEL_ODD), 0x00190019u), pk_min(perm(0, D4, SEL_EVEN), 0x00190019u), SEL_JOIN);
+                // the counts: seen reads, mapQ 0 and mapQ >= 59 of the accepted ones
+                const uint32_t m59_80 = ok80 & perm(mfo + 0x00c500c5u, mfe + 0x00c500c5u, SEL_GE8) << 7;     // 59 + 197 = 256
+                const uint32_t nref80 = no_ref ? 0x80808080u : nonzero80((F4 ^ refb4) & 0x0f0f0f0fu);      // nt != the reference's code
+                C.ori += __builtin_popcount(seen80);
+                C.mq0 += __builtin_popcount(ok80 & ~nonzero80(M4));
+                C.m59 += __builtin_popcount(m59_80);
+                C.ref59 += __builtin_popcount(m59_80 & ~nref80);
+                C.rev59 += __builtin_popcount(m59_80 & F4 << 3);
+                // the keys: byte lo = rev | q << 1 | base << 7, byte hi = base >> 1 | sclip << 2 | primary << 3; zero when rejected
+                const uint32_t nprim80 = nonzero80(BB4 ^ prim4);
+                const uint32_t klo = (((F4 >> 4) & 0x01010101u) | Q4 << 1 | (BB4 & 0x01010101u) << 7) & OK4;
+                const uint32_t khi = (((BB4 >> 1) & 0x03030303u) | ((F4 >> 3) & scm) | ((nprim80 ^ 0x80808080u) >> 4)) & OK4;
+                k01 = perm(khi, klo, 0x05010400u); k23 = perm(khi, klo, 0x07030602u);
+                // the I16 sums: Σ x and Σ x² of the accepted reads, four reads a v_dot4_u32_u8
+                const uint32_t Bm = B4 & OK4, Mm = Mf4 & OK4, Dm = Df4 & OK4;
+                A.t_bq = __builtin_amdgcn_udot4(Bm, 0x01010101u, A.t_bq, false); A.t_bq2 = __builtin_amdgcn_udot4(Bm, Bm, A.t_bq2, false);
+                A.t_mq = __builtin_amdgcn_udot4(Mm, 0x01010101u, A.t_mq, false); A.t_mq2 = __builtin_amdgcn_udot4(Mm, Mm, A.t_mq2, false);
+                A.t_md = __builtin_amdgcn_udot4(Dm, 0x01010101u, A.t_md, false); A.t_md2 = __builtin_amdgcn_udot4(Dm, Dm, A.t_md2, false);
+                const uint32_t dif80 = ok80 & (all_diff ? 0x80808080u : nprim80);                     // is_diff (bam2bcf.c:186,195)
+                if (dif80) {                                      // rare: sequencing errors and the ALT reads of variant sites
+                    const uint32_t DM = bytes_of80(dif80);
+                    const uint32_t bd = Bm & DM, qd = Mm & DM, dd = Dm & DM;
+                    A.d_bq = __builtin_amdgcn_udot4(bd, 0x01010101u, A.d_bq, false); A.d_bq2 = __builtin_amdgcn_udot4(bd, bd, A.d_bq2, false);
+                    A.d_mq = __builtin_amdgcn_udot4(qd, 0x01010101u, A.d_mq, false); A.d_mq2 = __builtin_amdgcn_udot4(qd, qd, A.d_mq2, false);
+                    A.d_md = __builtin_amdgcn_udot4(dd, 0x01010101u, A.d_md, false); A.d_md2 = __builtin_amdgcn_udot4(dd, dd, A.d_md2, false);
+                }
+                // bias-test histograms, a read at a time: ibq = (int)(baseQ/60.*60) is the identity on 0..59 (checked in tests).
+                // The mapQ >= 59 bins of the four mapQ histograms (most reads) are the counts above; every ALT array sits
+                // H_ALT_OFF after its REF array.
                 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const uint32_t w = wv[u];
-                    const bool valid = (vm >> u) & 1;
-                    uint32_t q, b, bq, mapQ, md;
-                    bool ok, seen;
-                    const uint32_t nt = (w >> 16) & 15;
-                    if (INDEL) {
-                        const uint32_t ax = av[u];
-                        b = (ax >> 16) & 0xf;                     // 0..4 after bcf_call_gap_prep (bam2bcf_indel.c:449-456)
-                        bq = q = ax & 0xff;
-                        if (q < min_baseQ) { b = 0; q = w & 0xff; }
-                        b = min(b, 4u);
-                        q = min(q, (ax >> 8) & 0xff);             // seqQ
-                        seen = valid && !(w & BCFGPU_RD_SKIP);
-                        ok = seen;
-                        mapQ = (w >> 8) & 0xff; md = w >> 24;
-                        if (!ok) { bq = 0; mapQ = 0; md = 0; }
-                    } else {
-                        seen = valid && !(w & (BCFGPU_RD_SKIP | BCFGPU_RD_DEL));
-                        ok = seen && (w & 0xff) >= min_baseQ;
-                        const uint32_t wz = ok ? w : 0u;          // a rejected read: a zero record
-                        bq = q = wz & 0xff;                       // seqQ = 99 never binds: q is capped by capQ <= 63 below
-                        mapQ = (wz >> 8) & 0xff; md = wz >> 24;
-                        b = (uint32_t)((tbl >> (4 * nt)) & 7);
-                    }
-                    const unsigned long long b_ok = __ballot(ok);
-                    C.ori += (uint32_t)__popcll(__ballot(seen));
-                    if (mapQ == 255) mapQ = DEF_MAPQ;
-                    C.mq0 += (uint32_t)__popcll(__ballot(mapQ == 0) & b_ok);
-                    mapQ = min(mapQ, capQ);
-                    q = max(min(min(q, mapQ), 63u), 4u);
-                    md = min(md, (uint32_t)CAP_DIST);
-                    const uint32_t rev = (w >> 20) & 1;
-                    uint32_t key = KEY_PACK(rev, q, b, 0) | (b == primq ? KEY_PRIM : 0u);
-                    if (want_scr) key |= ((w >> 21) & 1) << 10;
-                    kv[u] = ok ? key : 0u;
-                    bqz[u] = bq; mqz[u] = mapQ; mdz[u] = md;
-                    dif[u] = ok && (INDEL ? b != 0 : !(ref4 < 4 && b == ref4));
-                    // bias-test histograms: ibq = (int)(baseQ/60.*60) is the identity on 0..59 (checked in tests).
-                    // The mapQ >= 59 bins of the four mapQ histograms (most reads) are counted by ballot; every ALT array sits
-                    // H_ALT_OFF after its REF array.
-                    const bool isref = (int)nt == ref_base;
-                    const bool m59 = mapQ >= 59;
-                    {
-                        const unsigned long long b59 = __ballot(m59) & b_ok, bref = __ballot(isref), brev = __ballot(rev != 0);
-                        C.ref59 += (uint32_t)__popcll(b59 & bref); C.alt59 += (uint32_t)__popcll(b59 & ~bref);
-                        C.rev59 += (uint32_t)__popcll(b59 & brev); C.fwd59 += (uint32_t)__popcll(b59 & ~brev);
-                    }
-                    if (ok) {
-                        if (LDS_HIST) {
-                            const int inc = isref ? 1 : 0x10000;
-                            atomicAdd(&hist[H_REF_POS + ((e4 >> (8 * u)) & 0xff)], inc);
-                            atomicAdd(&hist[H_REF_BQ + min(bq, 59u)], inc);
-                            if (!m59) {
-                                atomicAdd(&hist[H_REF_MQ + mapQ], inc);
-                                atomicAdd(&hist[HP_MQS + mapQ], rev ? 0x10000 : 1);
-                            }
-                        } else {
-                            const uint32_t aoff = isref ? 0u : (uint32_t)H_ALT_OFF;
-                            atomicAdd(&hist[aoff + H_REF_POS + ((e4 >> (8 * u)) & 0xff)], 1);
-                            atomicAdd(&hist[aoff + H_REF_BQ + min(bq, 59u)], 1);
-                            if (!m59) {
-                                atomicAdd(&hist[aoff + H_REF_MQ + mapQ], 1);
-                                atomicAdd(&hist[(rev ? H_REV_MQS : H_FWD_MQS) + mapQ], 1);
-                            }
+                    if (!((ok80 >> (8 * u + 7)) & 1)) continue;
+                    const bool isref = !((nref80 >> (8 * u + 7)) & 1), rev = (F4 >> (8 * u + 4)) & 1;
+                    const uint32_t bq = byte_at(B4, u), mapQ = byte_at(Mf4, u), pos = byte_at(e4, u);
+                    const bool m59 = (m59_80 >> (8 * u + 7)) & 1;
+                    if (LDS_HIST) {
+                        const int inc = isref ? 1 : 0x10000;
+                        atomicAdd(&hist[H_REF_POS + pos], inc);
+                        atomicAdd(&hist[H_REF_BQ + min(bq, 59u)], inc);
+                        if (!m59) {
+                            atomicAdd(&hist[H_REF_MQ + mapQ], inc);
+                            atomicAdd(&hist[HP_MQS + mapQ], rev ? 0x10000 : 1);
                         }
-                    }
-                }
-                #pragma unroll
-                for (int h = 0; h < 4; h += 2) {
-                    const v2u16 one2 = { 1, 1 };
-                    const v2u16 bq2 = __builtin_bit_cast(v2u16, bqz[h] | bqz[h + 1] << 16);
-                    const v2u16 mq2 = __builtin_bit_cast(v2u16, mqz[h] | mqz[h + 1] << 16);
-                    const v2u16 md2 = __builtin_bit_cast(v2u16, mdz[h] | mdz[h + 1] << 16);
-                    A.t_bq = __builtin_amdgcn_udot2(bq2, one2, A.t_bq, false); A.t_bq2 = __builtin_amdgcn_udot2(bq2, bq2, A.t_bq2, false);
-                    A.t_mq = __builtin_amdgcn_udot2(mq2, one2, A.t_mq, false); A.t_mq2 = __builtin_amdgcn_udot2(mq2, mq2, A.t_mq2, false);
-                    A.t_md = __builtin_amdgcn_udot2(md2, one2, A.t_md, false); A.t_md2 = __builtin_amdgcn_udot2(md2, md2, A.t_md2, false);
-                    if (__any(dif[h] || dif[h + 1])) {           // rare: sequencing errors and the ALT reads of variant sites
-                        const uint32_t dm = (dif[h] ? 0xffffu : 0u) | (dif[h + 1] ? 0xffff0000u : 0u);
-                        const v2u16 bd = __builtin_bit_cast(v2u16, __builtin_bit_cast(uint32_t, bq2) & dm);
-                        const v2u16 qd = __builtin_bit_cast(v2u16, __builtin_bit_cast(uint32_t, mq2) & dm);
-                        const v2u16 dd = __builtin_bit_cast(v2u16, __builtin_bit_cast(uint32_t, md2) & dm);
-                        A.d_bq = __builtin_amdgcn_udot2(bd, one2, A.d_bq, false); A.d_bq2 = __builtin_amdgcn_udot2(bd, bd, A.d_bq2, false);
-                        A.d_mq = __builtin_amdgcn_udot2(qd, one2, A.d_mq, false); A.d_mq2 = __builtin_amdgcn_udot2(qd, qd, A.d_mq2, false);
-                        A.d_md = __builtin_amdgcn_udot2(dd, one2, A.d_md, false); A.d_md2 = __builtin_amdgcn_udot2(dd, dd, A.d_md2, false);
+                    } else {
+                        const uint32_t aoff = isref ? 0u : (uint32_t)H_ALT_OFF;
+                        atomicAdd(&hist[aoff + H_REF_POS + pos], 1);
+                        atomicAdd(&hist[aoff + H_REF_BQ + min(bq, 59u)], 1);
+                        if (!m59) {
+                            atomicAdd(&hist[aoff + H_REF_MQ + mapQ], 1);
+                            atomicAdd(&hist[(rev ? H_REV_MQS : H_FWD_MQS) + mapQ], 1);
+                        }
                     }
                 }
             };
@@ -450,57 +485,47 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                 }
             };
             fetch(g0 + 4u * tid);
-            const uint32_t ntrip = (re - g0 + 4u * WG - 1) / (4u * WG);       // uniform trip count: the ballots need whole waves
-            for (uint32_t it = 0; it < ntrip; ++it) {
-                const uint32_t i4 = g0 + 4u * tid + it * (4u * WG);
-                if (__all(i4 >= re)) break;                      // the wavefront is past the segment's last read (the last trip's upper waves)
-                const uint32_t wv[4] = { w4n.x, w4n.y, w4n.z, w4n.w };
-                const uint32_t av[4] = { a4n.x, a4n.y, a4n.z, a4n.w };
+            for (uint32_t i4 = g0 + 4u * tid; i4 < re; i4 += 4u * WG) {
+                const uint4 w4 = w4n, a4 = a4n;
                 const uint32_t e4 = e4n;
                 fetch(i4 + 4u * WG);                             // the next trip's loads fly while this one is worked on
+                // the reads of [i4, i4 + 4) inside [rb, re): bytes lo .. hi-1 (i4 >= g0 = rb & ~3, so lo <= 3)
+                const uint32_t lo = rb > i4 ? rb - i4 : 0u, hi = min(re - i4, 4u);
+                const uint32_t vm4 = (0xffffffffu << (8 * lo)) & (hi == 4u ? 0xffffffffu : ~(0xffffffffu << (8 * hi)));
+                uint32_t k01, k23;
+                quad(w4, a4, e4, vm4, k01, k23);
                 const uint32_t ko = i4 - abase;
-                if (__all(i4 >= rb && i4 + 3 < re)) {            // the whole wave inside the segment: no range checks, 8-byte LDS stores
-                    uint32_t kv[4];
-                    quad(wv, av, e4, 15u, kv);
-                    *reinterpret_cast<uint2*>(s_key + ko) = make_uint2(kv[0] | kv[1] << 16, kv[2] | kv[3] << 16);
-                } else {                                         // a wave at a ragged end of the segment
-                    uint32_t kv[4], vm = 0;
+                if (vm4 == 0xffffffffu) {                        // the four reads inside the segment: one 8-byte LDS store
+                    *reinterpret_cast<uint2*>(s_key + ko) = make_uint2(k01, k23);
+                } else {                                         // a lane at a ragged end of the segment
+                    const uint32_t kv[4] = { k01 & 0xffffu, k01 >> 16, k23 & 0xffffu, k23 >> 16 };
                     #pragma unroll
-                    for (int u = 0; u < 4; ++u) vm |= (i4 + u >= rb && i4 + u < re) ? 1u << u : 0u;
-                    quad(wv, av, e4, vm, kv);
-                    #pragma unroll
-                    for (int u = 0; u < 4; ++u) if ((vm >> u) & 1) s_key[ko + u] = (uint16_t)kv[u];
+                    for (int u = 0; u < 4; ++u) if ((vm4 >> (8 * u)) & 1) s_key[ko + u] = (uint16_t)kv[u];
                 }
             }
             // ---- the segment's site totals ----
-            // LDS mode: every lane adds its partial sums to its own column of the slot's [value][64] table (no conflicts
-            // inside a wave); the 64 columns are added up once, when the workgroup is through (below).
+            // LDS mode: every lane adds its partial sums and counts to its own column of the slot's [value][pcol] table (no
+            // conflicts inside a wave); the columns are added up once, when the workgroup is through (below).
             const uint32_t v[NPART] = { A.t_bq - A.d_bq, A.t_bq2 - A.d_bq2, A.d_bq, A.d_bq2, A.t_mq - A.d_mq, A.t_mq2 - A.d_mq2, A.d_mq, A.d_mq2,
-                                        A.t_md - A.d_md, A.t_md2 - A.d_md2, A.d_md, A.d_md2 };
-            unsigned long long *tot = LDS_HIST ? s_tot + (sg - site0) * SITE_NSUM : P.site_sums + (size_t)sg * SITE_NSUM;
+                                        A.t_md - A.d_md, A.t_md2 - A.d_md2, A.d_md, A.d_md2, C.ori, C.mq0, C.m59, C.ref59, C.rev59 };
             if (LDS_HIST) {
                 uint32_t *pt = s_part + (sg - site0) * (NPART * pcol) + (tid & (pcol - 1));
                 #pragma unroll
                 for (int j = 0; j < NPART; ++j) atomicAdd(&pt[j * pcol], v[j]);
             } else {
                 // global mode (many sites per workgroup, i.e. very few samples): wave sums, one atomic per wave and value
+                unsigned long long *tot = P.site_sums + (size_t)sg * SITE_NSUM;
+                uint32_t x[NPART];
                 #pragma unroll
-                for (int j = 0; j < NPART; ++j) {
-                    const uint32_t x = wave_sum_u32(v[j]);
-                    if ((tid & 63) == 0 && x) atomicAdd(&tot[j], (unsigned long long)x);
-                }
-            }
-            if ((tid & 63) == 0) {                               // the wave-uniform counts
-                if (C.ori) atomicAdd(&tot[12], (unsigned long long)C.ori);
-                if (C.mq0) atomicAdd(&tot[13], (unsigned long long)C.mq0);
-                if (LDS_HIST) {
-                    if (C.ref59 | C.alt59) atomicAdd(&hist[H_REF_MQ + 59], (int)(C.ref59 | C.alt59 << 16));
-                    if (C.fwd59 | C.rev59) atomicAdd(&hist[HP_MQS + 59], (int)(C.fwd59 | C.rev59 << 16));
-                } else {
-                    if (C.ref59) atomicAdd(&hist[H_REF_MQ + 59], (int)C.ref59);
-                    if (C.alt59) atomicAdd(&hist[H_ALT_MQ + 59], (int)C.alt59);
-                    if (C.fwd59) atomicAdd(&hist[H_FWD_MQS + 59], (int)C.fwd59);
-                    if (C.rev59) atomicAdd(&hist[H_REV_MQS + 59], (int)C.rev59);
+                for (int j = 0; j < NPART; ++j) x[j] = wave_sum_u32(v[j]);
+                if ((tid & 63) == 0) {
+                    #pragma unroll
+                    for (int j = 0; j < SITE_NSUM; ++j) if (x[j]) atomicAdd(&tot[j], (unsigned long long)x[j]);
+                    const uint32_t m59 = x[SITE_NSUM], ref59 = x[SITE_NSUM + 1], rev59 = x[SITE_NSUM + 2];
+                    if (ref59) atomicAdd(&hist[H_REF_MQ + 59], (int)ref59);
+                    if (m59 - ref59) atomicAdd(&hist[H_ALT_MQ + 59], (int)(m59 - ref59));
+                    if (m59 - rev59) atomicAdd(&hist[H_FWD_MQS + 59], (int)(m59 - rev59));
+                    if (rev59) atomicAdd(&hist[H_REV_MQS + 59], (int)rev59);
                 }
             }
         }
@@ -513,7 +538,17 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                 unsigned long long x = 0;
                 for (int k = 0; k < q4; ++k) x += pt[k];
                 x += __shfl_xor(x, 1); x += __shfl_xor(x, 2);
-                if ((i & 3) == 0 && x) { const int vi = i >> 2; s_tot[(vi / NPART) * SITE_NSUM + vi % NPART] += x; }
+                if ((i & 3) == 0 && x) {
+                    const int vi = i >> 2, sl = vi / NPART, j = vi % NPART;
+                    if (j < SITE_NSUM) s_tot[sl * SITE_NSUM + j] += x;
+                    else {                                   // the mapQ 59 bins, REF | ALT << 16 and forward | reverse << 16:
+                        const uint32_t c = (uint32_t)x;      // every count adds its share (mod 2^32; the dword's sum is exact)
+                        int *h = s_hist + sl * HP_SIZE;
+                        if (j == SITE_NSUM) { atomicAdd(&h[H_REF_MQ + 59], (int)(c << 16)); atomicAdd(&h[HP_MQS + 59], (int)c); }
+                        else if (j == SITE_NSUM + 1) atomicAdd(&h[H_REF_MQ + 59], (int)(c - (c << 16)));
+                        else atomicAdd(&h[HP_MQS + 59], (int)((c << 16) - c));
+                    }
+                }
             }
             __syncthreads();
         }

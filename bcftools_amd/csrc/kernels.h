@@ -56,7 +56,7 @@ struct GlfgenParams {
     int min_baseQ, capQ, fmt_flag;
     int hist_slots;                 // >0: per-workgroup LDS histograms with that many site slots; 0: global atomics
     int lds_cap;                    // read keys held in LDS per workgroup round (multiple of 16, <= 16384)
-    int part_cols;                  // LDS columns per partial sum of phase A (power of two >= 4; 12 * hist_slots * part_cols <= 2048: the slot region)
+    int part_cols;                  // LDS columns per partial sum of phase A (power of two >= 4; NPART (17) * hist_slots * part_cols <= 2048: the slot region)
     uint32_t n_reads;               // length of rd/epos (bounds of the vector loads)
     const int8_t   *ref16;
     const uint32_t *off;

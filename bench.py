@@ -11,6 +11,10 @@ workload is the one BASELINE.json's metric is quoted on: 1000 samples x 30x, a t
 collective is the ordered gather of the per-site call records to rank 0).
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the roofline accounting).
+
+A plain run does what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+everything else the benchmark measures: the CPU baselines (one core and all cores), the indel mode's host-pointer form and,
+in the snp mode, the other BASELINE shapes and the glfgen_kernel HBM counters (child runs of their own).
 """
 import argparse
 import ctypes as C
@@ -29,8 +33,13 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
-def parse():
+FULL_DEFAULTS = {"cpu_seconds": 15.0, "cpu_all_cores": 1, "extras": 1, "indel_callers": 1}   # a plain run: 0 each
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure (the CPU baselines, the indel "
+                                                        "mode's host-pointer form, the snp mode's extras); an option given explicitly wins")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10, help="timed steps (snp, indel, mixed, wgs, gvcf; ms_per_step = their mean); baq times "
                                                           "max(1, steps // 3) calls and keeps the fastest, pileup overlaps max(4, steps) regions")
@@ -39,22 +48,24 @@ def parse():
     ap.add_argument("--depth", type=float, default=30.0)
     ap.add_argument("--sites", type=int, default=None, help="pileup columns per tile (= per step, per rank); default 32768 (snp), 128 (indel), 32 (baq)")
     ap.add_argument("--var-rate", type=float, default=0.01)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget on rank 0 at N=1 (0: skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="CPU-baseline budget on rank 0 at N=1 (0: skip; default 15 with --full, else 0)")
     ap.add_argument("--seed", type=int, default=20260104)
     ap.add_argument("--packed", type=int, default=1, help="--mode pileup: 1 = the pool as bcfgpu_pileup_packed takes it (4-bit bases, palette qualities), 0 = a byte per base")
     ap.add_argument("--baq", type=int, default=0, help="--mode pileup: 1 = BAQ on the pool in HBM between the upload and the pileup (bcfgpu_pool_upload -> bcfgpu_pool_baq -> bcfgpu_pool_pileup)")
     ap.add_argument("--pageable", action="store_true", help="--mode pileup: keep the read pool in ordinary (pageable) host memory")
-    ap.add_argument("--cpu-all-cores", type=int, default=1, help="also time the CPU baseline on all host cores (0: skip)")
+    ap.add_argument("--cpu-all-cores", type=int, default=None, help="also time the CPU baseline on all host cores (0: skip; default 1 with --full, else 0)")
     ap.add_argument("--groups", type=int, default=1, help="snp mode: call -G with this many sample groups (frequencies from FORMAT/AD); "
                                                           ">1 takes the general caller path (BASELINE configs[4] shape)")
     ap.add_argument("--haploid-frac", type=float, default=0.0, help="snp mode: fraction of haploid samples (ploidy array; general caller path)")
-    ap.add_argument("--extras", type=int, default=1, help="snp mode at N=1: also measure the BASELINE configs[4] shape (sample groups + ploidy array) and "
-                                                          "the indel stage (configs[2] shape) in child processes and embed their results under \"extra\" (0: skip)")
+    ap.add_argument("--extras", type=int, default=None, help="snp mode at N=1: also measure the BASELINE configs[4] shape (sample groups + ploidy array) and "
+                                                             "the indel stage (configs[2] shape) in child processes and embed their results under \"extra\" "
+                                                             "(0: skip; default 1 with --full, else 0)")
     ap.add_argument("--indel-read-rate", type=float, default=0.005, help="wgs mode: fraction of reads that carry a noise indel (SURVEY 8d: 0.5 %%)")
     ap.add_argument("--true-indel-rate", type=float, default=0.01, help="wgs mode: true indel sites per column")
     ap.add_argument("--fixed-depth", type=int, default=0, help="snp mode (experiment): 1 = every cell exactly --depth reads deep instead of Poisson(--depth)")
     ap.add_argument("--long-indel-frac", type=float, default=0.05, help="wgs mode: fraction of the indels (noise and true) that are 8-40 bases long")
-    ap.add_argument("--indel-callers", type=int, default=1, help="indel mode: also time the host-pointer form of the stage on one 32-column batch (0: skip)")
+    ap.add_argument("--indel-callers", type=int, default=None, help="indel mode: also time the host-pointer form of the stage on one 32-column batch "
+                                                                    "(0: skip; default 1 with --full, else 0)")
     ap.add_argument("--mode", choices=["snp", "indel", "baq", "pileup", "gvcf", "mixed", "wgs"], default="snp",
                     help="snp: the headline pipeline (default).  indel: bcf_call_gap_prep on synthetic indel-candidate columns "
                          "(BASELINE configs[2] shape, 500 samples), reports DP cells/s of the realignment kernel.  "
@@ -63,7 +74,10 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="snp mode: after the timed steps, write what the last step computed to DIR/<name>.npy (float32/float64, "
                          "at most 64 MB in all; the per-sample planes of a fixed, seeded sample of sites)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    for k, v in FULL_DEFAULTS.items():
+        if getattr(a, k) is None:
+            setattr(a, k, v if a.full else type(v)(0))
     if a.steps < 1:
         ap.error("--steps must be at least 1")
     if a.dump_outputs is not None and a.mode != "snp":
@@ -1188,9 +1202,10 @@ def main():
         if world == 1 and a.extras and a.groups == 1 and a.haploid_frac == 0.0:
             import subprocess
 
-            def child(args, timeout=600):
+            def child(args, timeout=600):                    # (--full: a child measures whatever its arguments do not switch off)
                 try:
-                    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, cwd=ROOT, capture_output=True, text=True,
+                                       timeout=timeout)
                     for ln in reversed(r.stdout.strip().splitlines()):
                         if ln.startswith("{"):
                             return json.loads(ln)

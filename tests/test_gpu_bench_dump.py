@@ -51,6 +51,16 @@ def test_dump_outputs_are_the_last_steps_and_repeat(dumps):
     assert (np.load(os.path.join(a, "mplp_site_mwu_bq_nonfinite.npy")) == 2).any()     # untested sites: +HUGE_VAL in the record
 
 
+def test_plain_run_reports_the_headline_only():
+    """Without --full and without the options that switch them off, no CPU baseline and no child measurements run."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--sites", "2048",
+                        "--samples", "200"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stderr or r.stdout)[-2000:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "sites/s"
+    assert "cpu_baseline" not in j and "extra" not in j and "configs4_shape_sites_per_s" not in j["config"]
+
+
 def _columns(tile, sites):
     """the columns `sites` of a HostTile, as a HostTile of their own"""
     from bcftools_amd import host

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile on a GPU box (run through gpurun from the repo root): bash tools/profile.sh [round-tag]
-#  1. python bench.py (default workload, with the CPU baseline and the extras)  -> gpurun_out/prof/bench.json
+#  1. python bench.py --full (default workload, with the CPU baseline and the extras)  -> $OUT/bench.json
 #  2. rocprofv3 --kernel-trace --stats of the same command (no CPU baseline)    -> gpurun_out/prof/stats/
 #  3. HBM bytes of the kernels: --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs, on the bench's own tile
 #     (the default 32768 sites: the number bench.py reports is measured on this launch shape, not scaled)
@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof
 rm -rf $OUT && mkdir -p $OUT
-python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 echo "bench done"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- python3 $R/bench.py --cpu-seconds 0 --extras 0 > $OUT/stats.log 2>&1 || { tail -5 $OUT/stats.log; exit 1; }
 echo "stats done"

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
-#include "kernels.h"
+#include "ctx.h"
 #include "tables.h"
 
 using namespace bcfgpu;
@@ -24,7 +24,6 @@ static int set_err(int code, const char *what, hipError_t e = hipSuccess)
     g_err = buf;
     return code;
 }
-int bcfgpu_set_error(int code, const char *what) { return set_err(code, what); }
 #define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return set_err(BCFGPU_E_HIP, #call, e_); } while (0)
 
 struct bcfgpu_ctx {
@@ -52,21 +51,19 @@ struct bcfgpu_ctx {
     std::vector<int> pool_call;     // mode 2: 1 if the sequence included the call kernel
     std::vector<void*> owned;
     bcfgpu_gap_stats gap{};         // statistics of the last bcfgpu_gap_prep
-    // grow-only device workspaces of the indel / BAQ stages (GiB-sized scratch: not reallocated per call)
+    PileupParams pileup{};          // the parameters of the last bcfgpu_pool_pileup (pileup.hip)
+    DevPool read_pool{};            // the read pool bcfgpu_pool_upload left in HBM
+    // grow-only device workspaces of the stages (GiB-sized scratch: not reallocated per call), by slot (ctx.h)
     struct Ws { void *p = nullptr; size_t bytes = 0; };
-    alignas(16) unsigned char pileup_state[256] = {0};   // csrc/pileup.hip: the parameters of the last bcfgpu_pileup
-    alignas(16) unsigned char pool_state[256] = {0};     // kernels.h DevPool: the read pool bcfgpu_pool_upload left in HBM
-    Ws ws[152];                    // grow-only device workspaces of the host-fed stages (0-15: BAQ / overlaps, 16-35: pileup, 36-39: gVCF / indel tile, 40-103: gap_prep, 104-135: the resident read pool and its stages, 136-143: errmod_cal's draw, 144-151: BAQ's smaller band classes, which run beside the main one)
+    Ws ws[WS_COUNT];
     int n_cu = 256;                // compute units of the device (grid size of the work-queue kernels)
     hipStream_t side[8] = {};      // created on first use: the realignment kernels of different band widths run side by side
     hipEvent_t side_ev[9] = {};    // [0..7] a side stream's work is done, [8] the fork point on the main stream
-    Ws pinned[8];                  // grow-only pinned host staging buffers
+    Ws pinned[PINNED_COUNT];        // grow-only pinned host staging buffers
     DrawState draw;                // errmod_cal's generator and the plan of the next launches (draw.hip)
 };
 
 extern "C" {
-
-void *bcfgpu_internal_ws(bcfgpu_ctx *c, int slot, size_t bytes);
 
 const char *bcfgpu_last_error(void) { return g_err.c_str(); }
 
@@ -593,16 +590,37 @@ int bcfgpu_pipeline(bcfgpu_ctx *c, const bcfgpu_tile *tile, const uint8_t *ploid
     return 0;
 }
 
+int bcfgpu_gap_prep_stats(const bcfgpu_ctx *c, bcfgpu_gap_stats *out)
+{
+    if (!c || !out) return set_err(BCFGPU_E_ARG, "bcfgpu_gap_prep_stats: bad arguments");
+    *out = c->gap;
+    return 0;
+}
+
+}  // extern "C"
+
+// The realignment and BAQ stages fork their band classes onto side streams meant to run beside one another.  The HIP runtime
+// multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default); two streams of one queue run their
+// kernels one after the other, and with this context's streams beside the host program's own that happens: the realignment's
+// second chain of classes started only when the wide-band stream it shared a queue with had drained (29.0 ms a 16 384-column
+// tile; 25.6 ms with eight queues, profiles/r5_hw_queues.txt).  The variable is read when the runtime starts, i.e. at the first
+// HIP call of the process: set here, when the library is loaded, unless the user has set it.
+__attribute__((constructor)) static void bcfgpu_runtime_knobs() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
+
+// ---- the context's internal interface (ctx.h), for the stages implemented in their own translation units ----
+namespace bcfgpu {
+
+int bcfgpu_set_error(int code, const char *what) { return set_err(code, what); }
+
 bcfgpu_gap_stats *bcfgpu_internal_gap_stats(bcfgpu_ctx *c) { return &c->gap; }
 DrawState *bcfgpu_internal_draw_state(bcfgpu_ctx *c) { return &c->draw; }
 const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *c) { return c ? &c->cfg : nullptr; }
-void *bcfgpu_internal_pileup_state(bcfgpu_ctx *c) { return c ? c->pileup_state : nullptr; }
-void *bcfgpu_internal_pool_state(bcfgpu_ctx *c) { return c ? c->pool_state : nullptr; }
+PileupParams *bcfgpu_internal_pileup_state(bcfgpu_ctx *c) { return c ? &c->pileup : nullptr; }
+DevPool *bcfgpu_internal_pool_state(bcfgpu_ctx *c) { return c ? &c->read_pool : nullptr; }
 
-// workspace `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails
-void *bcfgpu_internal_ws(bcfgpu_ctx *c, int slot, size_t bytes)
+void *bcfgpu_internal_ws(bcfgpu_ctx *c, WsSlot slot, size_t bytes)
 {
-    if (!c || slot < 0 || slot >= 152) return nullptr;
+    if (!c || slot < 0 || slot >= WS_COUNT) return nullptr;
     auto &w = c->ws[slot];
     if (w.bytes >= bytes && w.p) return w.p;
     hipSetDevice(c->cfg.device);
@@ -613,10 +631,9 @@ void *bcfgpu_internal_ws(bcfgpu_ctx *c, int slot, size_t bytes)
     return w.p;
 }
 
-// pinned host staging buffer `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails
-void *bcfgpu_internal_pinned(bcfgpu_ctx *c, int slot, size_t bytes)
+void *bcfgpu_internal_pinned(bcfgpu_ctx *c, PinnedSlot slot, size_t bytes)
 {
-    if (!c || slot < 0 || slot >= 8) return nullptr;
+    if (!c || slot < 0 || slot >= PINNED_COUNT) return nullptr;
     auto &w = c->pinned[slot];
     if (w.bytes >= bytes && w.p) return w.p;
     hipSetDevice(c->cfg.device);
@@ -627,18 +644,15 @@ void *bcfgpu_internal_pinned(bcfgpu_ctx *c, int slot, size_t bytes)
     return w.p;
 }
 
-// The realignment and BAQ stages fork their band classes onto side streams meant to run beside one another.  The HIP runtime
-// multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default); two streams of one queue run their
-// kernels one after the other, and with this context's streams beside the host program's own that happens: the realignment's
-// second chain of classes started only when the wide-band stream it shared a queue with had drained (29.0 ms a 16 384-column
-// tile; 25.6 ms with eight queues, profiles/r5_hw_queues.txt).  The variable is read when the runtime starts, i.e. at the first
-// HIP call of the process: set here, when the library is loaded, unless the user has set it.
-__attribute__((constructor)) static void bcfgpu_runtime_knobs() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
+void *ws_upload(bcfgpu_ctx *c, WsSlot slot, const void *src, size_t bytes, size_t slack, hipStream_t stream)
+{
+    void *d = bcfgpu_internal_ws(c, slot, bytes + slack);
+    if (d && bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return nullptr;
+    return d;
+}
 
-// for the stages implemented in their own translation units: bind the device, hand out the stream and shared tables
 int bcfgpu_internal_n_cu(const bcfgpu_ctx *c) { return c ? c->n_cu : 256; }
 
-// side streams (fork / join around independent launches); 0 on success
 int bcfgpu_internal_side(bcfgpu_ctx *c, hipStream_t **streams, hipEvent_t **events)
 {
     if (!c) return -1;
@@ -660,11 +674,4 @@ int bcfgpu_internal_device(bcfgpu_ctx *c, hipStream_t *stream, const float **q2p
     return 0;
 }
 
-int bcfgpu_gap_prep_stats(const bcfgpu_ctx *c, bcfgpu_gap_stats *out)
-{
-    if (!c || !out) return set_err(BCFGPU_E_ARG, "bcfgpu_gap_prep_stats: bad arguments");
-    *out = c->gap;
-    return 0;
-}
-
-}  // extern "C"
+}  // namespace bcfgpu

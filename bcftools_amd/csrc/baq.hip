@@ -16,14 +16,7 @@
 #include <type_traits>
 #include <cstring>
 #include <cstdlib>
-#include "kernels.h"
-
-struct bcfgpu_ctx;
-int bcfgpu_set_error(int code, const char *what);
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *ctx, hipStream_t *stream, const float **q2p);
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *ctx, int slot, size_t bytes);
-extern "C" void *bcfgpu_internal_pinned(bcfgpu_ctx *ctx, int slot, size_t bytes);
-extern "C" int bcfgpu_internal_side(bcfgpu_ctx *ctx, hipStream_t **streams, hipEvent_t **events);
+#include "ctx.h"
 
 namespace bcfgpu {
 
@@ -1074,14 +1067,14 @@ extern "C" int bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const char *r
     }
 
     // ---- device half ----
-    // grow-only workspaces of the context (slots 7..): GiB-sized scratch is not reallocated per call
+    // grow-only workspaces of the context: GiB-sized scratch is not reallocated per call
     void *d_jobs = nullptr, *d_F = nullptr, *d_B = nullptr, *d_S = nullptr;
     auto cleanup = [&]() {};
-    void *d_tref = bcfgpu_internal_ws(ctx, 7, tref.size() + 16), *d_seq = bcfgpu_internal_ws(ctx, 8, nbase + 16),
-         *d_qual = bcfgpu_internal_ws(ctx, 9, nbase + 16), *d_cig = bcfgpu_internal_ws(ctx, 10, (ncig + 4) * 4),
-         *d_state = bcfgpu_internal_ws(ctx, 11, (nbase + 4) * 4), *d_q = bcfgpu_internal_ws(ctx, 12, nbase + 16),
-         *d_tmp = bcfgpu_internal_ws(ctx, 13, 2 * nbase + 16), *d_qo = bcfgpu_internal_ws(ctx, 14, nbase + 16),
-         *d_zo = bcfgpu_internal_ws(ctx, 15, nbase + 16);
+    void *d_tref = bcfgpu_internal_ws(ctx, WS_BAQ_TREF, tref.size() + 16), *d_seq = bcfgpu_internal_ws(ctx, WS_BAQ_SEQ, nbase + 16),
+         *d_qual = bcfgpu_internal_ws(ctx, WS_BAQ_QUAL, nbase + 16), *d_cig = bcfgpu_internal_ws(ctx, WS_BAQ_CIG, (ncig + 4) * 4),
+         *d_state = bcfgpu_internal_ws(ctx, WS_BAQ_STATE, (nbase + 4) * 4), *d_q = bcfgpu_internal_ws(ctx, WS_BAQ_Q, nbase + 16),
+         *d_tmp = bcfgpu_internal_ws(ctx, WS_BAQ_TMP, 2 * nbase + 16), *d_qo = bcfgpu_internal_ws(ctx, WS_BAQ_QUAL_OUT, nbase + 16),
+         *d_zo = bcfgpu_internal_ws(ctx, WS_BAQ_ZQ_OUT, nbase + 16);
     if (!d_tref || !d_seq || !d_qual || !d_cig || !d_state || !d_q || !d_tmp || !d_qo || !d_zo)
         return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_baq: device workspace");
     BQ_CHK(hipMemcpyAsync(d_tref, tref.data(), tref.size(), hipMemcpyHostToDevice, stream));
@@ -1108,15 +1101,14 @@ extern "C" int bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const char *r
         chunk = chunk < 64 ? 64 : (chunk & ~(size_t)63);
         if (chunk > nj) chunk = (nj + 63) & ~(size_t)63;
         P.stride = chunk;
-        // (slots 0..6 are shared with the indel stage; both stages finish their stream work before returning)
-        d_jobs = bcfgpu_internal_ws(ctx, 0, nj * sizeof(BaqJob));
-        d_F = bcfgpu_internal_ws(ctx, 4, per_mat * chunk);
-        d_B = reg ? nullptr : bcfgpu_internal_ws(ctx, 1, per_mat * chunk);
-        d_S = bcfgpu_internal_ws(ctx, 2, (size_t)(max_lq + 2) * chunk * sizeof(double));
+        d_jobs = bcfgpu_internal_ws(ctx, WS_BAQ_JOBS, nj * sizeof(BaqJob));
+        d_F = bcfgpu_internal_ws(ctx, WS_BAQ_F, per_mat * chunk);
+        d_B = reg ? nullptr : bcfgpu_internal_ws(ctx, WS_BAQ_B, per_mat * chunk);
+        d_S = bcfgpu_internal_ws(ctx, WS_BAQ_S, (size_t)(max_lq + 2) * chunk * sizeof(double));
         if (!d_jobs || !d_F || (!reg && !d_B) || !d_S) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_baq: device workspace");
         if (reg) {                                                   // state / posterior quality / left maxima, a wavefront's reads side by side
             const size_t wn = chunk * (size_t)max_lq;
-            uint8_t *d_w = (uint8_t*)bcfgpu_internal_ws(ctx, 5, wn * 6 + 64);
+            uint8_t *d_w = (uint8_t*)bcfgpu_internal_ws(ctx, WS_BAQ_W, wn * 6 + 64);
             if (!d_w) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_baq: device workspace");
             P.wstate = (int32_t*)d_w; P.wq = d_w + wn * 4; P.wleft = d_w + wn * 5;
         }
@@ -1138,8 +1130,6 @@ extern "C" int bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const char *r
     return BCFGPU_OK;
 }
 
-extern "C" void *bcfgpu_internal_pool_state(bcfgpu_ctx *ctx);
-
 // sam_prob_realn on every read of the pool in HBM: the pool's qualities become the new ones, the ZQ bytes stay there for
 // bcfgpu_gap_prep_tile.  The host part: the contig's length, one wait for the job counts (they size the scratch and the
 // reference slice to upload), launches.
@@ -1149,7 +1139,7 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     hipStream_t stream = nullptr;
     const float *d_q2p = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, &d_q2p)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_baq: bad context");
-    DevPool &D = *static_cast<DevPool*>(bcfgpu_internal_pool_state(ctx));
+    DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_baq: no read pool on this context (bcfgpu_pool_upload)");
     const int n = D.n_reads;
     if (n == 0) return BCFGPU_OK;
@@ -1157,17 +1147,18 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     const size_t nbase = D.n_bases;
     BaqPrepParams Q{};
     Q.D = D; Q.ref_len = (int)strnlen(ref, (size_t)ref_len);
-    Q.jobs0 = (BaqJob*)bcfgpu_internal_ws(ctx, 0, (size_t)n * sizeof(BaqJob) + 64);
-    Q.jobs1 = (BaqJob*)bcfgpu_internal_ws(ctx, 3, (size_t)n * sizeof(BaqJob) + 64);
-    Q.jobs2 = (BaqJob*)bcfgpu_internal_ws(ctx, 127, (size_t)n * sizeof(BaqJob) + 64);
-    Q.jobs3 = (BaqJob*)bcfgpu_internal_ws(ctx, 135, (size_t)n * sizeof(BaqJob) + 64);
-    Q.counts = (int*)bcfgpu_internal_ws(ctx, 115, 64);
-    Q.ret = (int32_t*)bcfgpu_internal_ws(ctx, 116, (size_t)n * 4 + 64);
-    Q.has_zq = (uint8_t*)bcfgpu_internal_ws(ctx, 117, (size_t)n + 64);
-    const int qo_slot = D.qual_slot == 118 ? 119 : 118;                 // not the buffer the pool's qualities are in now
+    Q.jobs0 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS0, (size_t)n * sizeof(BaqJob) + 64);
+    Q.jobs1 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS1, (size_t)n * sizeof(BaqJob) + 64);
+    Q.jobs2 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS2, (size_t)n * sizeof(BaqJob) + 64);
+    Q.jobs3 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS3, (size_t)n * sizeof(BaqJob) + 64);
+    Q.counts = (int*)bcfgpu_internal_ws(ctx, WS_PBAQ_COUNTS, 64);
+    Q.ret = (int32_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_RET, (size_t)n * 4 + 64);
+    Q.has_zq = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_HAS_ZQ, (size_t)n + 64);
+    const WsSlot qo_slot = D.qual_slot == WS_PBAQ_QUAL_A ? WS_PBAQ_QUAL_B : WS_PBAQ_QUAL_A;    // not the buffer the pool's qualities are in now
     uint8_t *d_qo = (uint8_t*)bcfgpu_internal_ws(ctx, qo_slot, nbase + 64);
-    uint8_t *d_zo = (uint8_t*)bcfgpu_internal_ws(ctx, 120, nbase + 64);
-    void *d_state = bcfgpu_internal_ws(ctx, 11, (nbase + 4) * 4), *d_q = bcfgpu_internal_ws(ctx, 12, nbase + 16), *d_tmp = bcfgpu_internal_ws(ctx, 13, 2 * nbase + 16);
+    uint8_t *d_zo = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_ZQ, nbase + 64);
+    void *d_state = bcfgpu_internal_ws(ctx, WS_PBAQ_STATE, (nbase + 4) * 4), *d_q = bcfgpu_internal_ws(ctx, WS_PBAQ_Q, nbase + 16),
+         *d_tmp = bcfgpu_internal_ws(ctx, WS_PBAQ_TMP, 2 * nbase + 16);
     if (!Q.jobs0 || !Q.jobs1 || !Q.jobs2 || !Q.jobs3 || !Q.counts || !Q.ret || !Q.has_zq || !d_qo || !d_zo || !d_state || !d_q || !d_tmp)
         return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
     const int init[8] = {0, 0, 1, 1, INT32_MAX, 0, 0, 0};
@@ -1180,12 +1171,12 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     BQ_CHK(hipStreamSynchronize(stream));
     // the reference slice the windows touch, as 0..4 codes
     const int lo = counts[4] == INT32_MAX ? 0 : counts[4], hi = std::max(counts[5], lo);
-    char *d_refc = (char*)bcfgpu_internal_ws(ctx, 121, (size_t)(hi - lo) + 64);
-    uint8_t *d_ref4 = (uint8_t*)bcfgpu_internal_ws(ctx, 7, (size_t)(hi - lo) + 64);
+    char *d_refc = (char*)bcfgpu_internal_ws(ctx, WS_PBAQ_REF, (size_t)(hi - lo) + 64);
+    uint8_t *d_ref4 = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_REF4, (size_t)(hi - lo) + 64);
     if (!d_refc || !d_ref4) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
     if (hi > lo) {
         // (through the context's page-locked staging buffer: the call returns with the copy in flight, `ref` is the caller's)
-        char *h_ref = (char*)bcfgpu_internal_pinned(ctx, 6, (size_t)(hi - lo));
+        char *h_ref = (char*)bcfgpu_internal_pinned(ctx, PIN_PBAQ_REF, (size_t)(hi - lo));
         if (!h_ref) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: host staging");
         std::memcpy(h_ref, ref + lo, (size_t)(hi - lo));
         BQ_CHK(hipMemcpyAsync(d_refc, h_ref, (size_t)(hi - lo), hipMemcpyHostToDevice, stream));
@@ -1207,12 +1198,13 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     if (bcfgpu_internal_side(ctx, &side, &sev)) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_baq: side streams");
     BaqJob *jobs2 = Q.jobs2;                               // the wide class's jobs, sorted by band (before anything else is on the chip:
     if (counts[6] > 0) {                                   // one workgroup, 20 us alone, 15 ms behind a launch that fills it)
-        jobs2 = (BaqJob*)bcfgpu_internal_ws(ctx, 128, (size_t)counts[6] * sizeof(BaqJob) + 64);
+        jobs2 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS2_SORTED, (size_t)counts[6] * sizeof(BaqJob) + 64);
         if (!jobs2) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
         hipLaunchKernelGGL(baq_sort_wide_kernel, dim3(1), dim3(1024), 0, stream, Q.jobs2, counts[6], jobs2);
     }
     BQ_CHK(hipEventRecord(sev[0], stream));
-    static const int slotF[4] = { 4, 144, 147, 149 }, slotS[4] = { 2, 145, 148, 150 }, slotW[4] = { 5, 146, 1, 151 };    // (W of the LDS-row classes: their second matrix)
+    static const WsSlot slotF[4] = { WS_PBAQ_F0, WS_PBAQ_F1, WS_PBAQ_F2, WS_PBAQ_F3 }, slotS[4] = { WS_PBAQ_S0, WS_PBAQ_S1, WS_PBAQ_S2, WS_PBAQ_S3 },
+                        slotW[4] = { WS_PBAQ_W0, WS_PBAQ_W1, WS_PBAQ_W2, WS_PBAQ_W3 };
     bool used_side[4] = { false, false, false, false };
     for (int ci = 0; ci < 4; ++ci) {
         const int c = ci == 0 ? 2 : ci == 1 ? 3 : ci == 2 ? 1 : 0;                // the small classes first, the slowest of them in front

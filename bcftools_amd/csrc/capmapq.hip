@@ -10,11 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <climits>
-#include "kernels.h"
-
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *ctx, hipStream_t *stream, const float **q2p);
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *ctx, int slot, size_t bytes);
-int bcfgpu_set_error(int code, const char *what);
+#include "ctx.h"
 
 namespace bcfgpu {
 
@@ -105,9 +101,6 @@ __global__ __launch_bounds__(256) void cap_apply_kernel(int n, const int32_t *ca
 }
 }
 
-extern "C" void *bcfgpu_internal_pool_state(bcfgpu_ctx *ctx);
-int bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, int *lo, int *hi);
-
 // The same on the pool in HBM (after bcfgpu_pool_baq): the caps come back for the caller's filters (cap < 0: the read is
 // dropped, mpileup.c:237), the pool's mapping qualities are lowered in place.
 extern "C" int bcfgpu_pool_cap_mapq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len, int32_t thres, int32_t *cap)
@@ -115,7 +108,7 @@ extern "C" int bcfgpu_pool_cap_mapq(bcfgpu_ctx *ctx, const char *ref, int32_t re
     if (!ctx || !cap || (ref_len > 0 && !ref)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_cap_mapq: bad arguments");
     hipStream_t st = nullptr;
     if (bcfgpu_internal_device(ctx, &st, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_cap_mapq: bad context");
-    const DevPool &D = *static_cast<const DevPool*>(bcfgpu_internal_pool_state(ctx));
+    const DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_cap_mapq: no read pool on this context (bcfgpu_pool_upload)");
     const int n = D.n_reads;
     if (!n) return BCFGPU_OK;
@@ -128,8 +121,8 @@ extern "C" int bcfgpu_pool_cap_mapq(bcfgpu_ctx *ctx, const char *ref, int32_t re
     P.n_reads = n; P.thres = thres;
     P.r_pos = D.r_pos; P.r_lq = D.r_lq; P.r_ncig = D.r_ncig; P.r_cig_off = D.r_cig_off; P.r_seq_off = D.r_seq_off;
     P.cig = D.cig; P.seq16 = D.seq16; P.qual = D.qual;
-    char *d_ref = (char*)bcfgpu_internal_ws(ctx, 125, (size_t)(hi - lo) + 64);
-    P.out = (int32_t*)bcfgpu_internal_ws(ctx, 126, (size_t)n * 4 + 64);
+    char *d_ref = (char*)bcfgpu_internal_ws(ctx, WS_PCAPQ_REF, (size_t)(hi - lo) + 64);
+    P.out = (int32_t*)bcfgpu_internal_ws(ctx, WS_PCAPQ_OUT, (size_t)n * 4 + 64);
     if (!d_ref || !P.out) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_cap_mapq: device workspace");
     if (hi > lo && hipMemcpyAsync(d_ref, ref + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, st) != hipSuccess)
         return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_cap_mapq: upload");
@@ -164,19 +157,18 @@ extern "C" int bcfgpu_cap_mapq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const ch
     if (hi > ref_len) hi = ref_len;
     if (hi < lo) hi = lo;
     #define CQ_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
-    auto up = [&](int slot, const void *src, size_t bytes) -> void* {
-        void *d = bcfgpu_internal_ws(ctx, slot, bytes + 16);
-        if (d && bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
-        return d;
-    };
     CapParams P{};
     P.n_reads = n; P.thres = thres;
-    P.r_pos = (const int32_t*)up(0, rd->r_pos, (size_t)n * 4); P.r_lq = (const int32_t*)up(1, rd->r_lq, (size_t)n * 4);
-    P.r_ncig = (const int32_t*)up(2, rd->r_ncig, (size_t)n * 4); P.r_cig_off = (const int32_t*)up(3, rd->r_cig_off, (size_t)n * 4);
-    P.r_seq_off = (const int32_t*)up(4, rd->r_seq_off, (size_t)n * 4); P.cig = (const uint32_t*)up(5, rd->cig, ncig * 4);
-    P.seq16 = (const uint8_t*)up(6, rd->seq16, nbase); P.qual = (const uint8_t*)up(7, rd->qual, nbase);
-    P.ref = (const char*)up(8, ref + lo, (size_t)(hi - lo)); P.ref_lo = lo; P.ref_hi = hi;
-    P.out = (int32_t*)bcfgpu_internal_ws(ctx, 9, (size_t)n * 4 + 16);
+    P.r_pos = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_POS, rd->r_pos, (size_t)n * 4, 16, st);
+    P.r_lq = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_LQ, rd->r_lq, (size_t)n * 4, 16, st);
+    P.r_ncig = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_NCIG, rd->r_ncig, (size_t)n * 4, 16, st);
+    P.r_cig_off = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_CIG_OFF, rd->r_cig_off, (size_t)n * 4, 16, st);
+    P.r_seq_off = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_SEQ_OFF, rd->r_seq_off, (size_t)n * 4, 16, st);
+    P.cig = (const uint32_t*)ws_upload(ctx, WS_CAPQ_CIG, rd->cig, ncig * 4, 16, st);
+    P.seq16 = (const uint8_t*)ws_upload(ctx, WS_CAPQ_SEQ, rd->seq16, nbase, 16, st);
+    P.qual = (const uint8_t*)ws_upload(ctx, WS_CAPQ_QUAL, rd->qual, nbase, 16, st);
+    P.ref = (const char*)ws_upload(ctx, WS_CAPQ_REF, ref + lo, (size_t)(hi - lo), 16, st); P.ref_lo = lo; P.ref_hi = hi;
+    P.out = (int32_t*)bcfgpu_internal_ws(ctx, WS_CAPQ_OUT, (size_t)n * 4 + 16);
     if (!P.r_pos || !P.r_lq || !P.r_ncig || !P.r_cig_off || !P.r_seq_off || !P.cig || !P.seq16 || !P.qual || !P.ref || !P.out)
         return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_cap_mapq: device workspace");
     hipLaunchKernelGGL(cap_mapq_kernel, dim3((n + 255) / 256), dim3(256), 0, st, P);

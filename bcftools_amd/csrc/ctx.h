@@ -1,0 +1,120 @@
+// ctx.h -- the context's internal interface, for the stages in their own translation units: the workspace slots and the
+// accessors of bcfgpu_ctx.  Defined in api.hip, except bcfgpu_internal_pool_extent (pileup.hip) and bcfgpu_internal_gap_core
+// (gap_prep.hip).  C++ linkage: none of it is part of the C-ABI of include/bcfgpu.h.
+#pragma once
+#include "kernels.h"
+
+namespace bcfgpu {
+
+// ---- the context's grow-only device workspaces (bcfgpu_internal_ws) ----
+// One name per use.  Names with the same value are one buffer, and each of their users takes it as scratch for one call (the
+// work a call queues on it is ordered on the context's stream).  "Kept" marks the slots whose contents a later entry point
+// reads: no other use may share their numbers.
+enum WsSlot : int {
+    // bcfgpu_baq (reads from the host): scratch for one call
+    WS_BAQ_JOBS = 0, WS_BAQ_B = 1, WS_BAQ_S = 2, WS_BAQ_F = 4, WS_BAQ_W = 5,
+    WS_BAQ_TREF = 7, WS_BAQ_SEQ = 8, WS_BAQ_QUAL = 9, WS_BAQ_CIG = 10, WS_BAQ_STATE = 11, WS_BAQ_Q = 12, WS_BAQ_TMP = 13,
+    WS_BAQ_QUAL_OUT = 14, WS_BAQ_ZQ_OUT = 15,
+    // bcfgpu_overlap_tweak: scratch for one call
+    WS_OVL_PAIR_A = 7, WS_OVL_PAIR_B = 8, WS_OVL_R_POS = 9, WS_OVL_R_NCIG = 10, WS_OVL_R_CIG_OFF = 11, WS_OVL_R_SEQ_OFF = 12,
+    WS_OVL_CIG = 13, WS_OVL_SEQ = 14, WS_OVL_QUAL = 15,
+    // bcfgpu_cap_mapq: scratch for one call
+    WS_CAPQ_R_POS = 0, WS_CAPQ_R_LQ = 1, WS_CAPQ_R_NCIG = 2, WS_CAPQ_R_CIG_OFF = 3, WS_CAPQ_R_SEQ_OFF = 4, WS_CAPQ_CIG = 5,
+    WS_CAPQ_SEQ = 6, WS_CAPQ_QUAL = 7, WS_CAPQ_REF = 8, WS_CAPQ_OUT = 9,
+
+    // the read pool (pileup.hip pool_upload_impl).  Kept: DevPool, read by the pool stages below and bcfgpu_pool_pileup
+    WS_POOL_CIG = 27, WS_POOL_SEQ16 = 28, WS_POOL_QUAL = 29,
+    WS_POOL_R_POS = 104, WS_POOL_R_LQ = 105, WS_POOL_R_FLAG = 106, WS_POOL_R_NCIG = 107, WS_POOL_R_CIG_OFF = 108,
+    WS_POOL_R_SEQ_OFF = 109, WS_POOL_R_MAPQ = 110,
+    //   the upload's packed inputs: scratch for one call
+    WS_POOL_SEQ4 = 111, WS_POOL_QUAL4 = 112, WS_POOL_RECS = 128, WS_POOL_SCAN_TMP = 129,
+    WS_POOL_KEEP = 114,                 // kept: DevPool::keep (bcfgpu_pool_keep), read by bcfgpu_pool_pileup
+    WS_POOL_EXTENT = 122,               // bcfgpu_internal_pool_extent: scratch for one call
+    // bcfgpu_pool_baq: scratch for one call
+    WS_PBAQ_JOBS0 = 0, WS_PBAQ_JOBS1 = 3, WS_PBAQ_JOBS2 = 127, WS_PBAQ_JOBS3 = 135, WS_PBAQ_JOBS2_SORTED = 128,
+    WS_PBAQ_COUNTS = 115, WS_PBAQ_RET = 116, WS_PBAQ_STATE = 11, WS_PBAQ_Q = 12, WS_PBAQ_TMP = 13,
+    WS_PBAQ_REF = 121, WS_PBAQ_REF4 = 7,
+    //   the matrices of band class c: F, S and W (W of the LDS-row classes 2 and 3: their second matrix)
+    WS_PBAQ_F0 = 4, WS_PBAQ_S0 = 2, WS_PBAQ_W0 = 5, WS_PBAQ_F1 = 144, WS_PBAQ_S1 = 145, WS_PBAQ_W1 = 146,
+    WS_PBAQ_F2 = 147, WS_PBAQ_S2 = 148, WS_PBAQ_W2 = 1, WS_PBAQ_F3 = 149, WS_PBAQ_S3 = 150, WS_PBAQ_W3 = 151,
+    //   kept: the pool's new qualities (DevPool::qual; the call writes to the one of the two it is not in), ZQ and which reads
+    //   have it (DevPool::zq, r_has_zq), read by the pool stages after it, bcfgpu_pool_download and bcfgpu_gap_prep_tile
+    WS_PBAQ_QUAL_A = 118, WS_PBAQ_QUAL_B = 119, WS_PBAQ_ZQ = 120, WS_PBAQ_HAS_ZQ = 117,
+    // bcfgpu_pool_overlap_tweak, bcfgpu_pool_cap_mapq: scratch for one call
+    WS_POVL_PAIR_A = 123, WS_POVL_PAIR_B = 124,
+    WS_PCAPQ_REF = 125, WS_PCAPQ_OUT = 126,
+
+    // bcfgpu_pool_pileup.  Kept: the SNP tile, read by bcfgpu_mpileup / bcfgpu_pipeline / bcfgpu_errmod_plan on it, and
+    // through PileupParams by bcfgpu_pileup_entries, bcfgpu_pileup_indel_tile and bcfgpu_gap_prep_tile
+    WS_PLP_REF16 = 16, WS_PLP_SMPL_OFF = 17, WS_PLP_S_POS = 18, WS_PLP_META = 19, WS_PLP_S_READ = 20,
+    WS_PLP_CNT = 30, WS_PLP_RECS = 31,
+    //   scratch for one call (the scan's temporary storage is done with before the records go to its buffer)
+    WS_PLP_SCAN_TMP = 31, WS_PLP_TOTAL = 34, WS_PLP_STATUS = 113, WS_PLP_COL_COUNTS = 134,
+    // bcfgpu_pileup_entries: scratch for one call
+    WS_ENT_COLS = 21, WS_ENT_SEL = 22, WS_ENT_SCAN_TMP = 23, WS_ENT_OUT = 24,
+    // bcfgpu_pileup_indel_tile and bcfgpu_gap_prep_tile.  Kept: the indel tile each returns, read by bcfgpu_mpileup /
+    // bcfgpu_errmod_plan on it.  The two calls share 25 and 26, so each overwrites the tile of the other, although
+    // include/bcfgpu.h says that tile stays valid.
+    WS_ITILE_SEL = 25, WS_ITILE_RECS = 26,
+    WS_ITILE_COLS = 21, WS_ITILE_SCAN_TMP = 23,                                // scratch for one call
+    WS_GTILE_LIVE_SEL = 131, WS_GTILE_RECS = 26,
+    //   scratch for one call
+    WS_GTILE_COLS = 21, WS_GTILE_N_KEPT = 143, WS_GTILE_SEL = 25, WS_GTILE_SCAN_TMP = 23, WS_GTILE_ENT = 24, WS_GTILE_LIVE = 130,
+
+    // bcfgpu_gap_prep and bcfgpu_gap_prep_tile: scratch for one call.  The inputs as bcfgpu_gap_prep uploads them (those
+    // bcfgpu_gap_prep_tile forms or uploads itself: the per-read arrays 40-45, ZQ, the positions, the reference slice, p->aux)
+    WS_GAP_R_POS = 40, WS_GAP_R_LQ = 41, WS_GAP_R_FLAG = 42, WS_GAP_R_NCIG = 43, WS_GAP_R_CIG_OFF = 44, WS_GAP_R_SEQ_OFF = 45,
+    WS_GAP_CIG = 46, WS_GAP_SEQ = 47, WS_GAP_QUAL = 48, WS_GAP_ZQ = 49, WS_GAP_HAS_ZQ = 50, WS_GAP_POS = 51, WS_GAP_SMPL_OFF = 52,
+    WS_GAP_P_READ = 53, WS_GAP_P_QPOS = 54, WS_GAP_P_INDEL = 55, WS_GAP_REF = 64, WS_GAP_AUX = 67,
+    //   bcfgpu_internal_gap_core
+    WS_GAP_INSCNT = 56, WS_GAP_INSCNS = 57, WS_GAP_REF2 = 58, WS_GAP_SCORE1 = 59, WS_GAP_SCORE2 = 60, WS_GAP_WIDE = 61,
+    WS_GAP_OUT_INSCNS = 62, WS_GAP_WIDE_ROWS = 63, WS_GAP_SITES = 65, WS_GAP_READ_INFO = 66, WS_GAP_SMALL = 68, WS_GAP_ENT = 69,
+    WS_GAP_QPACK = 70, WS_GAP_PJOB = 71, WS_GAP_KEY_IN = 72, WS_GAP_VAL_IN = 73, WS_GAP_KEY_SORTED = 74, WS_GAP_VAL_SORTED = 75,
+    WS_GAP_LIST2 = 76, WS_GAP_SORT_TMP = 77, WS_GAP_QUEUE = 78, WS_GAP_SUMQ = 79, WS_GAP_OTYPE = 80, WS_GAP_EMT = 133,
+
+    // bcfgpu_gvcf_blocks, bcfgpu_compact_calls[_async]: scratch for one call
+    WS_GVCF_SCAN = 32, WS_GVCF_SCAN_TMP = 33,
+    WS_COMPACT_SIZE = 35, WS_COMPACT_SCAN_TMP = 36, WS_COMPACT_COUNTS = 37,
+
+    // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
+    WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
+    //   scratch for one call
+    WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
+
+    WS_COUNT = WS_PBAQ_W3 + 1           // one past the highest slot
+};
+
+// ---- the context's grow-only pinned host buffers (bcfgpu_internal_pinned): each is scratch for one call ----
+enum PinnedSlot : int {
+    PIN_GAP_SMALL = 0,                  // bcfgpu_internal_gap_core: the totals and per-site results
+    PIN_COMPACT_COUNTS = 1,             // bcfgpu_compact_counts
+    PIN_GTILE_KEPT = 2,                 // bcfgpu_gap_prep_tile: the columns that go on
+    PIN_PLP_COL_COUNTS = 3,             // bcfgpu_pool_pileup: col_n / col_indel
+    PIN_PBAQ_REF = 6,                   // bcfgpu_pool_baq: the reference slice (the call returns with its copy in flight)
+    PINNED_COUNT = PIN_PBAQ_REF + 1     // one past the highest slot
+};
+
+// workspace / pinned host buffer `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails
+void *bcfgpu_internal_ws(bcfgpu_ctx *c, WsSlot slot, size_t bytes);
+void *bcfgpu_internal_pinned(bcfgpu_ctx *c, PinnedSlot slot, size_t bytes);
+// workspace `slot` of at least bytes + slack, the copy of `bytes` from host `src` queued on `stream`; nullptr on failure
+void *ws_upload(bcfgpu_ctx *c, WsSlot slot, const void *src, size_t bytes, size_t slack, hipStream_t stream);
+
+// bind the context's device, hand out its stream and the qual2prob table (either may be NULL); 0 on success
+int bcfgpu_internal_device(bcfgpu_ctx *c, hipStream_t *stream, const float **q2p);
+// the side streams (fork / join around independent launches), created on first use; 0 on success
+int bcfgpu_internal_side(bcfgpu_ctx *c, hipStream_t **streams, hipEvent_t **events);
+int bcfgpu_internal_n_cu(const bcfgpu_ctx *c);
+const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *c);
+bcfgpu_gap_stats *bcfgpu_internal_gap_stats(bcfgpu_ctx *c);
+DrawState *bcfgpu_internal_draw_state(bcfgpu_ctx *c);
+DevPool *bcfgpu_internal_pool_state(bcfgpu_ctx *c);             // the read pool bcfgpu_pool_upload left in HBM
+PileupParams *bcfgpu_internal_pileup_state(bcfgpu_ctx *c);      // the parameters of the last bcfgpu_pool_pileup
+int bcfgpu_set_error(int code, const char *what);               // bcfgpu_last_error() becomes `what`; returns `code`
+
+// [lowest start, highest end) of the pool's reads (pileup.hip)
+int bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, int *lo, int *hi);
+// bcf_call_gap_prep on inputs already in HBM (gap_prep.hip)
+int bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint32_t *d_aux, const bcfgpu_indel_out *out, int inscns_cap);
+
+}  // namespace bcfgpu

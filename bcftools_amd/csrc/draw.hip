@@ -22,14 +22,7 @@
 #include <cstring>
 #include <vector>
 #include <algorithm>
-#include "kernels.h"
-
-struct bcfgpu_ctx;
-int bcfgpu_set_error(int code, const char *what);
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *ctx, hipStream_t *stream, const float **q2p);
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *ctx, int slot, size_t bytes);
-extern "C" const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *ctx);
-extern "C" bcfgpu::DrawState *bcfgpu_internal_draw_state(bcfgpu_ctx *ctx);
+#include "ctx.h"
 
 namespace bcfgpu {
 
@@ -163,24 +156,24 @@ extern "C" int bcfgpu_errmod_plan_visit(bcfgpu_ctx *ctx, const bcfgpu_tile *snp,
     for (int t = 0; t < 2; ++t) {
         if (!tiles[t] || !n_reads[t]) continue;
         const size_t words = (size_t)((n_reads[t] + 31) / 32);
-        bits[t] = (uint32_t*)bcfgpu_internal_ws(ctx, 136 + t, words * 4 + 64);
+        bits[t] = (uint32_t*)bcfgpu_internal_ws(ctx, t ? WS_DRAW_BITS_INDEL : WS_DRAW_BITS_SNP, words * 4 + 64);
         if (!bits[t]) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
         DR_CHK(hipMemsetAsync(bits[t], 0, words * 4, stream));
     }
-    DrawEnt *d_ent = (DrawEnt*)bcfgpu_internal_ws(ctx, 138, (size_t)cap * sizeof(DrawEnt) + 64);
-    unsigned long long *d_ctr = (unsigned long long*)bcfgpu_internal_ws(ctx, 139, 64);
+    DrawEnt *d_ent = (DrawEnt*)bcfgpu_internal_ws(ctx, WS_DRAW_ENT, (size_t)cap * sizeof(DrawEnt) + 64);
+    unsigned long long *d_ctr = (unsigned long long*)bcfgpu_internal_ws(ctx, WS_DRAW_CTR, 64);
     if (!d_ent || !d_ctr) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
     DR_CHK(hipMemsetAsync(d_ctr, 0, 64, stream));
     int32_t *d_cols = nullptr, *d_ret = nullptr;
     if (indel && indel->n_sites) {
-        d_cols = (int32_t*)bcfgpu_internal_ws(ctx, 140, (size_t)indel->n_sites * 8 + 64);
+        d_cols = (int32_t*)bcfgpu_internal_ws(ctx, WS_DRAW_COLS, (size_t)indel->n_sites * 8 + 64);
         if (!d_cols) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
         DR_CHK(hipMemcpyAsync(d_cols, indel_cols, (size_t)indel->n_sites * 4, hipMemcpyHostToDevice, stream));
         if (indel_ret) { d_ret = d_cols + indel->n_sites; DR_CHK(hipMemcpyAsync(d_ret, indel_ret, (size_t)indel->n_sites * 4, hipMemcpyHostToDevice, stream)); }
     }
     uint8_t *d_visit = nullptr;
     if (snp && snp_visit && snp->n_sites) {
-        d_visit = (uint8_t*)bcfgpu_internal_ws(ctx, 132, (size_t)snp->n_sites + 64);
+        d_visit = (uint8_t*)bcfgpu_internal_ws(ctx, WS_DRAW_VISIT, (size_t)snp->n_sites + 64);
         if (!d_visit) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
         DR_CHK(hipMemcpyAsync(d_visit, snp_visit, (size_t)snp->n_sites, hipMemcpyHostToDevice, stream));
     }
@@ -206,8 +199,8 @@ extern "C" int bcfgpu_errmod_plan_visit(bcfgpu_ctx *ctx, const bcfgpu_tile *snp,
     std::vector<unsigned long long> idx_off(n_ent);
     unsigned long long draws = 0, usable = 0;
     for (uint32_t k = 0; k < n_ent; ++k) { ent[k].off = draws; draws += ent[k].n - 1; idx_off[k] = usable; usable += ent[k].n; }
-    unsigned long long *d_ioff = (unsigned long long*)bcfgpu_internal_ws(ctx, 141, (size_t)n_ent * 8 + 64);
-    uint32_t *d_idx = (uint32_t*)bcfgpu_internal_ws(ctx, 142, (size_t)usable * 4 + 64);
+    unsigned long long *d_ioff = (unsigned long long*)bcfgpu_internal_ws(ctx, WS_DRAW_IDX_OFF, (size_t)n_ent * 8 + 64);
+    uint32_t *d_idx = (uint32_t*)bcfgpu_internal_ws(ctx, WS_DRAW_IDX, (size_t)usable * 4 + 64);
     if (!d_ioff || !d_idx) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
     DR_CHK(hipMemcpyAsync(d_ent, ent.data(), (size_t)n_ent * sizeof(DrawEnt), hipMemcpyHostToDevice, stream));
     DR_CHK(hipMemcpyAsync(d_ioff, idx_off.data(), (size_t)n_ent * 8, hipMemcpyHostToDevice, stream));

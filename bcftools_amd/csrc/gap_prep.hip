@@ -28,15 +28,9 @@
 #include <cmath>
 #include <chrono>
 #include <limits.h>
-#include "kernels.h"
+#include "ctx.h"
 
 using namespace bcfgpu;
-
-extern "C" bcfgpu_gap_stats *bcfgpu_internal_gap_stats(bcfgpu_ctx *ctx);
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *c, int slot, size_t bytes);
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *c, hipStream_t *stream, const float **q2p);
-extern "C" void *bcfgpu_internal_pinned(bcfgpu_ctx *c, int slot, size_t bytes);
-int bcfgpu_set_error(int code, const char *what);
 
 namespace bcfgpu {
 
@@ -621,16 +615,13 @@ __global__ __launch_bounds__(256) void gap_fin_aux_kernel(const GapSite *sites, 
 // =====================================================================================================================
 // host: transfers and launch sequencing only
 #define GP_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
-#define WS(slot, bytes) bcfgpu_internal_ws(ctx, 40 + (slot), (bytes) + 64)      /* slots 40..: this stage's own */
-
-extern "C" int bcfgpu_internal_n_cu(const bcfgpu_ctx *c);
-extern "C" int bcfgpu_internal_side(bcfgpu_ctx *c, hipStream_t **streams, hipEvent_t **events);
+#define WS(slot, bytes) bcfgpu_internal_ws(ctx, slot, (bytes) + 64)      /* 64 bytes of padding on every workspace of the stage */
 
 // The stage on arrays that are already in HBM (`g`: device pointers throughout; n_ent pileup entries).  d_aux [n_ent]
 // (device) receives p->aux; the per-site outputs go to the host arrays of `out` (out->p_aux is not touched: the callers
 // decide whether the entries' words leave the device).  Three waits on the stream: the totals that size the second
 // half's buffers, the count of wide-band jobs, the per-site results.
-int bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint32_t *d_aux, const bcfgpu_indel_out *out, int inscns_cap)
+int bcfgpu::bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint32_t *d_aux, const bcfgpu_indel_out *out, int inscns_cap)
 {
     hipStream_t st;
     const float *q2p;
@@ -640,14 +631,14 @@ int bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint
     auto ms_since = [](std::chrono::steady_clock::time_point t0) {
         return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     const int ns = g.n_sites, n = g.n_smpl, nr = g.n_reads;
-    GapSite *d_sites = (GapSite*)WS(25, (size_t)ns * sizeof(GapSite));
-    uint32_t *d_rinfo = (uint32_t*)WS(26, (size_t)nr * 4);
+    GapSite *d_sites = (GapSite*)WS(WS_GAP_SITES, (size_t)ns * sizeof(GapSite));
+    uint32_t *d_rinfo = (uint32_t*)WS(WS_GAP_READ_INFO, (size_t)nr * 4);
     // small outputs share one block: ret, types[4], maxins, indelreg, max_support, max_frac per site, then the totals
     const size_t so_ret = 0, so_types = (size_t)ns * 4, so_maxins = so_types + (size_t)ns * 16, so_ireg = so_maxins + (size_t)ns * 4,
                  so_msup = so_ireg + (size_t)ns * 4, so_mfrac = so_msup + (size_t)ns * 4, so_tot = (so_mfrac + (size_t)ns * 4 + 15) & ~(size_t)15,
                  so_bytes = so_tot + sizeof(GapTotals) + sizeof(ProbalnQueue);
-    uint8_t *d_small = (uint8_t*)WS(28, so_bytes);
-    uint8_t *h_small = (uint8_t*)bcfgpu_internal_pinned(ctx, 0, so_bytes);
+    uint8_t *d_small = (uint8_t*)WS(WS_GAP_SMALL, so_bytes);
+    uint8_t *h_small = (uint8_t*)bcfgpu_internal_pinned(ctx, PIN_GAP_SMALL, so_bytes);
     if (!d_sites || !d_rinfo || !d_small || !h_small) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep: device workspace");
     int32_t *o_ret = (int32_t*)(d_small + so_ret), *o_types = (int32_t*)(d_small + so_types), *o_maxins = (int32_t*)(d_small + so_maxins);
     int32_t *o_ireg = (int32_t*)(d_small + so_ireg), *o_msup = (int32_t*)(d_small + so_msup);
@@ -671,27 +662,27 @@ int bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint
     int8_t *d_oinscns = nullptr;
     if (tot.n_live) {
         const size_t nj = (size_t)tot.n_jobs;
-        int32_t *d_inscnt = (int32_t*)WS(16, (size_t)tot.ins_bytes * 5 * 4);
-        int8_t *d_inscns = (int8_t*)WS(17, (size_t)tot.ins_bytes);
+        int32_t *d_inscnt = (int32_t*)WS(WS_GAP_INSCNT, (size_t)tot.ins_bytes * 5 * 4);
+        int8_t *d_inscns = (int8_t*)WS(WS_GAP_INSCNS, (size_t)tot.ins_bytes);
         // (the realignment reads 8 bytes at a time, up to two groups ahead; the LDS class reads the bases under its whole band, which
         // hangs over a row's ends by up to PROBALN_LDS16_MAX + 16 positions: 512 bytes of padding on both sides)
-        uint8_t *d_ref2 = (uint8_t*)WS(18, (size_t)tot.ref2_bytes + 1024);
+        uint8_t *d_ref2 = (uint8_t*)WS(WS_GAP_REF2, (size_t)tot.ref2_bytes + 1024);
         if (d_ref2) d_ref2 += 512;
-        int32_t *d_s1 = (int32_t*)WS(19, nj * 4), *d_s2 = (int32_t*)WS(20, nj * 4);
-        uint32_t *d_wide = (uint32_t*)WS(21, nj * 4);
-        GapEntry *d_ent = (GapEntry*)WS(29, n_ent * sizeof(GapEntry));
-        uint8_t *d_qpack = (uint8_t*)WS(30, (size_t)tot.qpack8 * 8 + 64);
-        PJob *d_pjob = (PJob*)WS(31, nj * sizeof(PJob));
-        uint32_t *d_k0 = (uint32_t*)WS(32, nj * 4), *d_v0 = (uint32_t*)WS(33, nj * 4), *d_k1 = (uint32_t*)WS(34, nj * 4), *d_v1 = (uint32_t*)WS(35, nj * 4);
-        uint32_t *d_list2 = (uint32_t*)WS(36, nj * 4);
-        ProbalnQueue *d_queue = (ProbalnQueue*)WS(38, sizeof(ProbalnQueue));
-        double2 *d_emt = (double2*)bcfgpu_internal_ws(ctx, 133, 256 * sizeof(double2));
-        int32_t *d_sumq = (int32_t*)WS(39, (size_t)ns * 64 * 4);
-        uint8_t *d_otype = (uint8_t*)WS(40, (size_t)ns * 64);
+        int32_t *d_s1 = (int32_t*)WS(WS_GAP_SCORE1, nj * 4), *d_s2 = (int32_t*)WS(WS_GAP_SCORE2, nj * 4);
+        uint32_t *d_wide = (uint32_t*)WS(WS_GAP_WIDE, nj * 4);
+        GapEntry *d_ent = (GapEntry*)WS(WS_GAP_ENT, n_ent * sizeof(GapEntry));
+        uint8_t *d_qpack = (uint8_t*)WS(WS_GAP_QPACK, (size_t)tot.qpack8 * 8 + 64);
+        PJob *d_pjob = (PJob*)WS(WS_GAP_PJOB, nj * sizeof(PJob));
+        uint32_t *d_k0 = (uint32_t*)WS(WS_GAP_KEY_IN, nj * 4), *d_v0 = (uint32_t*)WS(WS_GAP_VAL_IN, nj * 4), *d_k1 = (uint32_t*)WS(WS_GAP_KEY_SORTED, nj * 4), *d_v1 = (uint32_t*)WS(WS_GAP_VAL_SORTED, nj * 4);
+        uint32_t *d_list2 = (uint32_t*)WS(WS_GAP_LIST2, nj * 4);
+        ProbalnQueue *d_queue = (ProbalnQueue*)WS(WS_GAP_QUEUE, sizeof(ProbalnQueue));
+        double2 *d_emt = (double2*)bcfgpu_internal_ws(ctx, WS_GAP_EMT, 256 * sizeof(double2));
+        int32_t *d_sumq = (int32_t*)WS(WS_GAP_SUMQ, (size_t)ns * 64 * 4);
+        uint8_t *d_otype = (uint8_t*)WS(WS_GAP_OTYPE, (size_t)ns * 64);
         size_t sort_bytes = 0;
         GP_CHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_k0, d_k1, d_v0, d_v1, (int)nj, 0, 17, st));
-        void *d_sort = WS(37, sort_bytes);
-        if (out->inscns) d_oinscns = (int8_t*)WS(22, (size_t)ns * 4 * inscns_cap);
+        void *d_sort = WS(WS_GAP_SORT_TMP, sort_bytes);
+        if (out->inscns) d_oinscns = (int8_t*)WS(WS_GAP_OUT_INSCNS, (size_t)ns * 4 * inscns_cap);
         if (!d_inscnt || !d_inscns || !d_ref2 || !d_s1 || !d_s2 || !d_wide || !d_ent || !d_qpack || !d_pjob || !d_k0 || !d_v0 || !d_k1 || !d_v1 ||
             !d_list2 || !d_queue || !d_emt || !d_sort || !d_sumq || !d_otype || (out->inscns && !d_oinscns))
             return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep: device workspace");
@@ -741,7 +732,7 @@ int bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint
             chunk = chunk < 64 ? 64 : (chunk & ~(size_t)63);
             if (chunk > tot.n_wide) chunk = ((size_t)tot.n_wide + 63) & ~(size_t)63;
             p.scratch_stride = chunk;
-            p.scratch = (double*)WS(23, 2 * (size_t)p.ncell * chunk * sizeof(double));
+            p.scratch = (double*)WS(WS_GAP_WIDE_ROWS, 2 * (size_t)p.ncell * chunk * sizeof(double));
             if (!p.scratch) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep: device workspace");
             for (size_t j0 = 0; j0 < tot.n_wide; j0 += chunk) {
                 p.wide_first = (uint32_t)j0;
@@ -814,15 +805,15 @@ extern "C" int bcfgpu_gap_prep(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bc
     const long ref_hi = pmax + 1 + (long)strnlen(in->ref + pmax + 1, 65536 + 4096);   // the caller guarantees ref[pos+1] exists (mpileup.c:341)
 
     // ---- inputs to HBM (queued on the stream; the kernels follow in order) ----
-    int32_t *d_rpos = (int32_t*)WS(0, (size_t)nr * 4), *d_rlq = (int32_t*)WS(1, (size_t)nr * 4), *d_rflag = (int32_t*)WS(2, (size_t)nr * 4);
-    int32_t *d_rncig = (int32_t*)WS(3, (size_t)nr * 4), *d_rcoff = (int32_t*)WS(4, (size_t)nr * 4), *d_rsoff = (int32_t*)WS(5, (size_t)nr * 4);
-    uint32_t *d_cig = (uint32_t*)WS(6, ncig * 4);
-    uint8_t *d_seq = (uint8_t*)WS(7, nbase), *d_qual = (uint8_t*)WS(8, nbase), *d_zq = any_zq ? (uint8_t*)WS(9, nbase) : nullptr;
-    uint8_t *d_haszq = any_zq ? (uint8_t*)WS(10, (size_t)nr) : nullptr;
-    int32_t *d_pos = (int32_t*)WS(11, (size_t)ns * 4), *d_soff = (int32_t*)WS(12, ((size_t)ns * n + 1) * 4);
-    int32_t *d_pread = (int32_t*)WS(13, n_ent * 4), *d_pqpos = (int32_t*)WS(14, n_ent * 4), *d_pindel = (int32_t*)WS(15, n_ent * 4);
-    char *d_ref = (char*)WS(24, (size_t)(ref_hi - ref_lo));
-    uint32_t *d_aux = (uint32_t*)WS(27, n_ent * 4);
+    int32_t *d_rpos = (int32_t*)WS(WS_GAP_R_POS, (size_t)nr * 4), *d_rlq = (int32_t*)WS(WS_GAP_R_LQ, (size_t)nr * 4), *d_rflag = (int32_t*)WS(WS_GAP_R_FLAG, (size_t)nr * 4);
+    int32_t *d_rncig = (int32_t*)WS(WS_GAP_R_NCIG, (size_t)nr * 4), *d_rcoff = (int32_t*)WS(WS_GAP_R_CIG_OFF, (size_t)nr * 4), *d_rsoff = (int32_t*)WS(WS_GAP_R_SEQ_OFF, (size_t)nr * 4);
+    uint32_t *d_cig = (uint32_t*)WS(WS_GAP_CIG, ncig * 4);
+    uint8_t *d_seq = (uint8_t*)WS(WS_GAP_SEQ, nbase), *d_qual = (uint8_t*)WS(WS_GAP_QUAL, nbase), *d_zq = any_zq ? (uint8_t*)WS(WS_GAP_ZQ, nbase) : nullptr;
+    uint8_t *d_haszq = any_zq ? (uint8_t*)WS(WS_GAP_HAS_ZQ, (size_t)nr) : nullptr;
+    int32_t *d_pos = (int32_t*)WS(WS_GAP_POS, (size_t)ns * 4), *d_soff = (int32_t*)WS(WS_GAP_SMPL_OFF, ((size_t)ns * n + 1) * 4);
+    int32_t *d_pread = (int32_t*)WS(WS_GAP_P_READ, n_ent * 4), *d_pqpos = (int32_t*)WS(WS_GAP_P_QPOS, n_ent * 4), *d_pindel = (int32_t*)WS(WS_GAP_P_INDEL, n_ent * 4);
+    char *d_ref = (char*)WS(WS_GAP_REF, (size_t)(ref_hi - ref_lo));
+    uint32_t *d_aux = (uint32_t*)WS(WS_GAP_AUX, n_ent * 4);
     if (!d_rpos || !d_rlq || !d_rflag || !d_rncig || !d_rcoff || !d_rsoff || !d_cig || !d_seq || !d_qual || (any_zq && (!d_zq || !d_haszq)) ||
         !d_pos || !d_soff || !d_pread || !d_pqpos || !d_pindel || !d_ref || !d_aux)
         return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep: device workspace");

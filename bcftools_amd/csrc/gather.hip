@@ -13,15 +13,9 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "kernels.h"
+#include "ctx.h"
 
 using namespace bcfgpu;
-
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *c, int slot, size_t bytes);
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *c, hipStream_t *stream, const float **q2p);
-extern "C" const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *c);
-extern "C" void *bcfgpu_internal_pinned(bcfgpu_ctx *c, int slot, size_t bytes);
-int bcfgpu_set_error(int code, const char *what);
 
 namespace bcfgpu {
 
@@ -91,13 +85,13 @@ extern "C" int bcfgpu_compact_calls_async(bcfgpu_ctx *ctx, int32_t n_sites, int3
     if (hipMemsetAsync(d_counts, 0, 4 * sizeof(uint64_t), st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_compact_calls_async: counters");
     if (n_sites == 0) return 0;
     const int S = bcfgpu_internal_cfg(ctx)->n_smpl;
-    unsigned long long *d_size = (unsigned long long*)bcfgpu_internal_ws(ctx, 35, ((size_t)n_sites + 1) * 8 + 64);
+    unsigned long long *d_size = (unsigned long long*)bcfgpu_internal_ws(ctx, WS_COMPACT_SIZE, ((size_t)n_sites + 1) * 8 + 64);
     if (!d_size) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_compact_calls_async: device workspace");
     hipLaunchKernelGGL(compact_size_kernel, dim3((n_sites + 256) / 256), dim3(256), 0, st, cout->site, n_sites, S, variants_only, d_size,
                        reinterpret_cast<unsigned long long*>(d_counts));
     size_t tmp = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_size, d_size, n_sites + 1, st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "scan");
-    void *d_tmp = bcfgpu_internal_ws(ctx, 36, tmp + 64);
+    void *d_tmp = bcfgpu_internal_ws(ctx, WS_COMPACT_SCAN_TMP, tmp + 64);
     if (!d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_compact_calls_async: device workspace");
     if (hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, d_size, d_size, n_sites + 1, st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "scan");
     hipLaunchKernelGGL(compact_copy_kernel, dim3(n_sites), dim3(256), 0, st, cout->site, msite, cout->gt, cout->pl, n_gt_planes, S, n_sites, site0,
@@ -111,7 +105,7 @@ extern "C" int bcfgpu_compact_counts(bcfgpu_ctx *ctx, const uint64_t *d_counts, 
     if (!ctx || !d_counts || !n_bytes) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_compact_counts: bad arguments");
     hipStream_t st;
     if (bcfgpu_internal_device(ctx, &st, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_compact_counts: bad context");
-    uint64_t *h = (uint64_t*)bcfgpu_internal_pinned(ctx, 1, 4 * sizeof(uint64_t));
+    uint64_t *h = (uint64_t*)bcfgpu_internal_pinned(ctx, PIN_COMPACT_COUNTS, 4 * sizeof(uint64_t));
     if (!h) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_compact_counts: staging");
     if (hipMemcpyAsync(h, d_counts, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_compact_counts: read");
@@ -126,7 +120,7 @@ extern "C" int bcfgpu_compact_calls(bcfgpu_ctx *ctx, int32_t n_sites, int32_t si
 {
     if (!n_bytes) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_compact_calls: bad arguments");
     *n_bytes = 0; if (n_rec) *n_rec = 0;
-    uint64_t *d_counts = (uint64_t*)bcfgpu_internal_ws(ctx, 37, 64);
+    uint64_t *d_counts = (uint64_t*)bcfgpu_internal_ws(ctx, WS_COMPACT_COUNTS, 64);
     if (!d_counts) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_compact_calls: device workspace");
     const int rc = bcfgpu_compact_calls_async(ctx, n_sites, site0, msite, cout, n_gt_planes, variants_only, d_buf, cap_bytes, d_counts);
     if (rc) return rc;

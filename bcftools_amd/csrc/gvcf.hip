@@ -12,12 +12,7 @@
 // Everything is integer: bit-exact against the oracle's sequential restatement (oracle/gvcf.c).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include "kernels.h"
-
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *ctx, hipStream_t *stream, const float **q2p);
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *ctx, int slot, size_t bytes);
-extern "C" const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *c);
-int bcfgpu_set_error(int code, const char *what);
+#include "ctx.h"
 
 namespace bcfgpu {
 
@@ -160,8 +155,8 @@ extern "C" int bcfgpu_gvcf_blocks(bcfgpu_ctx *ctx, const bcfgpu_gvcf_in *in, con
     P.blk = out->blk; P.min_dp = out->min_dp; P.block = out->block; P.dp_out = out->dp; P.pl_out = out->pl;
     size_t tmp_bytes = 0;
     GV_CHK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, (int32_t*)nullptr, (int32_t*)nullptr, n, stream));
-    int32_t *w = (int32_t*)bcfgpu_internal_ws(ctx, 32, (size_t)n * 3 * sizeof(int32_t));
-    void *d_tmp = bcfgpu_internal_ws(ctx, 33, tmp_bytes + 16);
+    int32_t *w = (int32_t*)bcfgpu_internal_ws(ctx, WS_GVCF_SCAN, (size_t)n * 3 * sizeof(int32_t));
+    void *d_tmp = bcfgpu_internal_ws(ctx, WS_GVCF_SCAN_TMP, tmp_bytes + 16);
     if (!w || !d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gvcf_blocks: workspace");
     P.range = w; P.head = w + n; P.scan = w + 2 * (size_t)n;
     hipLaunchKernelGGL(gvcf_site_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, P);

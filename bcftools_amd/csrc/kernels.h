@@ -137,7 +137,28 @@ struct DevPool {
     uint8_t *zq, *r_has_zq;          // the "ZQ" bytes bcfgpu_pool_baq left and which reads have them; NULL before
     uint8_t *keep;                   // [n_reads] 0 = the read does not enter the pileup (bcfgpu_pool_keep); NULL = all do
     int ext_valid, ext_lo, ext_hi;   // [lowest start, highest end) of the reads on the reference, once something asked for it
-    int qual_slot;                   // the workspace slot `qual` lives in (bcfgpu_pool_baq writes the new qualities to another one)
+    int qual_slot;                   // the workspace slot (ctx.h) `qual` lives in (bcfgpu_pool_baq writes the new qualities to another one)
+};
+
+// ---- the pileup of the read pool (pileup.hip; bcfgpu_pool_pileup keeps the parameters of the last one in the context) ----
+struct ReadMeta;                    // pileup.hip
+struct PileupParams {
+    int n_sites, n_smpl, beg, want_epos, max_span;
+    // reads in (sample, position) order: index k of the sorted list
+    const int32_t *smpl_off;        // [n_smpl+1] into the sorted list
+    const int32_t *s_pos;           // [n_reads] reference start of sorted read k (the binary searches)
+    const int32_t *s_read;          // [n_reads] pool index of sorted read k
+    const ReadMeta *meta;           // [n_reads] everything else about sorted read k, one 32-byte record
+    const uint32_t *cig;
+    const uint8_t *seq16, *qual;
+    // out
+    uint32_t *cnt;                  // [n_cells + 1] pass 1: reads per cell; after the scan: plp_off
+    uint32_t *rd; uint8_t *epos;    // pass 2
+    uint32_t *col_indel;            // [n_sites] entries of the column that are followed by an indel (n_alt of bam2bcf_indel.c:117-140)
+    int n_reads;                    // reads of the pool (bcfgpu_gap_prep_tile)
+    uint32_t n_bases;               // bases of the pool's seq16 / qual
+    const int *d_span;              // the longest reference span of a read, as pileup_meta_kernel left it (max_span once the host has read it)
+    int ref_len;                    // length of the contig handed to bcfgpu_pileup (bcfgpu_gap_prep_tile: the end of par->ref)
 };
 
 // ---- bcf_call_gap_prep on the device (gap_prep.hip, indel.hip) ----

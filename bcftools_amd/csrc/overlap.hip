@@ -9,11 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <vector>
-#include "kernels.h"
-
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *ctx, hipStream_t *stream, const float **q2p);
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *ctx, int slot, size_t bytes);
-int bcfgpu_set_error(int code, const char *what);
+#include "ctx.h"
 
 namespace bcfgpu {
 
@@ -97,12 +93,11 @@ extern "C" int bcfgpu_overlap_tweak(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, int
         }
     }
     if (n_pairs == 0 || nbase == 0) { if (nbase) std::memcpy(qual_out, rd->qual, nbase); return BCFGPU_OK; }
-    // context workspaces (shared with the BAQ stage's slots; both finish their stream work before returning)
-    void *d_pa = bcfgpu_internal_ws(ctx, 7, (size_t)n_pairs * 4), *d_pb = bcfgpu_internal_ws(ctx, 8, (size_t)n_pairs * 4),
-         *d_pos = bcfgpu_internal_ws(ctx, 9, (size_t)n * 4), *d_ncig = bcfgpu_internal_ws(ctx, 10, (size_t)n * 4),
-         *d_coff = bcfgpu_internal_ws(ctx, 11, (size_t)n * 4), *d_soff = bcfgpu_internal_ws(ctx, 12, (size_t)n * 4),
-         *d_cig = bcfgpu_internal_ws(ctx, 13, (ncig + 4) * 4), *d_seq = bcfgpu_internal_ws(ctx, 14, nbase + 16),
-         *d_qual = bcfgpu_internal_ws(ctx, 15, nbase + 16);
+    void *d_pa = bcfgpu_internal_ws(ctx, WS_OVL_PAIR_A, (size_t)n_pairs * 4), *d_pb = bcfgpu_internal_ws(ctx, WS_OVL_PAIR_B, (size_t)n_pairs * 4),
+         *d_pos = bcfgpu_internal_ws(ctx, WS_OVL_R_POS, (size_t)n * 4), *d_ncig = bcfgpu_internal_ws(ctx, WS_OVL_R_NCIG, (size_t)n * 4),
+         *d_coff = bcfgpu_internal_ws(ctx, WS_OVL_R_CIG_OFF, (size_t)n * 4), *d_soff = bcfgpu_internal_ws(ctx, WS_OVL_R_SEQ_OFF, (size_t)n * 4),
+         *d_cig = bcfgpu_internal_ws(ctx, WS_OVL_CIG, (ncig + 4) * 4), *d_seq = bcfgpu_internal_ws(ctx, WS_OVL_SEQ, nbase + 16),
+         *d_qual = bcfgpu_internal_ws(ctx, WS_OVL_QUAL, nbase + 16);
     if (!d_pa || !d_pb || !d_pos || !d_ncig || !d_coff || !d_soff || !d_cig || !d_seq || !d_qual)
         return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_overlap_tweak: device workspace");
     #define OV_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
@@ -127,15 +122,13 @@ extern "C" int bcfgpu_overlap_tweak(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, int
     return BCFGPU_OK;
 }
 
-extern "C" void *bcfgpu_internal_pool_state(bcfgpu_ctx *ctx);
-
 // The same tweak on the pool bcfgpu_pool_upload left in HBM (after bcfgpu_pool_baq): the pairs go up, nothing comes back.
 extern "C" int bcfgpu_pool_overlap_tweak(bcfgpu_ctx *ctx, int32_t n_pairs, const int32_t *pair_a, const int32_t *pair_b)
 {
     if (!ctx || n_pairs < 0 || (n_pairs && (!pair_a || !pair_b))) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_overlap_tweak: bad arguments");
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_overlap_tweak: bad context");
-    const DevPool &D = *static_cast<const DevPool*>(bcfgpu_internal_pool_state(ctx));
+    const DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_overlap_tweak: no read pool on this context (bcfgpu_pool_upload)");
     const int n = D.n_reads;
     {   // every read may be in one pair only (a second pair would race with the first on the read's qualities)
@@ -148,7 +141,7 @@ extern "C" int bcfgpu_pool_overlap_tweak(bcfgpu_ctx *ctx, int32_t n_pairs, const
         }
     }
     if (n_pairs == 0 || D.n_bases == 0) return BCFGPU_OK;
-    void *d_pa = bcfgpu_internal_ws(ctx, 123, (size_t)n_pairs * 4 + 64), *d_pb = bcfgpu_internal_ws(ctx, 124, (size_t)n_pairs * 4 + 64);
+    void *d_pa = bcfgpu_internal_ws(ctx, WS_POVL_PAIR_A, (size_t)n_pairs * 4 + 64), *d_pb = bcfgpu_internal_ws(ctx, WS_POVL_PAIR_B, (size_t)n_pairs * 4 + 64);
     if (!d_pa || !d_pb) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_overlap_tweak: device workspace");
     if (hipMemcpyAsync(d_pa, pair_a, (size_t)n_pairs * 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
         hipMemcpyAsync(d_pb, pair_b, (size_t)n_pairs * 4, hipMemcpyHostToDevice, stream) != hipSuccess)

@@ -24,14 +24,7 @@
 #include <memory>
 #include <thread>
 #include <vector>
-#include "kernels.h"
-
-extern "C" int bcfgpu_internal_device(bcfgpu_ctx *ctx, hipStream_t *stream, const float **q2p);
-extern "C" void *bcfgpu_internal_ws(bcfgpu_ctx *ctx, int slot, size_t bytes);
-extern "C" void *bcfgpu_internal_pinned(bcfgpu_ctx *ctx, int slot, size_t bytes);
-extern "C" const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *ctx);
-extern "C" void *bcfgpu_internal_pileup_state(bcfgpu_ctx *ctx);
-int bcfgpu_set_error(int code, const char *what);
+#include "ctx.h"
 
 namespace bcfgpu {
 
@@ -46,25 +39,6 @@ struct ReadMeta {
     uint32_t pad2;
 };
 static_assert(sizeof(ReadMeta) == 32, "one read = two 16-byte loads");
-
-struct PileupParams {
-    int n_sites, n_smpl, beg, want_epos, max_span;
-    // reads in (sample, position) order: index k of the sorted list
-    const int32_t *smpl_off;        // [n_smpl+1] into the sorted list
-    const int32_t *s_pos;           // [n_reads] reference start of sorted read k (the binary searches)
-    const int32_t *s_read;          // [n_reads] pool index of sorted read k
-    const ReadMeta *meta;           // [n_reads] everything else about sorted read k, one 32-byte record
-    const uint32_t *cig;
-    const uint8_t *seq16, *qual;
-    // out
-    uint32_t *cnt;                  // [n_cells + 1] pass 1: reads per cell; after the scan: plp_off
-    uint32_t *rd; uint8_t *epos;    // pass 2
-    uint32_t *col_indel;            // [n_sites] entries of the column that are followed by an indel (n_alt of bam2bcf_indel.c:117-140)
-    int n_reads;                    // reads of the pool (bcfgpu_gap_prep_tile)
-    uint32_t n_bases;               // bases of the pool's seq16 / qual
-    const int *d_span;              // the longest reference span of a read, as pileup_meta_kernel left it (max_span once the host has read it)
-    int ref_len;                    // length of the contig handed to bcfgpu_pileup (bcfgpu_gap_prep_tile: the end of par->ref)
-};
 
 // first k in [lo, hi) with a[k] > x
 __device__ __forceinline__ int upper_bound(const int32_t *a, int lo, int hi, int x)
@@ -601,7 +575,6 @@ static int ref_nt16(char c)
 // bcfgpu_pileup / bcfgpu_pileup_packed = pool_upload + pool_pileup.  The host part is argument checks, the read -> sample
 // bookkeeping (one pass over r_smpl, none when the caller hands over smpl_off), uploads of the caller's arrays as they are,
 // and launches.
-extern "C" void *bcfgpu_internal_pool_state(bcfgpu_ctx *ctx);
 
 static int host_threads(int n)
 {
@@ -629,8 +602,7 @@ static int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads
         return fail(BCFGPU_E_ARG, "bad packed pool");
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return fail(BCFGPU_E_ARG, "bad context");
-    DevPool &D = *static_cast<DevPool*>(bcfgpu_internal_pool_state(ctx));
-    static_assert(sizeof(DevPool) <= 256, "fits the context's pool_state");
+    DevPool &D = *bcfgpu_internal_pool_state(ctx);
     D = DevPool{};
     const int n = rd->n_reads;
     // the extent of the pools (the packed form states it)
@@ -652,45 +624,42 @@ static int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads
         for (int t = 0; t < nthr; ++t) { nbase = std::max(nbase, t_nbase[t]); ncig = std::max(ncig, t_ncig[t]); }
         if (nbase >> 32) return fail(BCFGPU_E_RANGE, "the pool holds 2^32 or more bases");
     }
-    auto up = [&](int slot, const void *src, size_t bytes) -> void* {
-        void *d = bcfgpu_internal_ws(ctx, slot, bytes + 64);
-        if (d && bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return nullptr;
-        return d;
-    };
     D.n_reads = n; D.n_bases = (uint32_t)nbase; D.n_cig = (uint32_t)ncig;
     if (pk && pk->recs) {
         // the 12-byte records: the arrays are formed here, the offsets by two prefix sums
-        const bcfgpu_read12 *d_rec = (const bcfgpu_read12*)up(128, pk->recs, (size_t)n * sizeof(bcfgpu_read12));
-        int32_t *a_pos = (int32_t*)bcfgpu_internal_ws(ctx, 104, (size_t)n * 4 + 64), *a_lq = (int32_t*)bcfgpu_internal_ws(ctx, 105, (size_t)n * 4 + 64);
-        int32_t *a_flag = (int32_t*)bcfgpu_internal_ws(ctx, 106, (size_t)n * 4 + 64), *a_ncig = (int32_t*)bcfgpu_internal_ws(ctx, 107, (size_t)n * 4 + 64);
-        int32_t *a_coff = (int32_t*)bcfgpu_internal_ws(ctx, 108, (size_t)(n + 1) * 4 + 64), *a_soff = (int32_t*)bcfgpu_internal_ws(ctx, 109, (size_t)(n + 1) * 4 + 64);
-        uint8_t *a_mapq = (uint8_t*)bcfgpu_internal_ws(ctx, 110, (size_t)n + 64);
+        const bcfgpu_read12 *d_rec = (const bcfgpu_read12*)ws_upload(ctx, WS_POOL_RECS, pk->recs, (size_t)n * sizeof(bcfgpu_read12), 64, stream);
+        int32_t *a_pos = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_POS, (size_t)n * 4 + 64), *a_lq = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_LQ, (size_t)n * 4 + 64);
+        int32_t *a_flag = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_FLAG, (size_t)n * 4 + 64), *a_ncig = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_NCIG, (size_t)n * 4 + 64);
+        int32_t *a_coff = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_CIG_OFF, (size_t)(n + 1) * 4 + 64), *a_soff = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_SEQ_OFF, (size_t)(n + 1) * 4 + 64);
+        uint8_t *a_mapq = (uint8_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_MAPQ, (size_t)n + 64);
         if (!d_rec || !a_pos || !a_lq || !a_flag || !a_ncig || !a_coff || !a_soff || !a_mapq) return fail(BCFGPU_E_NOMEM, "device workspace");
         hipLaunchKernelGGL(pool_expand_kernel, dim3((n + 256) / 256), dim3(256), 0, stream, d_rec, n, a_pos, a_lq, a_flag, a_ncig, a_coff, a_soff, a_mapq);
         size_t tmp_bytes = 0;
         if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, a_soff, a_soff, n + 1, stream) != hipSuccess) return fail(BCFGPU_E_HIP, "scan");
-        void *d_tmp = bcfgpu_internal_ws(ctx, 129, tmp_bytes + 64);
+        void *d_tmp = bcfgpu_internal_ws(ctx, WS_POOL_SCAN_TMP, tmp_bytes + 64);
         if (!d_tmp) return fail(BCFGPU_E_NOMEM, "device workspace");
         if (hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, a_soff, a_soff, n + 1, stream) != hipSuccess ||
             hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, a_coff, a_coff, n + 1, stream) != hipSuccess) return fail(BCFGPU_E_HIP, "scan");
         D.r_pos = a_pos; D.r_lq = a_lq; D.r_flag = a_flag; D.r_ncig = a_ncig; D.r_cig_off = a_coff; D.r_seq_off = a_soff; D.r_mapq = a_mapq;
     } else {
-    D.r_pos = (const int32_t*)up(104, rd->r_pos, (size_t)n * 4);
-    D.r_lq = (const int32_t*)up(105, rd->r_lq, (size_t)n * 4);
-    D.r_flag = (const int32_t*)up(106, rd->r_flag, (size_t)n * 4);
-    D.r_ncig = (const int32_t*)up(107, rd->r_ncig, (size_t)n * 4);
-    D.r_cig_off = (const int32_t*)up(108, rd->r_cig_off, (size_t)n * 4);
-    D.r_seq_off = (const int32_t*)up(109, rd->r_seq_off, (size_t)n * 4);
-    D.r_mapq = (uint8_t*)up(110, r_mapq, (size_t)n);
+    D.r_pos = (const int32_t*)ws_upload(ctx, WS_POOL_R_POS, rd->r_pos, (size_t)n * 4, 64, stream);
+    D.r_lq = (const int32_t*)ws_upload(ctx, WS_POOL_R_LQ, rd->r_lq, (size_t)n * 4, 64, stream);
+    D.r_flag = (const int32_t*)ws_upload(ctx, WS_POOL_R_FLAG, rd->r_flag, (size_t)n * 4, 64, stream);
+    D.r_ncig = (const int32_t*)ws_upload(ctx, WS_POOL_R_NCIG, rd->r_ncig, (size_t)n * 4, 64, stream);
+    D.r_cig_off = (const int32_t*)ws_upload(ctx, WS_POOL_R_CIG_OFF, rd->r_cig_off, (size_t)n * 4, 64, stream);
+    D.r_seq_off = (const int32_t*)ws_upload(ctx, WS_POOL_R_SEQ_OFF, rd->r_seq_off, (size_t)n * 4, 64, stream);
+    D.r_mapq = (uint8_t*)ws_upload(ctx, WS_POOL_R_MAPQ, r_mapq, (size_t)n, 64, stream);
     }
-    D.cig = (const uint32_t*)up(27, rd->cig, ncig * 4);
+    D.cig = (const uint32_t*)ws_upload(ctx, WS_POOL_CIG, rd->cig, ncig * 4, 64, stream);
     uint8_t *d_seq16 = nullptr, *d_qual = nullptr;
     if (pk) {
         const size_t n_in = (nbase + 1) / 2;
-        d_seq16 = (uint8_t*)bcfgpu_internal_ws(ctx, 28, nbase + 64);
-        const uint8_t *d_seq4 = (const uint8_t*)up(111, pk->seq4, n_in), *d_qual4 = nullptr;
-        if (pk->qual4) { d_qual = (uint8_t*)bcfgpu_internal_ws(ctx, 29, nbase + 64); d_qual4 = (const uint8_t*)up(112, pk->qual4, pk->qual_bits == 2 ? (nbase + 3) / 4 : n_in); }
-        else d_qual = (uint8_t*)up(29, rd->qual, nbase);
+        d_seq16 = (uint8_t*)bcfgpu_internal_ws(ctx, WS_POOL_SEQ16, nbase + 64);
+        const uint8_t *d_seq4 = (const uint8_t*)ws_upload(ctx, WS_POOL_SEQ4, pk->seq4, n_in, 64, stream), *d_qual4 = nullptr;
+        if (pk->qual4) {
+            d_qual = (uint8_t*)bcfgpu_internal_ws(ctx, WS_POOL_QUAL, nbase + 64);
+            d_qual4 = (const uint8_t*)ws_upload(ctx, WS_POOL_QUAL4, pk->qual4, pk->qual_bits == 2 ? (nbase + 3) / 4 : n_in, 64, stream);
+        } else d_qual = (uint8_t*)ws_upload(ctx, WS_POOL_QUAL, rd->qual, nbase, 64, stream);
         if (!d_seq4 || (pk->qual4 && !d_qual4) || !d_seq16 || !d_qual) return fail(BCFGPU_E_NOMEM, "device workspace");
         unsigned long long pal[2] = {0, 0};
         std::memcpy(pal, pk->palette, 16);
@@ -698,10 +667,10 @@ static int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads
         if (nthreads) hipLaunchKernelGGL(pileup_unpack_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream,
                                          d_seq4, d_qual4, pal[0], pal[1], n_in, d_seq16, d_qual, (int)pk->qual_bits);
     } else {
-        d_seq16 = (uint8_t*)up(28, rd->seq16, nbase);
-        d_qual = (uint8_t*)up(29, rd->qual, nbase);
+        d_seq16 = (uint8_t*)ws_upload(ctx, WS_POOL_SEQ16, rd->seq16, nbase, 64, stream);
+        d_qual = (uint8_t*)ws_upload(ctx, WS_POOL_QUAL, rd->qual, nbase, 64, stream);
     }
-    D.seq16 = d_seq16; D.qual = d_qual; D.qual_slot = 29;
+    D.seq16 = d_seq16; D.qual = d_qual; D.qual_slot = WS_POOL_QUAL;
     if (!D.r_pos || !D.r_lq || !D.r_flag || !D.r_ncig || !D.r_cig_off || !D.r_seq_off || !D.r_mapq || !D.cig || !D.seq16 || !D.qual)
         return fail(BCFGPU_E_NOMEM, "device workspace");
     if (hipGetLastError() != hipSuccess) return fail(BCFGPU_E_HIP, "launch");
@@ -726,7 +695,7 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
     if (!ctx || !tile || end < beg || (ref_len > 0 && !ref)) return fail(BCFGPU_E_ARG, "bad arguments");
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return fail(BCFGPU_E_ARG, "bad context");
-    const DevPool &D = *static_cast<const DevPool*>(bcfgpu_internal_pool_state(ctx));
+    const DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return fail(BCFGPU_E_ARG, "no read pool on this context (bcfgpu_pool_upload)");
     if (D.n_reads && !r_smpl && !given_off) return fail(BCFGPU_E_ARG, "bad arguments");
     const bcfgpu_cfg *cfg = bcfgpu_internal_cfg(ctx);
@@ -796,26 +765,21 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
     if (trace) fprintf(stderr, "[pileup] host preparation done at %.2f ms\n", ms_now());
     // ---- device ----
     #define PL_CHK(call) do { if ((call) != hipSuccess) return fail(BCFGPU_E_HIP, #call); } while (0)
-    auto up = [&](int slot, const void *src, size_t bytes) -> void* {
-        void *d = bcfgpu_internal_ws(ctx, slot, bytes + 64);
-        if (d && bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return nullptr;
-        return d;
-    };
     PileupParams P{};
     P.n_sites = n_sites; P.n_smpl = S; P.beg = beg; P.max_span = 1; P.n_reads = n; P.n_bases = D.n_bases;
     P.want_epos = (cfg->fmt_flag & (BCFGPU_INFO_RPB | BCFGPU_INFO_VDB)) ? 1 : 0;
-    void *d_ref16 = up(16, ref16.data(), (size_t)n_sites);
-    P.smpl_off = (const int32_t*)up(17, smpl_off.data(), (size_t)(S + 1) * 4);
+    void *d_ref16 = ws_upload(ctx, WS_PLP_REF16, ref16.data(), (size_t)n_sites, 64, stream);
+    P.smpl_off = (const int32_t*)ws_upload(ctx, WS_PLP_SMPL_OFF, smpl_off.data(), (size_t)(S + 1) * 4, 64, stream);
     MetaParams M{};
     M.n = n; M.n_smpl = S; M.smpl_off = P.smpl_off;
     M.r_pos = D.r_pos; M.r_lq = D.r_lq; M.r_flag = D.r_flag; M.r_ncig = D.r_ncig; M.r_cig_off = D.r_cig_off; M.r_seq_off = D.r_seq_off;
     M.r_mapq = D.r_mapq; M.keep = D.keep; M.cig = D.cig;
-    M.s_read = s_read ? (const int32_t*)up(20, s_read, (size_t)n * 4) : nullptr;
-    M.meta = (ReadMeta*)bcfgpu_internal_ws(ctx, 19, (size_t)n * sizeof(ReadMeta) + 64);
-    M.s_pos = (int32_t*)bcfgpu_internal_ws(ctx, 18, (size_t)n * 4 + 64);
-    M.status = (int*)bcfgpu_internal_ws(ctx, 113, 64);
+    M.s_read = s_read ? (const int32_t*)ws_upload(ctx, WS_PLP_S_READ, s_read, (size_t)n * 4, 64, stream) : nullptr;
+    M.meta = (ReadMeta*)bcfgpu_internal_ws(ctx, WS_PLP_META, (size_t)n * sizeof(ReadMeta) + 64);
+    M.s_pos = (int32_t*)bcfgpu_internal_ws(ctx, WS_PLP_S_POS, (size_t)n * 4 + 64);
+    M.status = (int*)bcfgpu_internal_ws(ctx, WS_PLP_STATUS, 64);
     P.cig = D.cig; P.seq16 = D.seq16; P.qual = D.qual; P.s_read = M.s_read; P.meta = M.meta; P.s_pos = M.s_pos; P.d_span = M.status;
-    uint32_t *d_cnt = (uint32_t*)bcfgpu_internal_ws(ctx, 30, (ncells + 1) * 4 + (size_t)n_sites * 4 + 64);
+    uint32_t *d_cnt = (uint32_t*)bcfgpu_internal_ws(ctx, WS_PLP_CNT, (ncells + 1) * 4 + (size_t)n_sites * 4 + 64);
     if (!d_ref16 || !P.smpl_off || (s_read && !M.s_read) || !M.meta || !M.s_pos || !M.status || !d_cnt) return fail(BCFGPU_E_NOMEM, "device workspace");
     P.cnt = d_cnt;
     P.col_indel = d_cnt + ncells + 1;
@@ -831,14 +795,14 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
     if (ncells) {
         hipLaunchKernelGGL(pileup_kernel<false>, dim3(grid), dim3(256), 0, stream, P);
         // the total in 64 bits first: plp_off is 32-bit, a region whose pileup reaches 2^32 entries must be refused, not wrapped
-        unsigned long long *d_tot64 = (unsigned long long*)bcfgpu_internal_ws(ctx, 34, 64);
+        unsigned long long *d_tot64 = (unsigned long long*)bcfgpu_internal_ws(ctx, WS_PLP_TOTAL, 64);
         if (!d_tot64) return fail(BCFGPU_E_NOMEM, "device workspace");
         PL_CHK(hipMemsetAsync(d_tot64, 0, 8, stream));
         hipLaunchKernelGGL(count_total_kernel, dim3((unsigned)std::min<size_t>((ncells + 4095) / 4096, 1024)), dim3(256), 0, stream, d_cnt, ncells, d_tot64);   // (one atomic per wavefront on one word: few, long-running workgroups)
         // plp_off = exclusive prefix sum of the counts (in place, one element past the end for the total)
         size_t tmp_bytes = 0;
         PL_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt, d_cnt, (int)(ncells + 1), stream));
-        void *d_tmp = bcfgpu_internal_ws(ctx, 31, tmp_bytes + 16);
+        void *d_tmp = bcfgpu_internal_ws(ctx, WS_PLP_SCAN_TMP, tmp_bytes + 16);
         if (!d_tmp) return fail(BCFGPU_E_NOMEM, "device workspace");
         PL_CHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_cnt, d_cnt, (int)(ncells + 1), stream));
         unsigned long long tot64 = 0;
@@ -857,7 +821,7 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
     if (trace) fprintf(stderr, "[pileup] counted and scanned at %.2f ms (%u entries)\n", ms_now(), total);
     // the read records: the scan's temporary storage is done with, its slot is reused (grow-only) for rd + epos
     const size_t epos_at = (((size_t)total + 4) * 4 + 255) & ~(size_t)255;      // both arrays aligned for 16-byte staging loads
-    uint8_t *d_out = (uint8_t*)bcfgpu_internal_ws(ctx, 31, epos_at + (size_t)total + 64);
+    uint8_t *d_out = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PLP_RECS, epos_at + (size_t)total + 64);
     if (!d_out) return fail(BCFGPU_E_NOMEM, "device workspace");
     P.rd = (uint32_t*)d_out; P.epos = d_out + epos_at;
     if (total) hipLaunchKernelGGL(pileup_kernel<true>, dim3(grid), dim3(256), 0, stream, P);
@@ -866,8 +830,8 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
     if ((col_n || col_indel) && n_sites) {
         // per column: its entries (the difference of two offsets, formed on the device: the offsets themselves are 4 bytes a cell and
         // stay in HBM) and whether any is followed by an indel; two words a column come back, through page-locked memory
-        uint32_t *d_cc = (uint32_t*)bcfgpu_internal_ws(ctx, 134, (size_t)n_sites * 8 + 64);
-        uint32_t *h_cc = (uint32_t*)bcfgpu_internal_pinned(ctx, 3, (size_t)n_sites * 8 + 64);
+        uint32_t *d_cc = (uint32_t*)bcfgpu_internal_ws(ctx, WS_PLP_COL_COUNTS, (size_t)n_sites * 8 + 64);
+        uint32_t *h_cc = (uint32_t*)bcfgpu_internal_pinned(ctx, PIN_PLP_COL_COUNTS, (size_t)n_sites * 8 + 64);
         if (!d_cc || !h_cc) return fail(BCFGPU_E_NOMEM, "device workspace");
         hipLaunchKernelGGL(col_counts_kernel, dim3((n_sites + 255) / 256), dim3(256), 0, stream, d_cnt, P.col_indel, n_sites, S, d_cc);
         PL_CHK(hipMemcpyAsync(h_cc, d_cc, (size_t)n_sites * 8, hipMemcpyDeviceToHost, stream));
@@ -878,9 +842,8 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
         }
     }
     #undef PL_CHK
-    static_assert(sizeof(PileupParams) <= 256, "fits the context's pileup_state");
     P.ref_len = ref_len;
-    std::memcpy(bcfgpu_internal_pileup_state(ctx), &P, sizeof P);          // for bcfgpu_pileup_entries
+    *bcfgpu_internal_pileup_state(ctx) = P;          // for bcfgpu_pileup_entries
     tile->n_sites = n_sites; tile->is_indel = 0; tile->n_reads = total;
     tile->ref16 = (const int8_t*)d_ref16; tile->plp_off = d_cnt; tile->rd = P.rd; tile->epos = P.epos;
     return BCFGPU_OK;
@@ -906,14 +869,14 @@ extern "C" int bcfgpu_pileup_packed(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, con
 
 // ---- the pool as an object of its own: upload once, run the stages on it, build the tile ----
 // [lowest start, highest end) of the pool's reads (one small kernel and a wait, once per pool)
-int bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, int *lo, int *hi)
+int bcfgpu::bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, int *lo, int *hi)
 {
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return BCFGPU_E_ARG;
-    DevPool &D = *static_cast<DevPool*>(bcfgpu_internal_pool_state(ctx));
+    DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return BCFGPU_E_ARG;
     if (!D.ext_valid) {
-        int *d = (int*)bcfgpu_internal_ws(ctx, 122, 64);
+        int *d = (int*)bcfgpu_internal_ws(ctx, WS_POOL_EXTENT, 64);
         if (!d) return BCFGPU_E_NOMEM;
         int v[2] = {INT32_MAX, 0};
         if (hipMemcpyAsync(d, v, 8, hipMemcpyHostToDevice, stream) != hipSuccess) return BCFGPU_E_HIP;
@@ -941,10 +904,10 @@ extern "C" int bcfgpu_pool_keep(bcfgpu_ctx *ctx, const uint8_t *keep)
 {
     hipStream_t stream = nullptr;
     if (!ctx || bcfgpu_internal_device(ctx, &stream, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_keep: bad context");
-    DevPool &D = *static_cast<DevPool*>(bcfgpu_internal_pool_state(ctx));
+    DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_keep: no read pool on this context (bcfgpu_pool_upload)");
     if (!keep) { D.keep = nullptr; return BCFGPU_OK; }
-    uint8_t *d = (uint8_t*)bcfgpu_internal_ws(ctx, 114, (size_t)D.n_reads + 64);
+    uint8_t *d = (uint8_t*)bcfgpu_internal_ws(ctx, WS_POOL_KEEP, (size_t)D.n_reads + 64);
     if (!d) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_keep: device workspace");
     if (D.n_reads && hipMemcpyAsync(d, keep, (size_t)D.n_reads, hipMemcpyHostToDevice, stream) != hipSuccess)
         return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_keep: upload");
@@ -963,7 +926,7 @@ extern "C" int bcfgpu_pool_download(bcfgpu_ctx *ctx, uint8_t *qual, uint8_t *zq,
 {
     hipStream_t stream = nullptr;
     if (!ctx || bcfgpu_internal_device(ctx, &stream, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_download: bad context");
-    const DevPool &D = *static_cast<const DevPool*>(bcfgpu_internal_pool_state(ctx));
+    const DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_download: no read pool on this context (bcfgpu_pool_upload)");
     if (qual && D.n_bases && hipMemcpyAsync(qual, D.qual, D.n_bases, hipMemcpyDeviceToHost, stream) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_download");
     if (zq && D.n_bases) {
@@ -983,7 +946,7 @@ extern "C" int bcfgpu_pileup_entries(bcfgpu_ctx *ctx, int32_t n_cols, const int3
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_entries: bad context");
     EntriesParams E{};
-    std::memcpy(&E.P, bcfgpu_internal_pileup_state(ctx), sizeof E.P);
+    E.P = *bcfgpu_internal_pileup_state(ctx);
     if (!E.P.cnt) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_entries: no bcfgpu_pileup on this context yet");
     if (n_cols == 0) return BCFGPU_OK;
     const int S = E.P.n_smpl;
@@ -991,8 +954,8 @@ extern "C" int bcfgpu_pileup_entries(bcfgpu_ctx *ctx, int32_t n_cols, const int3
         if (cols[i] < 0 || cols[i] >= E.P.n_sites) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_entries: column out of range");
     const size_t nsel = (size_t)n_cols * S;
     #define PE_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
-    int32_t *d_cols = (int32_t*)bcfgpu_internal_ws(ctx, 21, (size_t)n_cols * 4 + 16);
-    uint32_t *d_sel = (uint32_t*)bcfgpu_internal_ws(ctx, 22, (nsel + 1) * 4 + 16);
+    int32_t *d_cols = (int32_t*)bcfgpu_internal_ws(ctx, WS_ENT_COLS, (size_t)n_cols * 4 + 16);
+    uint32_t *d_sel = (uint32_t*)bcfgpu_internal_ws(ctx, WS_ENT_SEL, (nsel + 1) * 4 + 16);
     if (!d_cols || !d_sel) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pileup_entries: device workspace");
     PE_CHK(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, stream));
     PE_CHK(hipMemsetAsync(d_sel, 0, (nsel + 1) * 4, stream));
@@ -1001,7 +964,7 @@ extern "C" int bcfgpu_pileup_entries(bcfgpu_ctx *ctx, int32_t n_cols, const int3
     hipLaunchKernelGGL(entries_kernel<false>, dim3(grid), dim3(256), 0, stream, E);
     size_t tmp_bytes = 0;
     PE_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_sel, d_sel, (int)(nsel + 1), stream));
-    void *d_tmp = bcfgpu_internal_ws(ctx, 23, tmp_bytes + 16);
+    void *d_tmp = bcfgpu_internal_ws(ctx, WS_ENT_SCAN_TMP, tmp_bytes + 16);
     if (!d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pileup_entries: device workspace");
     PE_CHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_sel, d_sel, (int)(nsel + 1), stream));
     std::vector<uint32_t> off(nsel + 1);
@@ -1012,7 +975,7 @@ extern "C" int bcfgpu_pileup_entries(bcfgpu_ctx *ctx, int32_t n_cols, const int3
     if ((int64_t)total > cap || (total && (!p_read || !p_qpos || !p_indel)))
         return bcfgpu_set_error(BCFGPU_E_RANGE, "bcfgpu_pileup_entries: the output arrays are too small (sum of col_n over the columns)");
     if (total) {
-        int32_t *d_e = (int32_t*)bcfgpu_internal_ws(ctx, 24, (size_t)total * 12 + 16);
+        int32_t *d_e = (int32_t*)bcfgpu_internal_ws(ctx, WS_ENT_OUT, (size_t)total * 12 + 16);
         if (!d_e) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pileup_entries: device workspace");
         E.e_read = d_e; E.e_qpos = d_e + total; E.e_indel = d_e + 2 * (size_t)total;
         hipLaunchKernelGGL(entries_kernel<true>, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, E);
@@ -1034,7 +997,7 @@ extern "C" int bcfgpu_pileup_indel_tile(bcfgpu_ctx *ctx, int32_t n_cols, const i
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_indel_tile: bad context");
     EntriesParams E{};
-    std::memcpy(&E.P, bcfgpu_internal_pileup_state(ctx), sizeof E.P);
+    E.P = *bcfgpu_internal_pileup_state(ctx);
     if (!E.P.cnt) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_indel_tile: no bcfgpu_pileup on this context yet");
     std::memset(tile, 0, sizeof *tile);
     const int S = E.P.n_smpl;
@@ -1042,8 +1005,8 @@ extern "C" int bcfgpu_pileup_indel_tile(bcfgpu_ctx *ctx, int32_t n_cols, const i
         if (cols[i] < 0 || cols[i] >= E.P.n_sites) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_indel_tile: column out of range");
     const size_t nsel = (size_t)n_cols * S;
     #define PT_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
-    int32_t *d_cols = (int32_t*)bcfgpu_internal_ws(ctx, 21, (size_t)n_cols * 4 + 16);
-    uint32_t *d_sel = (uint32_t*)bcfgpu_internal_ws(ctx, 25, (nsel + 1) * 4 + (size_t)n_cols + 64);
+    int32_t *d_cols = (int32_t*)bcfgpu_internal_ws(ctx, WS_ITILE_COLS, (size_t)n_cols * 4 + 16);
+    uint32_t *d_sel = (uint32_t*)bcfgpu_internal_ws(ctx, WS_ITILE_SEL, (nsel + 1) * 4 + (size_t)n_cols + 64);
     if (!d_cols || !d_sel) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pileup_indel_tile: device workspace");
     PT_CHK(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, stream));
     PT_CHK(hipMemsetAsync(d_sel, 0, (nsel + 1) * 4 + (size_t)n_cols + 64, stream));
@@ -1054,7 +1017,7 @@ extern "C" int bcfgpu_pileup_indel_tile(bcfgpu_ctx *ctx, int32_t n_cols, const i
         hipLaunchKernelGGL(subtile_kernel<false>, dim3(grid), dim3(256), 0, stream, E, (uint32_t*)nullptr, (uint8_t*)nullptr);
         size_t tmp_bytes = 0;
         PT_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_sel, d_sel, (int)(nsel + 1), stream));
-        void *d_tmp = bcfgpu_internal_ws(ctx, 23, tmp_bytes + 16);
+        void *d_tmp = bcfgpu_internal_ws(ctx, WS_ITILE_SCAN_TMP, tmp_bytes + 16);
         if (!d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pileup_indel_tile: device workspace");
         PT_CHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_sel, d_sel, (int)(nsel + 1), stream));
         PT_CHK(hipMemcpyAsync(&total, d_sel + nsel, 4, hipMemcpyDeviceToHost, stream));
@@ -1062,7 +1025,7 @@ extern "C" int bcfgpu_pileup_indel_tile(bcfgpu_ctx *ctx, int32_t n_cols, const i
     }
     if ((int64_t)total != n_aux) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_indel_tile: aux must hold one word per entry of the columns");
     const size_t ep_at = (((size_t)total + 4) * 4 + 255) & ~(size_t)255, aux_at = (ep_at + total + 64 + 255) & ~(size_t)255;
-    uint8_t *d_out = (uint8_t*)bcfgpu_internal_ws(ctx, 26, aux_at + ((size_t)total + 4) * 4);
+    uint8_t *d_out = (uint8_t*)bcfgpu_internal_ws(ctx, WS_ITILE_RECS, aux_at + ((size_t)total + 4) * 4);
     if (!d_out) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pileup_indel_tile: device workspace");
     if (total) {
         hipLaunchKernelGGL(subtile_kernel<true>, dim3(grid), dim3(256), 0, stream, E, (uint32_t*)d_out, d_out + ep_at);
@@ -1097,9 +1060,6 @@ __global__ __launch_bounds__(256) void gap_col_pos_kernel(const int32_t *cols, i
 }
 }  // namespace bcfgpu
 
-int bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint32_t *d_aux, const bcfgpu_indel_out *out, int inscns_cap);
-extern "C" bcfgpu_gap_stats *bcfgpu_internal_gap_stats(bcfgpu_ctx *ctx);
-
 extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32_t *cols, const bcfgpu_reads *reads,
                                     const bcfgpu_indel_in *par, const bcfgpu_indel_out *out, int inscns_cap, bcfgpu_tile *tile)
 {
@@ -1108,7 +1068,7 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_gap_prep_tile: bad context");
     EntriesParams E{};
-    std::memcpy(&E.P, bcfgpu_internal_pileup_state(ctx), sizeof E.P);
+    E.P = *bcfgpu_internal_pileup_state(ctx);
     const PileupParams &P = E.P;
     if (!P.cnt) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_gap_prep_tile: no bcfgpu_pileup on this context yet");
     std::memset(tile, 0, sizeof *tile);
@@ -1130,13 +1090,13 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     if (out->max_support) std::memset(out->max_support, 0, (size_t)n_cols * 4);
     if (out->max_frac) std::memset(out->max_frac, 0, (size_t)n_cols * 4);
     #define GT_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
-    #define GWS(slot, bytes) bcfgpu_internal_ws(ctx, 40 + (slot), (bytes) + 64)      /* the slots bcfgpu_gap_prep uses for its uploads */
+    #define GWS(slot, bytes) bcfgpu_internal_ws(ctx, slot, (bytes) + 64)      /* (padded as bcfgpu_gap_prep pads them) */
     // ---- the columns the stage goes on with: those that pass the pooled support filter (bam2bcf_indel.c:150-154; every column with
     // per_sample_flt), compacted on the device.  Nothing below touches a column that fails: no entry of it is listed, no workgroup
     // of the stage is started for it. ----
-    int32_t *d_cols = (int32_t*)bcfgpu_internal_ws(ctx, 21, (size_t)n_cols * 12 + 64);     // cols, then the kept columns, then their places in cols
-    int32_t *d_nk = (int32_t*)bcfgpu_internal_ws(ctx, 143, 64);
-    int32_t *h_k = (int32_t*)bcfgpu_internal_pinned(ctx, 2, (size_t)n_cols * 4 + 64);    // [0] the count, [16..] the places
+    int32_t *d_cols = (int32_t*)bcfgpu_internal_ws(ctx, WS_GTILE_COLS, (size_t)n_cols * 12 + 64);     // cols, then the kept columns, then their places in cols
+    int32_t *d_nk = (int32_t*)bcfgpu_internal_ws(ctx, WS_GTILE_N_KEPT, 64);
+    int32_t *h_k = (int32_t*)bcfgpu_internal_pinned(ctx, PIN_GTILE_KEPT, (size_t)n_cols * 4 + 64);    // [0] the count, [16..] the places
     if (!d_cols || !d_nk || !h_k) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     int32_t *d_kcols = d_cols + n_cols, *d_kidx = d_cols + 2 * (size_t)n_cols;
     GT_CHK(hipMemcpyAsync(d_cols, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, stream));
@@ -1145,8 +1105,8 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     GT_CHK(hipMemcpyAsync(h_k, d_nk, 4, hipMemcpyDeviceToHost, stream));
     GT_CHK(hipMemcpyAsync(h_k + 16, d_kidx, (size_t)n_cols * 4, hipMemcpyDeviceToHost, stream));
     // meanwhile: the reads as bcfgpu_gap_prep's kernels index them
-    int32_t *d_rpos = (int32_t*)GWS(0, (size_t)nr * 4), *d_rlq = (int32_t*)GWS(1, (size_t)nr * 4), *d_rflag = (int32_t*)GWS(2, (size_t)nr * 4);
-    int32_t *d_rncig = (int32_t*)GWS(3, (size_t)nr * 4), *d_rcoff = (int32_t*)GWS(4, (size_t)nr * 4), *d_rsoff = (int32_t*)GWS(5, (size_t)nr * 4);
+    int32_t *d_rpos = (int32_t*)GWS(WS_GAP_R_POS, (size_t)nr * 4), *d_rlq = (int32_t*)GWS(WS_GAP_R_LQ, (size_t)nr * 4), *d_rflag = (int32_t*)GWS(WS_GAP_R_FLAG, (size_t)nr * 4);
+    int32_t *d_rncig = (int32_t*)GWS(WS_GAP_R_NCIG, (size_t)nr * 4), *d_rcoff = (int32_t*)GWS(WS_GAP_R_CIG_OFF, (size_t)nr * 4), *d_rsoff = (int32_t*)GWS(WS_GAP_R_SEQ_OFF, (size_t)nr * 4);
     if (!d_rpos || !d_rlq || !d_rflag || !d_rncig || !d_rcoff || !d_rsoff) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     if (nr) hipLaunchKernelGGL(gap_unpack_reads_kernel, dim3((nr + 255) / 256), dim3(256), 0, stream, P, d_rpos, d_rlq, d_rflag, d_rncig, d_rcoff, d_rsoff);
     GT_CHK(hipStreamSynchronize(stream));                       // how many columns go on
@@ -1156,7 +1116,7 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     if (nk == 0) { gs.total_ms = ms_since(t_begin); return BCFGPU_OK; }
     const size_t nsel = (size_t)nk * S;
     // ---- their pileup entries (read, query offset, indel after the position), on the device ----
-    uint32_t *d_sel = (uint32_t*)bcfgpu_internal_ws(ctx, 25, (nsel + 1) * 4 + 64);
+    uint32_t *d_sel = (uint32_t*)bcfgpu_internal_ws(ctx, WS_GTILE_SEL, (nsel + 1) * 4 + 64);
     if (!d_sel) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     GT_CHK(hipMemsetAsync(d_sel, 0, (nsel + 1) * 4, stream));
     E.n_cols = nk; E.cols = d_kcols; E.sel_cnt = d_sel; E.col_keep = nullptr;
@@ -1164,7 +1124,7 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     hipLaunchKernelGGL(entries_kernel<false>, dim3(grid), dim3(256), 0, stream, E);
     size_t tmp_bytes = 0;
     GT_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_sel, d_sel, (int)(nsel + 1), stream));
-    void *d_tmp = bcfgpu_internal_ws(ctx, 23, tmp_bytes + 16);
+    void *d_tmp = bcfgpu_internal_ws(ctx, WS_GTILE_SCAN_TMP, tmp_bytes + 16);
     if (!d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     GT_CHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_sel, d_sel, (int)(nsel + 1), stream));
     uint32_t total = 0;
@@ -1172,7 +1132,7 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     // meanwhile: the columns' positions, the reference slice, ZQ
     int cmin = INT32_MAX, cmax = 0;
     for (int j = 0; j < nk; ++j) { cmin = std::min(cmin, cols[kidx[j]]); cmax = std::max(cmax, cols[kidx[j]]); }
-    int32_t *d_pos = (int32_t*)GWS(11, (size_t)nk * 4);
+    int32_t *d_pos = (int32_t*)GWS(WS_GAP_POS, (size_t)nk * 4);
     const int pmin = P.beg + cmin, pmax = P.beg + cmax;
     // The slice of the contig the batch touches.  The contig ends where bcfgpu_pileup was told it ends (ref_len): a candidate
     // column at or past that end reads nothing of par->ref (bcfgpu_indel_in carries no length of its own).
@@ -1180,11 +1140,11 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     const long ref_lo = std::min<long>(pmin > 65536 ? pmin - 65536 : 0, ref_end);
     const long ref_from = std::min<long>((long)pmax + 1, ref_end);
     const long ref_hi = ref_from + (long)strnlen(par->ref + ref_from, (size_t)std::min<long>(65536 + 4096, ref_end - ref_from));
-    char *d_ref = (char*)GWS(24, (size_t)(ref_hi - ref_lo));
+    char *d_ref = (char*)GWS(WS_GAP_REF, (size_t)(ref_hi - ref_lo));
     const bool any_zq = reads && reads->zq && reads->r_has_zq;
-    uint8_t *d_zq = any_zq ? (uint8_t*)GWS(9, (size_t)P.n_bases) : nullptr, *d_haszq = any_zq ? (uint8_t*)GWS(10, (size_t)nr) : nullptr;
+    uint8_t *d_zq = any_zq ? (uint8_t*)GWS(WS_GAP_ZQ, (size_t)P.n_bases) : nullptr, *d_haszq = any_zq ? (uint8_t*)GWS(WS_GAP_HAS_ZQ, (size_t)nr) : nullptr;
     {   // no ZQ bytes from the host: those bcfgpu_pool_baq left in HBM, if the pool of the pileup is still the context's pool
-        const DevPool &D = *static_cast<const DevPool*>(bcfgpu_internal_pool_state(ctx));
+        const DevPool &D = *bcfgpu_internal_pool_state(ctx);
         if (!any_zq && D.valid && D.zq && D.r_has_zq && D.n_reads == nr && D.seq16 == P.seq16) { d_zq = D.zq; d_haszq = D.r_has_zq; }
     }
     if (!d_pos || !d_ref || (any_zq && (!d_zq || !d_haszq))) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
@@ -1197,8 +1157,8 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     }
     GT_CHK(hipStreamSynchronize(stream));                       // the entry count sizes everything that follows
     if ((total >> 31) != 0) return bcfgpu_set_error(BCFGPU_E_RANGE, "bcfgpu_gap_prep_tile: too many pileup entries in one call, use fewer columns");
-    int32_t *d_e = (int32_t*)bcfgpu_internal_ws(ctx, 24, (size_t)total * 12 + 16);
-    uint32_t *d_aux = (uint32_t*)GWS(27, ((size_t)total + 4) * 4);
+    int32_t *d_e = (int32_t*)bcfgpu_internal_ws(ctx, WS_GTILE_ENT, (size_t)total * 12 + 16);
+    uint32_t *d_aux = (uint32_t*)GWS(WS_GAP_AUX, ((size_t)total + 4) * 4);
     if (!d_e || !d_aux) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     E.e_read = d_e; E.e_qpos = d_e + total; E.e_indel = d_e + 2 * (size_t)total;
     if (total) hipLaunchKernelGGL(entries_kernel<true>, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, E);
@@ -1237,8 +1197,8 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     const int nl = (int)lk.size();
     if (nl == 0) { gs.total_ms = ms_since(t_begin); return BCFGPU_OK; }
     const size_t nlsel = (size_t)nl * S;
-    int32_t *d_l = (int32_t*)bcfgpu_internal_ws(ctx, 130, (size_t)nl * 8 + 64);
-    uint32_t *d_lsel = (uint32_t*)bcfgpu_internal_ws(ctx, 131, (nlsel + 1) * 4 + (size_t)nl + 64);
+    int32_t *d_l = (int32_t*)bcfgpu_internal_ws(ctx, WS_GTILE_LIVE, (size_t)nl * 8 + 64);
+    uint32_t *d_lsel = (uint32_t*)bcfgpu_internal_ws(ctx, WS_GTILE_LIVE_SEL, (nlsel + 1) * 4 + (size_t)nl + 64);
     if (!d_l || !d_lsel) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     GT_CHK(hipMemcpyAsync(d_l, lk.data(), (size_t)nl * 4, hipMemcpyHostToDevice, stream));
     GT_CHK(hipMemcpyAsync(d_l + nl, lcols.data(), (size_t)nl * 4, hipMemcpyHostToDevice, stream));
@@ -1247,14 +1207,14 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     hipLaunchKernelGGL(live_tile_kernel<true>, dim3(lgrid), dim3(256), 0, stream, P, nl, d_l + nl, d_l, d_sel, d_lsel,
                        (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr);
     GT_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_lsel, d_lsel, (int)(nlsel + 1), stream));
-    d_tmp = bcfgpu_internal_ws(ctx, 23, tmp_bytes + 16);
+    d_tmp = bcfgpu_internal_ws(ctx, WS_GTILE_SCAN_TMP, tmp_bytes + 16);
     if (!d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     GT_CHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_lsel, d_lsel, (int)(nlsel + 1), stream));
     uint32_t ltotal = 0;
     GT_CHK(hipMemcpyAsync(&ltotal, d_lsel + nlsel, 4, hipMemcpyDeviceToHost, stream));
     GT_CHK(hipStreamSynchronize(stream));                       // (lk / lcols are this call's host vectors)
     const size_t ep_at = (((size_t)ltotal + 4) * 4 + 255) & ~(size_t)255, aux_at = (ep_at + ltotal + 64 + 255) & ~(size_t)255;
-    uint8_t *d_out = (uint8_t*)bcfgpu_internal_ws(ctx, 26, aux_at + ((size_t)ltotal + 4) * 4);
+    uint8_t *d_out = (uint8_t*)bcfgpu_internal_ws(ctx, WS_GTILE_RECS, aux_at + ((size_t)ltotal + 4) * 4);
     if (!d_out) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     if (ltotal) hipLaunchKernelGGL(live_tile_kernel<false>, dim3(32, nl < 65535 ? nl : 65535), dim3(256), 0, stream, P, nl, d_l + nl, d_l, d_sel, d_lsel,
                                    (const uint32_t*)d_aux, (uint32_t*)d_out, d_out + ep_at, (uint32_t*)(d_out + aux_at));

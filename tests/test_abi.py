@@ -4,6 +4,7 @@ the product path refuses to run instead of falling back to the CPU."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -12,16 +13,35 @@ from bcftools_amd import abi, lib
 from tests.helpers import sam
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+READELF = "/opt/rocm/llvm/bin/llvm-readelf"
+
+
+def declared_functions():
+    hdr = open(os.path.join(ROOT, "include", "bcfgpu.h")).read()
+    declared = set(re.findall(r"^(?:int|void|size_t|uint64_t|const char|bcfgpu_[a-z_]+)\s+\*?(bcfgpu_[a-z0-9_]+)\s*\(", hdr, flags=re.M))
+    assert declared, "no declarations found"
+    return declared
 
 
 def test_library_exports_every_declared_symbol():
     L = lib.load()
-    hdr = open(os.path.join(ROOT, "include", "bcfgpu.h")).read()
-    declared = set(re.findall(r"^(?:int|void|size_t|uint64_t|const char|bcfgpu_[a-z_]+)\s+\*?(bcfgpu_[a-z0-9_]+)\s*\(", hdr, flags=re.M))
-    assert declared, "no declarations found"
+    declared = declared_functions()
     for name in declared:
         assert hasattr(L, name), "libbcfgpu.so does not export %s" % name
     assert declared == set(abi.PROTOTYPES), declared ^ set(abi.PROTOTYPES)
+
+
+def test_library_exports_no_undeclared_c_function():
+    """The library's unmangled bcfgpu_* functions are exactly the header's: the context's internal interface
+    (bcftools_amd/csrc/ctx.h) has C++ linkage and stays out of the C-ABI."""
+    out = subprocess.run([READELF, "--dyn-syms", "--wide", lib.SO_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set()
+    for line in out.splitlines():
+        f = line.split()      # Num: Value Size Type Bind Vis Ndx Name
+        if len(f) >= 8 and f[3] == "FUNC" and f[6] != "UND" and f[7].startswith("bcfgpu_"):
+            exported.add(f[7])
+    declared = declared_functions()
+    assert exported == declared, sorted(exported ^ declared)
 
 
 def test_struct_sizes_match():

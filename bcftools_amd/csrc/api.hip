@@ -53,6 +53,8 @@ struct bcfgpu_ctx {
     bcfgpu_gap_stats gap{};         // statistics of the last bcfgpu_gap_prep
     PileupParams pileup{};          // the parameters of the last bcfgpu_pool_pileup (pileup.hip)
     DevPool read_pool{};            // the read pool bcfgpu_pool_upload left in HBM
+    uint64_t pool_gen = 0;          // generation of read_pool (ctx.h bcfgpu_internal_pool_replaced)
+    uint64_t pileup_pool_gen = 0;   // generation of the pool `pileup` was built from
     // grow-only device workspaces of the stages (GiB-sized scratch: not reallocated per call), by slot (ctx.h)
     struct Ws { void *p = nullptr; size_t bytes = 0; };
     Ws ws[WS_COUNT];
@@ -472,7 +474,7 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
     g.deep_cap = c->deep_cap; g.deep_key_cap = c->deep_key_cap;
     {   // the plan bcfgpu_errmod_plan made for this pass of this tile, if any: it serves this one launch
         const int kind = tile->is_indel ? 1 : 0;
-        g.draw_bits = (c->draw.rd[kind] && c->draw.rd[kind] == tile->rd) ? c->draw.bits[kind] : nullptr;
+        g.draw_bits = (c->draw.rd[kind] && c->draw.rd[kind] == tile->rd && c->draw.n_reads[kind] == tile->n_reads) ? c->draw.bits[kind] : nullptr;
         c->draw.rd[kind] = nullptr;
     }
     g.wide_ctr = reinterpret_cast<uint32_t*>(c->d_err + 5); g.wide_cap = c->wide_cap;
@@ -617,6 +619,14 @@ DrawState *bcfgpu_internal_draw_state(bcfgpu_ctx *c) { return &c->draw; }
 const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *c) { return c ? &c->cfg : nullptr; }
 PileupParams *bcfgpu_internal_pileup_state(bcfgpu_ctx *c) { return c ? &c->pileup : nullptr; }
 DevPool *bcfgpu_internal_pool_state(bcfgpu_ctx *c) { return c ? &c->read_pool : nullptr; }
+void bcfgpu_internal_pool_replaced(bcfgpu_ctx *c) { c->read_pool = DevPool{}; ++c->pool_gen; }
+void bcfgpu_internal_pileup_built(bcfgpu_ctx *c, const PileupParams &P) { c->pileup = P; c->pileup_pool_gen = c->pool_gen; }
+bool bcfgpu_internal_pileup_pool_gone(const bcfgpu_ctx *c) { return !c->read_pool.valid || c->pileup_pool_gen != c->pool_gen; }
+void bcfgpu_internal_drop_plan(bcfgpu_ctx *c, WsSlot recs)
+{
+    const void *p = c->ws[recs].p;
+    for (int k = 0; k < 2; ++k) if (p && c->draw.rd[k] == p) c->draw.rd[k] = nullptr;
+}
 
 void *bcfgpu_internal_ws(bcfgpu_ctx *c, WsSlot slot, size_t bytes)
 {

@@ -7,9 +7,10 @@
 namespace bcfgpu {
 
 // ---- the context's grow-only device workspaces (bcfgpu_internal_ws) ----
-// One name per use.  Names with the same value are one buffer, and each of their users takes it as scratch for one call (the
-// work a call queues on it is ordered on the context's stream).  "Kept" marks the slots whose contents a later entry point
-// reads: no other use may share their numbers.
+// One name per use; the prefix after WS_ names the entry point that uses it.  Names with the same value are one buffer, and
+// each of their users takes it as scratch for one call (the work a call queues on it is ordered on the context's stream).
+// "Kept" marks the slots whose contents a later entry point reads: they are listed in WS_KEPT below, and no other use may
+// share their numbers (tests/test_ctx_slots.py checks both against this enum).
 enum WsSlot : int {
     // bcfgpu_baq (reads from the host): scratch for one call
     WS_BAQ_JOBS = 0, WS_BAQ_B = 1, WS_BAQ_S = 2, WS_BAQ_F = 4, WS_BAQ_W = 5,
@@ -53,13 +54,12 @@ enum WsSlot : int {
     // bcfgpu_pileup_entries: scratch for one call
     WS_ENT_COLS = 21, WS_ENT_SEL = 22, WS_ENT_SCAN_TMP = 23, WS_ENT_OUT = 24,
     // bcfgpu_pileup_indel_tile and bcfgpu_gap_prep_tile.  Kept: the indel tile each returns, read by bcfgpu_mpileup /
-    // bcfgpu_errmod_plan on it.  The two calls share 25 and 26, so each overwrites the tile of the other, although
-    // include/bcfgpu.h says that tile stays valid.
+    // bcfgpu_errmod_plan on it; each call has slots of its own, so that its tile stays valid through the other call
     WS_ITILE_SEL = 25, WS_ITILE_RECS = 26,
     WS_ITILE_COLS = 21, WS_ITILE_SCAN_TMP = 23,                                // scratch for one call
-    WS_GTILE_LIVE_SEL = 131, WS_GTILE_RECS = 26,
+    WS_GTILE_LIVE_SEL = 131, WS_GTILE_RECS = 152,
     //   scratch for one call
-    WS_GTILE_COLS = 21, WS_GTILE_N_KEPT = 143, WS_GTILE_SEL = 25, WS_GTILE_SCAN_TMP = 23, WS_GTILE_ENT = 24, WS_GTILE_LIVE = 130,
+    WS_GTILE_COLS = 21, WS_GTILE_N_KEPT = 143, WS_GTILE_SEL = 153, WS_GTILE_SCAN_TMP = 23, WS_GTILE_ENT = 24, WS_GTILE_LIVE = 130,
 
     // bcfgpu_gap_prep and bcfgpu_gap_prep_tile: scratch for one call.  The inputs as bcfgpu_gap_prep uploads them (those
     // bcfgpu_gap_prep_tile forms or uploads itself: the per-read arrays 40-45, ZQ, the positions, the reference slice, p->aux)
@@ -81,7 +81,17 @@ enum WsSlot : int {
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_PBAQ_W3 + 1           // one past the highest slot
+    WS_COUNT = WS_GTILE_SEL + 1         // one past the highest slot
+};
+
+// the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names
+constexpr WsSlot WS_KEPT[] = {
+    WS_POOL_CIG, WS_POOL_SEQ16, WS_POOL_QUAL, WS_POOL_R_POS, WS_POOL_R_LQ, WS_POOL_R_FLAG, WS_POOL_R_NCIG, WS_POOL_R_CIG_OFF,
+    WS_POOL_R_SEQ_OFF, WS_POOL_R_MAPQ, WS_POOL_KEEP,
+    WS_PBAQ_QUAL_A, WS_PBAQ_QUAL_B, WS_PBAQ_ZQ, WS_PBAQ_HAS_ZQ,
+    WS_PLP_REF16, WS_PLP_SMPL_OFF, WS_PLP_S_POS, WS_PLP_META, WS_PLP_S_READ, WS_PLP_CNT, WS_PLP_RECS,
+    WS_ITILE_SEL, WS_ITILE_RECS, WS_GTILE_LIVE_SEL, WS_GTILE_RECS,
+    WS_DRAW_BITS_SNP, WS_DRAW_BITS_INDEL,
 };
 
 // ---- the context's grow-only pinned host buffers (bcfgpu_internal_pinned): each is scratch for one call ----
@@ -110,6 +120,17 @@ bcfgpu_gap_stats *bcfgpu_internal_gap_stats(bcfgpu_ctx *c);
 DrawState *bcfgpu_internal_draw_state(bcfgpu_ctx *c);
 DevPool *bcfgpu_internal_pool_state(bcfgpu_ctx *c);             // the read pool bcfgpu_pool_upload left in HBM
 PileupParams *bcfgpu_internal_pileup_state(bcfgpu_ctx *c);      // the parameters of the last bcfgpu_pool_pileup
+// The read pool's generation: every pool bcfgpu_pool_upload / bcfgpu_pileup[_packed] puts in place of the last is a new one.
+// bcfgpu_internal_pool_replaced: the context's pool is about to be replaced (the old one's arrays are gone from here on).
+// bcfgpu_internal_pileup_built: P is the new pileup, built from the context's pool as it is now (P.cnt = nullptr: none).
+// bcfgpu_internal_pileup_pool_gone: the pool the last pileup was built from is no longer in the workspace -- the calls that
+// read the pool through PileupParams must refuse then.
+void bcfgpu_internal_pool_replaced(bcfgpu_ctx *c);
+void bcfgpu_internal_pileup_built(bcfgpu_ctx *c, const PileupParams &P);
+bool bcfgpu_internal_pileup_pool_gone(const bcfgpu_ctx *c);
+// The tile whose read records start workspace `recs` is about to be rebuilt: a draw plan made for it (DrawState::rd, matched by
+// that address) is dropped, so that the new tile in the same buffer does not take it for its own.
+void bcfgpu_internal_drop_plan(bcfgpu_ctx *c, WsSlot recs);
 int bcfgpu_set_error(int code, const char *what);               // bcfgpu_last_error() becomes `what`; returns `code`
 
 // [lowest start, highest end) of the pool's reads (pileup.hip)

@@ -190,7 +190,7 @@ extern "C" int bcfgpu_errmod_plan_visit(bcfgpu_ctx *ctx, const bcfgpu_tile *snp,
     DR_CHK(hipMemcpyAsync(ctr, d_ctr, 16, hipMemcpyDeviceToHost, stream));
     DR_CHK(hipStreamSynchronize(stream));
     const uint32_t n_ent = (uint32_t)std::min<unsigned long long>(ctr[0] & 0xffffffffull, cap);
-    for (int t = 0; t < 2; ++t) if (tiles[t]) { D.rd[t] = tiles[t]->rd; D.bits[t] = bits[t]; }
+    for (int t = 0; t < 2; ++t) if (tiles[t]) { D.rd[t] = tiles[t]->rd; D.n_reads[t] = n_reads[t]; D.bits[t] = bits[t]; }
     if (n_ent == 0) return BCFGPU_OK;
     // visit order and the draws before every cell: the list is short (a cell in it holds more than 255 reads), ranked on the host
     std::vector<DrawEnt> ent(n_ent);

@@ -83,6 +83,7 @@ struct GlfgenParams {
 struct DrawState {
     uint64_t x = 0x1234ABCD330EULL;      // hts_drand48's state: htslib's default seed in a fresh process
     const uint32_t *rd[2] = {nullptr, nullptr};   // the read records of the planned SNP / indel tile (a plan serves one launch per pass)
+    uint64_t n_reads[2] = {0, 0};                 // their read counts (a tile matches its plan by both)
     uint32_t *bits[2] = {nullptr, nullptr};       // their bitmaps
     uint32_t n_planned = 0;
 };

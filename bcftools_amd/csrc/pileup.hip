@@ -602,8 +602,8 @@ static int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads
         return fail(BCFGPU_E_ARG, "bad packed pool");
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return fail(BCFGPU_E_ARG, "bad context");
+    bcfgpu_internal_pool_replaced(ctx);
     DevPool &D = *bcfgpu_internal_pool_state(ctx);
-    D = DevPool{};
     const int n = rd->n_reads;
     // the extent of the pools (the packed form states it)
     size_t nbase = 0, ncig = 0;
@@ -698,6 +698,9 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
     const DevPool &D = *bcfgpu_internal_pool_state(ctx);
     if (!D.valid) return fail(BCFGPU_E_ARG, "no read pool on this context (bcfgpu_pool_upload)");
     if (D.n_reads && !r_smpl && !given_off) return fail(BCFGPU_E_ARG, "bad arguments");
+    // the last pileup's tile and a draw plan made for it end here, whether or not this call succeeds
+    bcfgpu_internal_pileup_built(ctx, PileupParams{});
+    bcfgpu_internal_drop_plan(ctx, WS_PLP_RECS);
     const bcfgpu_cfg *cfg = bcfgpu_internal_cfg(ctx);
     const int n = D.n_reads, n_sites = end - beg, S = cfg->n_smpl;
     const bool trace = getenv("BCFGPU_TRACE") != nullptr;          // diagnostics: host timeline on stderr
@@ -843,7 +846,7 @@ static int pool_pileup_impl(const char *who, bcfgpu_ctx *ctx, const int32_t *r_s
     }
     #undef PL_CHK
     P.ref_len = ref_len;
-    *bcfgpu_internal_pileup_state(ctx) = P;          // for bcfgpu_pileup_entries
+    bcfgpu_internal_pileup_built(ctx, P);            // for bcfgpu_pileup_entries, bcfgpu_pileup_indel_tile, bcfgpu_gap_prep_tile
     tile->n_sites = n_sites; tile->is_indel = 0; tile->n_reads = total;
     tile->ref16 = (const int8_t*)d_ref16; tile->plp_off = d_cnt; tile->rd = P.rd; tile->epos = P.epos;
     return BCFGPU_OK;
@@ -948,6 +951,8 @@ extern "C" int bcfgpu_pileup_entries(bcfgpu_ctx *ctx, int32_t n_cols, const int3
     EntriesParams E{};
     E.P = *bcfgpu_internal_pileup_state(ctx);
     if (!E.P.cnt) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_entries: no bcfgpu_pileup on this context yet");
+    if (bcfgpu_internal_pileup_pool_gone(ctx))
+        return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_entries: the read pool the last bcfgpu_pileup was built from is gone (replaced by bcfgpu_pool_upload / bcfgpu_pileup)");
     if (n_cols == 0) return BCFGPU_OK;
     const int S = E.P.n_smpl;
     for (int i = 0; i < n_cols; ++i)
@@ -999,6 +1004,9 @@ extern "C" int bcfgpu_pileup_indel_tile(bcfgpu_ctx *ctx, int32_t n_cols, const i
     EntriesParams E{};
     E.P = *bcfgpu_internal_pileup_state(ctx);
     if (!E.P.cnt) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_indel_tile: no bcfgpu_pileup on this context yet");
+    if (bcfgpu_internal_pileup_pool_gone(ctx))
+        return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pileup_indel_tile: the read pool the last bcfgpu_pileup was built from is gone (replaced by bcfgpu_pool_upload / bcfgpu_pileup)");
+    bcfgpu_internal_drop_plan(ctx, WS_ITILE_RECS);        // the tile this call returned last ends here
     std::memset(tile, 0, sizeof *tile);
     const int S = E.P.n_smpl;
     for (int i = 0; i < n_cols; ++i)
@@ -1071,6 +1079,9 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     E.P = *bcfgpu_internal_pileup_state(ctx);
     const PileupParams &P = E.P;
     if (!P.cnt) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_gap_prep_tile: no bcfgpu_pileup on this context yet");
+    if (bcfgpu_internal_pileup_pool_gone(ctx))
+        return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_gap_prep_tile: the read pool the last bcfgpu_pileup was built from is gone (replaced by bcfgpu_pool_upload / bcfgpu_pileup)");
+    bcfgpu_internal_drop_plan(ctx, WS_GTILE_RECS);        // the tile this call returned last ends here
     std::memset(tile, 0, sizeof *tile);
     tile->is_indel = 1;
     bcfgpu_gap_stats &gs = *bcfgpu_internal_gap_stats(ctx);

@@ -173,7 +173,7 @@ typedef struct {
  *      pl [site][BCFGPU_MAX_PL][n_smpl]      u8   PL (<=255, bam2bcf.c:645-647); first n_alleles*(n_alleles+1)/2 planes valid
  *      dp4[site][4][n_smpl]                  u16  DP4 (anno[0..3], bam2bcf.c:650-659)
  *      adf/adr[site][5][n_smpl]              u16  ADF/ADR in *allele order* (bam2bcf.c:668-697); first n_alleles planes valid
- *      qs [site][5][n_smpl]                  i32  FMT/QS in allele order (bam2bcf.c:698-712)
+ *      qs [site][5][n_smpl]                  i32  FMT/QS in allele order (bam2bcf.c:698-712); first n_alleles planes valid
  *      scr[site][n_smpl]                     u16  SCR[1+i]
  *      sp [site][n_smpl]                     u8   FMT/SP: Phred-scaled two-sided Fisher exact test of DP4 (bam2bcf.c:867-885)
  * The count planes are 16 bits wide so that a cell deeper than 255 reads keeps its counts over all of its reads, as
@@ -276,7 +276,10 @@ int  bcfgpu_truncated_cells(bcfgpu_ctx *ctx, uint32_t *n_cells);
  * bcfgpu_errmod_plan ranks the over-deep cells of a tile's two passes in that order, jumps the generator to each cell's place
  * and marks the 255 reads it keeps; the NEXT bcfgpu_mpileup / bcfgpu_pipeline of each of the two tiles uses the marks (its
  * likelihoods are then errmod_cal's, and bcfgpu_truncated_cells does not count those cells), and the context's generator
- * moves on by the numbers drawn, as the process-wide one does.
+ * moves on by the numbers drawn, as the process-wide one does.  A pass's plan is dropped by the next bcfgpu_mpileup /
+ * bcfgpu_pipeline of that pass on any tile, and when the call that built its tile builds another (bcfgpu_pileup[_packed] /
+ * bcfgpu_pool_pileup for the SNP tile, bcfgpu_pileup_indel_tile / bcfgpu_gap_prep_tile for the indel tile each returned):
+ * the new tile is then run without it.
  *   snp     the SNP pass's tile (or NULL);  indel  the indel pass's tile as bcfgpu_gap_prep_tile left it (or NULL)
  *   indel_cols  HOST [indel->n_sites]: the SNP-tile column of every site of the indel tile (bcfgpu_gap_prep_tile: the entries of
  *               its `cols` with ret == 0, in order)
@@ -492,7 +495,9 @@ void bcfgpu_depth_cap_free(bcfgpu_depth_state *st);
 /* The pileup entries of selected columns of the last bcfgpu_pileup on this context, in the form bcfgpu_gap_prep takes them
  * (bcfgpu_indel_in: what bcf_call_gap_prep reads of bam_pileup1_t): for column cols[i] and sample s the entries
  * smpl_off[i*n_smpl+s] .. smpl_off[i*n_smpl+s+1]-1 of p_read (index into the read pool), p_qpos, p_indel.
- * HOST pointers; smpl_off has n_cols*n_smpl+1 elements, the p_* arrays `cap` elements (>= the sum of col_n over cols). */
+ * HOST pointers; smpl_off has n_cols*n_smpl+1 elements, the p_* arrays `cap` elements (>= the sum of col_n over cols).
+ * This call, bcfgpu_pileup_indel_tile and bcfgpu_gap_prep_tile read the read pool the pileup was built from: once a
+ * bcfgpu_pool_upload has replaced that pool they return BCFGPU_E_ARG (the pileup's tile itself stays valid). */
 int  bcfgpu_pileup_entries(bcfgpu_ctx *ctx, int32_t n_cols, const int32_t *cols, int32_t *smpl_off,
                            int32_t *p_read, int32_t *p_qpos, int32_t *p_indel, int64_t cap);
 
@@ -500,7 +505,7 @@ int  bcfgpu_pileup_entries(bcfgpu_ctx *ctx, int32_t n_cols, const int32_t *cols,
  * selected columns of the last bcfgpu_pileup on this context -- the columns where bcfgpu_gap_prep returned 0.
  * aux: HOST, one word per entry of those columns in bcfgpu_pileup_entries' order (bcfgpu_indel_out.p_aux of the same
  * columns); n_aux must equal their entry count.  tile: out, DEVICE pointers into the context's workspace (is_indel = 1),
- * valid until the next call of this function or of bcfgpu_pileup on this context. */
+ * valid until the next call of this function or of bcfgpu_pileup / bcfgpu_pileup_packed / bcfgpu_pool_pileup on this context. */
 int  bcfgpu_pileup_indel_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32_t *cols, const uint32_t *aux, int64_t n_aux,
                               bcfgpu_tile *tile);
 
@@ -519,7 +524,8 @@ int  bcfgpu_pileup_indel_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32_t *co
  *   tile   out: DEVICE pointers, the indel pass's tile (is_indel = 1, aux set), ready for bcfgpu_mpileup: the columns with
  *          ret[i] == 0 and only those, in the order of `cols` -- site j of the tile is the j-th such column (mpileup.c:354-360
  *          runs the indel pass where bcf_call_gap_prep returned >= 0).  n_sites = 0 when there is none.
- *          Valid until the next bcfgpu_gap_prep_tile / bcfgpu_gap_prep / bcfgpu_pileup* call on this context.
+ *          Valid until the next bcfgpu_gap_prep_tile / bcfgpu_gap_prep / bcfgpu_pileup / bcfgpu_pileup_packed /
+ *          bcfgpu_pool_pileup call on this context.
  * Without per_sample_flt the pooled support filter of bam2bcf_indel.c:150-154 is decided on the device from two counts the
  * pileup left per column, and nothing else -- no entry, no workgroup of the stage -- touches a column that fails it. */
 int  bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32_t *cols, const bcfgpu_reads *reads,

@@ -940,10 +940,11 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
             int pl[NG]; double pdg[NG];
             load_pl<NG>(P, is, s, ngts, pl);
             const double psum = set_pdg_one<NG>(s_pl2p, pl, pdg, ngts, nals, unseen, s_fill + tid);
-            // the subset likelihoods only feed log-sums (QUAL, 1e-4 contract): one reciprocal instead of n_gt divisions
-            const double rsum = psum != 0.0 ? 1.0 / psum : 0.0;
+            // normalised first, as set_pdg does (mcall.c:541): with PLs past ~3000 a term can be subnormal, and the reference's
+            // `if (val)` (mcall.c:644, 689) must see the same value -- a product of raw terms scaled afterwards can reach 0 on
+            // one side only, and then a row is -inf here and finite there
             #pragma unroll
-            for (int k = 0; k < NG; ++k) s_pdg[k * WGS + tid] = pdg[k];
+            for (int k = 0; k < NG; ++k) s_pdg[k * WGS + tid] = psum != 0.0 ? pdg[k] / psum : 0.0;
             const int ploidy = P.ploidy ? P.ploidy[s] : 2;
             for (int t = 0; t < nsub; ++t) {
                 const Subset &u = sh.sub[t];
@@ -966,9 +967,10 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
                     }
                 }
                 if (val != 0.0) {
-                    const double m = s_man[t * WGS + tid] * (val * rsum);
+                    // (val split before it is multiplied in: a subnormal factor would lose bits or round the product to 0)
+                    const double m = s_man[t * WGS + tid] * frexp_mant(val);
                     s_man[t * WGS + tid] = frexp_mant(m);
-                    s_exp[t * WGS + tid] += frexp_exp(m);
+                    s_exp[t * WGS + tid] += frexp_exp(val) + frexp_exp(m);
                     setbits |= 1 << t;
                 }
             }

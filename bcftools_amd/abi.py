@@ -197,6 +197,8 @@ PROTOTYPES = {
     "bcfgpu_pileup_packed": (C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Packed), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p,
                                        C.c_int32, C.POINTER(Tile), C.c_void_p, C.c_void_p]),
     "bcfgpu_pool_upload": (C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Packed), C.c_void_p]),
+    "bcfgpu_pool_stage": (C.c_int, [C.c_void_p, C.POINTER(Reads), C.POINTER(Packed), C.c_void_p]),
+    "bcfgpu_pool_adopt": (C.c_int, [C.c_void_p]),
     "bcfgpu_pool_baq": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_int, C.c_void_p]),
     "bcfgpu_pool_cap_mapq": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
     "bcfgpu_pool_keep": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -55,6 +55,7 @@ struct bcfgpu_ctx {
     DevPool read_pool{};            // the read pool bcfgpu_pool_upload left in HBM
     uint64_t pool_gen = 0;          // generation of read_pool (ctx.h bcfgpu_internal_pool_replaced)
     uint64_t pileup_pool_gen = 0;   // generation of the pool `pileup` was built from
+    PoolStage stage;                // the pool bcfgpu_pool_stage brings up beside read_pool, and which set of slots each is in
     // grow-only device workspaces of the stages (GiB-sized scratch: not reallocated per call), by slot (ctx.h)
     struct Ws { void *p = nullptr; size_t bytes = 0; };
     Ws ws[WS_COUNT];
@@ -185,6 +186,7 @@ void bcfgpu_destroy(bcfgpu_ctx *c)
     if (!c) return;
     hipSetDevice(c->cfg.device);
     if (c->own_stream) hipStreamSynchronize(c->own_stream);
+    if (c->stage.copy) hipStreamSynchronize(c->stage.copy);      // a staged pool nobody adopted: its copies write to the workspace
     for (void *p : c->owned) hipFree(p);
     if (c->d_grp_q) hipFree(c->d_grp_q);
     for (auto &w : c->ws) if (w.p) hipFree(w.p);
@@ -193,6 +195,9 @@ void bcfgpu_destroy(bcfgpu_ctx *c)
     for (int i = 0; i < 4; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
     for (int i = 0; i < 8; ++i) if (c->side[i]) { hipStreamSynchronize(c->side[i]); hipStreamDestroy(c->side[i]); }
     for (int i = 0; i < 9; ++i) if (c->side_ev[i]) hipEventDestroy(c->side_ev[i]);
+    if (c->stage.copy) hipStreamDestroy(c->stage.copy);
+    if (c->stage.copied) hipEventDestroy(c->stage.copied);
+    if (c->stage.freed) hipEventDestroy(c->stage.freed);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -622,6 +627,19 @@ DevPool *bcfgpu_internal_pool_state(bcfgpu_ctx *c) { return c ? &c->read_pool : 
 void bcfgpu_internal_pool_replaced(bcfgpu_ctx *c) { c->read_pool = DevPool{}; ++c->pool_gen; }
 void bcfgpu_internal_pileup_built(bcfgpu_ctx *c, const PileupParams &P) { c->pileup = P; c->pileup_pool_gen = c->pool_gen; }
 bool bcfgpu_internal_pileup_pool_gone(const bcfgpu_ctx *c) { return !c->read_pool.valid || c->pileup_pool_gen != c->pool_gen; }
+PoolStage *bcfgpu_internal_pool_stage(bcfgpu_ctx *c, bool with_stream)
+{
+    if (!c) return nullptr;
+    PoolStage &st = c->stage;
+    if (!with_stream) return &st;
+    if (!st.copy) {
+        hipSetDevice(c->cfg.device);
+        if (hipStreamCreateWithFlags(&st.copy, hipStreamNonBlocking) != hipSuccess) { st.copy = nullptr; return nullptr; }
+        if (hipEventCreateWithFlags(&st.copied, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&st.freed, hipEventDisableTiming) != hipSuccess) return nullptr;
+    }
+    return (st.copied && st.freed) ? &st : nullptr;
+}
 void bcfgpu_internal_drop_plan(bcfgpu_ctx *c, WsSlot recs)
 {
     const void *p = c->ws[recs].p;

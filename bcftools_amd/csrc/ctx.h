@@ -31,6 +31,12 @@ enum WsSlot : int {
     WS_POOL_SEQ4 = 111, WS_POOL_QUAL4 = 112, WS_POOL_RECS = 128, WS_POOL_SCAN_TMP = 129,
     WS_POOL_KEEP = 114,                 // kept: DevPool::keep (bcfgpu_pool_keep), read by bcfgpu_pool_pileup
     WS_POOL_EXTENT = 122,               // bcfgpu_internal_pool_extent: scratch for one call
+    //   the second set of the pool's arrays.  Kept: the pool bcfgpu_pool_stage brings up lands in the set the context's pool
+    //   is not in, and bcfgpu_pool_adopt makes that set the pool's (PoolStage::set says which one DevPool points into)
+    WS_POOL_B_CIG = 154, WS_POOL_B_SEQ16 = 155, WS_POOL_B_QUAL = 156, WS_POOL_B_R_POS = 157, WS_POOL_B_R_LQ = 158,
+    WS_POOL_B_R_FLAG = 159, WS_POOL_B_R_NCIG = 160, WS_POOL_B_R_CIG_OFF = 161, WS_POOL_B_R_SEQ_OFF = 162, WS_POOL_B_R_MAPQ = 163,
+    //   a staged pool's packed inputs.  Kept from bcfgpu_pool_stage to bcfgpu_pool_adopt, which expands them
+    WS_POOL_STAGE_SEQ4 = 164, WS_POOL_STAGE_QUAL4 = 165, WS_POOL_STAGE_RECS = 166,
     // bcfgpu_pool_baq: scratch for one call
     WS_PBAQ_JOBS0 = 0, WS_PBAQ_JOBS1 = 3, WS_PBAQ_JOBS2 = 127, WS_PBAQ_JOBS3 = 135, WS_PBAQ_JOBS2_SORTED = 128,
     WS_PBAQ_COUNTS = 115, WS_PBAQ_RET = 116, WS_PBAQ_STATE = 11, WS_PBAQ_Q = 12, WS_PBAQ_TMP = 13,
@@ -81,13 +87,15 @@ enum WsSlot : int {
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_GTILE_SEL + 1         // one past the highest slot
+    WS_COUNT = WS_POOL_STAGE_RECS + 1    // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names
 constexpr WsSlot WS_KEPT[] = {
     WS_POOL_CIG, WS_POOL_SEQ16, WS_POOL_QUAL, WS_POOL_R_POS, WS_POOL_R_LQ, WS_POOL_R_FLAG, WS_POOL_R_NCIG, WS_POOL_R_CIG_OFF,
     WS_POOL_R_SEQ_OFF, WS_POOL_R_MAPQ, WS_POOL_KEEP,
+    WS_POOL_B_CIG, WS_POOL_B_SEQ16, WS_POOL_B_QUAL, WS_POOL_B_R_POS, WS_POOL_B_R_LQ, WS_POOL_B_R_FLAG, WS_POOL_B_R_NCIG,
+    WS_POOL_B_R_CIG_OFF, WS_POOL_B_R_SEQ_OFF, WS_POOL_B_R_MAPQ, WS_POOL_STAGE_SEQ4, WS_POOL_STAGE_QUAL4, WS_POOL_STAGE_RECS,
     WS_PBAQ_QUAL_A, WS_PBAQ_QUAL_B, WS_PBAQ_ZQ, WS_PBAQ_HAS_ZQ,
     WS_PLP_REF16, WS_PLP_SMPL_OFF, WS_PLP_S_POS, WS_PLP_META, WS_PLP_S_READ, WS_PLP_CNT, WS_PLP_RECS,
     WS_ITILE_SEL, WS_ITILE_RECS, WS_GTILE_LIVE_SEL, WS_GTILE_RECS,
@@ -118,9 +126,10 @@ int bcfgpu_internal_n_cu(const bcfgpu_ctx *c);
 const bcfgpu_cfg *bcfgpu_internal_cfg(const bcfgpu_ctx *c);
 bcfgpu_gap_stats *bcfgpu_internal_gap_stats(bcfgpu_ctx *c);
 DrawState *bcfgpu_internal_draw_state(bcfgpu_ctx *c);
-DevPool *bcfgpu_internal_pool_state(bcfgpu_ctx *c);             // the read pool bcfgpu_pool_upload left in HBM
+DevPool *bcfgpu_internal_pool_state(bcfgpu_ctx *c);             // the read pool bcfgpu_pool_upload / bcfgpu_pool_adopt left in HBM
 PileupParams *bcfgpu_internal_pileup_state(bcfgpu_ctx *c);      // the parameters of the last bcfgpu_pool_pileup
-// The read pool's generation: every pool bcfgpu_pool_upload / bcfgpu_pileup[_packed] puts in place of the last is a new one.
+// The read pool's generation: every pool bcfgpu_pool_upload / bcfgpu_pool_adopt / bcfgpu_pileup[_packed] puts in place of the
+// last is a new one.
 // bcfgpu_internal_pool_replaced: the context's pool is about to be replaced (the old one's arrays are gone from here on).
 // bcfgpu_internal_pileup_built: P is the new pileup, built from the context's pool as it is now (P.cnt = nullptr: none).
 // bcfgpu_internal_pileup_pool_gone: the pool the last pileup was built from is no longer in the workspace -- the calls that
@@ -128,6 +137,24 @@ PileupParams *bcfgpu_internal_pileup_state(bcfgpu_ctx *c);      // the parameter
 void bcfgpu_internal_pool_replaced(bcfgpu_ctx *c);
 void bcfgpu_internal_pileup_built(bcfgpu_ctx *c, const PileupParams &P);
 bool bcfgpu_internal_pileup_pool_gone(const bcfgpu_ctx *c);
+// The staged read pool (bcfgpu_pool_stage / bcfgpu_pool_adopt, pileup.hip): the pool has two sets of its kept slots, the
+// context's pool in one and the pool a stage brings up in the other; adopting is a change of roles.
+struct PoolStage {
+    int set = 0;                        // the set DevPool points into: 0 = WS_POOL_*, 1 = WS_POOL_B_*
+    int pending = 0;                    // a staged pool waits for bcfgpu_pool_adopt
+    int freed_valid = 0;                // `freed` has been recorded
+    hipStream_t copy = nullptr;         // the copy stream
+    hipEvent_t copied = nullptr;        // on `copy`, behind the staged pool's host-to-device copies
+    hipEvent_t freed = nullptr;         // on the context's stream at the last adopt, behind every reader of the set (and of the
+                                        // staging slots) the next stage writes to
+    DevPool D{};                        // the staged pool: its arrays in the other set (the packed forms': still to be formed)
+    const bcfgpu_read12 *d_rec = nullptr;                   // its packed inputs in HBM (NULL: not that form) and how to read them
+    const uint8_t *d_seq4 = nullptr, *d_qual4 = nullptr;
+    unsigned long long pal[2] = {0, 0};
+    int qual_bits = 0;
+};
+// the context's PoolStage; with_stream: its stream and events are created on first use, nullptr when that fails
+PoolStage *bcfgpu_internal_pool_stage(bcfgpu_ctx *c, bool with_stream);
 // The tile whose read records start workspace `recs` is about to be rebuilt: a draw plan made for it (DrawState::rd, matched by
 // that address) is dropped, so that the new tile in the same buffer does not take it for its own.
 void bcfgpu_internal_drop_plan(bcfgpu_ctx *c, WsSlot recs);

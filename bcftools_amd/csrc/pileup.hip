@@ -590,20 +590,43 @@ template <class F> static void on_threads(int nthr, F &&fn)
     for (auto &th : thr) th.join();
 }
 
-static int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bcfgpu_packed *pk, const uint8_t *r_mapq)
+// The pool's kept slots come in two sets (ctx.h): the context's pool lies in one, the pool bcfgpu_pool_stage brings up in the other.
+struct PoolSlots { WsSlot cig, seq16, qual, r_pos, r_lq, r_flag, r_ncig, r_cig_off, r_seq_off, r_mapq; };
+static const PoolSlots POOL_SET[2] = {
+    {WS_POOL_CIG, WS_POOL_SEQ16, WS_POOL_QUAL, WS_POOL_R_POS, WS_POOL_R_LQ, WS_POOL_R_FLAG, WS_POOL_R_NCIG, WS_POOL_R_CIG_OFF, WS_POOL_R_SEQ_OFF, WS_POOL_R_MAPQ},
+    {WS_POOL_B_CIG, WS_POOL_B_SEQ16, WS_POOL_B_QUAL, WS_POOL_B_R_POS, WS_POOL_B_R_LQ, WS_POOL_B_R_FLAG, WS_POOL_B_R_NCIG, WS_POOL_B_R_CIG_OFF, WS_POOL_B_R_SEQ_OFF, WS_POOL_B_R_MAPQ},
+};
+// where the packed inputs go: scratch of one call (bcfgpu_pool_upload), or kept from the stage to the adopt
+struct PackedSlots { WsSlot seq4, qual4, recs; };
+static const PackedSlots PACKED_SCRATCH = {WS_POOL_SEQ4, WS_POOL_QUAL4, WS_POOL_RECS}, PACKED_STAGED = {WS_POOL_STAGE_SEQ4, WS_POOL_STAGE_QUAL4, WS_POOL_STAGE_RECS};
+
+static int pool_fail(const char *who, int code, const char *what)
 {
-    auto fail = [&](int code, const char *what) { char msg[160]; snprintf(msg, sizeof msg, "%s: %s", who, what); return bcfgpu_set_error(code, msg); };
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return bcfgpu_set_error(code, msg);
+}
+
+static int pool_check_args(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bcfgpu_packed *pk, const uint8_t *r_mapq)
+{
     const bool recs = pk && pk->recs;
-    if (!ctx || !rd || rd->n_reads < 0 || (rd->n_reads && !recs && !r_mapq)) return fail(BCFGPU_E_ARG, "bad arguments");
+    if (!ctx || !rd || rd->n_reads < 0 || (rd->n_reads && !recs && !r_mapq)) return pool_fail(who, BCFGPU_E_ARG, "bad arguments");
     if (rd->n_reads && ((!recs && (!rd->r_pos || !rd->r_lq || !rd->r_flag || !rd->r_ncig || !rd->r_cig_off || !rd->r_seq_off)) ||
                         (!pk && !rd->seq16) || (!(pk && pk->qual4) && !rd->qual)))
-        return fail(BCFGPU_E_ARG, "a read array is missing");
+        return pool_fail(who, BCFGPU_E_ARG, "a read array is missing");
     if (pk && (!pk->seq4 || pk->n_bases < 0 || pk->n_cig < 0 || (pk->n_bases >> 32) || (pk->qual_bits != 0 && pk->qual_bits != 2 && pk->qual_bits != 4)))
-        return fail(BCFGPU_E_ARG, "bad packed pool");
-    hipStream_t stream = nullptr;
-    if (bcfgpu_internal_device(ctx, &stream, nullptr)) return fail(BCFGPU_E_ARG, "bad context");
-    bcfgpu_internal_pool_replaced(ctx);
-    DevPool &D = *bcfgpu_internal_pool_state(ctx);
+        return pool_fail(who, BCFGPU_E_ARG, "bad packed pool");
+    return BCFGPU_OK;
+}
+
+// The caller's arrays to HBM: every host-to-device copy of a pool, queued on `stream`, into set `ps` of the pool's slots and (the
+// packed inputs) into `pks`.  `in` becomes the pool's description: D's arrays all have their room, those of the packed forms are
+// formed by pool_form.  No kernel is launched here.
+static int pool_copy(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bcfgpu_packed *pk, const uint8_t *r_mapq,
+                     const PoolSlots &ps, const PackedSlots &pks, hipStream_t stream, PoolStage &in)
+{
+    auto fail = [&](int code, const char *what) { return pool_fail(who, code, what); };
+    DevPool D{};
     const int n = rd->n_reads;
     // the extent of the pools (the packed form states it)
     size_t nbase = 0, ncig = 0;
@@ -625,57 +648,88 @@ static int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads
         if (nbase >> 32) return fail(BCFGPU_E_RANGE, "the pool holds 2^32 or more bases");
     }
     D.n_reads = n; D.n_bases = (uint32_t)nbase; D.n_cig = (uint32_t)ncig;
+    in.d_rec = nullptr; in.d_seq4 = in.d_qual4 = nullptr; in.qual_bits = 0; in.pal[0] = in.pal[1] = 0;
     if (pk && pk->recs) {
-        // the 12-byte records: the arrays are formed here, the offsets by two prefix sums
-        const bcfgpu_read12 *d_rec = (const bcfgpu_read12*)ws_upload(ctx, WS_POOL_RECS, pk->recs, (size_t)n * sizeof(bcfgpu_read12), 64, stream);
-        int32_t *a_pos = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_POS, (size_t)n * 4 + 64), *a_lq = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_LQ, (size_t)n * 4 + 64);
-        int32_t *a_flag = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_FLAG, (size_t)n * 4 + 64), *a_ncig = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_NCIG, (size_t)n * 4 + 64);
-        int32_t *a_coff = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_CIG_OFF, (size_t)(n + 1) * 4 + 64), *a_soff = (int32_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_SEQ_OFF, (size_t)(n + 1) * 4 + 64);
-        uint8_t *a_mapq = (uint8_t*)bcfgpu_internal_ws(ctx, WS_POOL_R_MAPQ, (size_t)n + 64);
-        if (!d_rec || !a_pos || !a_lq || !a_flag || !a_ncig || !a_coff || !a_soff || !a_mapq) return fail(BCFGPU_E_NOMEM, "device workspace");
-        hipLaunchKernelGGL(pool_expand_kernel, dim3((n + 256) / 256), dim3(256), 0, stream, d_rec, n, a_pos, a_lq, a_flag, a_ncig, a_coff, a_soff, a_mapq);
+        // the 12-byte records: the arrays are formed from them, the offsets by two prefix sums (pool_form)
+        in.d_rec = (const bcfgpu_read12*)ws_upload(ctx, pks.recs, pk->recs, (size_t)n * sizeof(bcfgpu_read12), 64, stream);
+        D.r_pos = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_pos, (size_t)n * 4 + 64); D.r_lq = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_lq, (size_t)n * 4 + 64);
+        D.r_flag = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_flag, (size_t)n * 4 + 64); D.r_ncig = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_ncig, (size_t)n * 4 + 64);
+        D.r_cig_off = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_cig_off, (size_t)(n + 1) * 4 + 64); D.r_seq_off = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_seq_off, (size_t)(n + 1) * 4 + 64);
+        D.r_mapq = (uint8_t*)bcfgpu_internal_ws(ctx, ps.r_mapq, (size_t)n + 64);
+        if (!in.d_rec) return fail(BCFGPU_E_NOMEM, "device workspace");
+    } else {
+        D.r_pos = (const int32_t*)ws_upload(ctx, ps.r_pos, rd->r_pos, (size_t)n * 4, 64, stream);
+        D.r_lq = (const int32_t*)ws_upload(ctx, ps.r_lq, rd->r_lq, (size_t)n * 4, 64, stream);
+        D.r_flag = (const int32_t*)ws_upload(ctx, ps.r_flag, rd->r_flag, (size_t)n * 4, 64, stream);
+        D.r_ncig = (const int32_t*)ws_upload(ctx, ps.r_ncig, rd->r_ncig, (size_t)n * 4, 64, stream);
+        D.r_cig_off = (const int32_t*)ws_upload(ctx, ps.r_cig_off, rd->r_cig_off, (size_t)n * 4, 64, stream);
+        D.r_seq_off = (const int32_t*)ws_upload(ctx, ps.r_seq_off, rd->r_seq_off, (size_t)n * 4, 64, stream);
+        D.r_mapq = (uint8_t*)ws_upload(ctx, ps.r_mapq, r_mapq, (size_t)n, 64, stream);
+    }
+    D.cig = (const uint32_t*)ws_upload(ctx, ps.cig, rd->cig, ncig * 4, 64, stream);
+    uint8_t *d_seq16 = nullptr, *d_qual = nullptr;
+    if (pk) {
+        const size_t n_in = (nbase + 1) / 2;
+        d_seq16 = (uint8_t*)bcfgpu_internal_ws(ctx, ps.seq16, nbase + 64);
+        in.d_seq4 = (const uint8_t*)ws_upload(ctx, pks.seq4, pk->seq4, n_in, 64, stream);
+        if (pk->qual4) {
+            d_qual = (uint8_t*)bcfgpu_internal_ws(ctx, ps.qual, nbase + 64);
+            in.d_qual4 = (const uint8_t*)ws_upload(ctx, pks.qual4, pk->qual4, pk->qual_bits == 2 ? (nbase + 3) / 4 : n_in, 64, stream);
+        } else d_qual = (uint8_t*)ws_upload(ctx, ps.qual, rd->qual, nbase, 64, stream);
+        if (!in.d_seq4 || (pk->qual4 && !in.d_qual4) || !d_seq16 || !d_qual) return fail(BCFGPU_E_NOMEM, "device workspace");
+        std::memcpy(in.pal, pk->palette, 16);
+        in.qual_bits = (int)pk->qual_bits;
+    } else {
+        d_seq16 = (uint8_t*)ws_upload(ctx, ps.seq16, rd->seq16, nbase, 64, stream);
+        d_qual = (uint8_t*)ws_upload(ctx, ps.qual, rd->qual, nbase, 64, stream);
+    }
+    D.seq16 = d_seq16; D.qual = d_qual; D.qual_slot = ps.qual;
+    if (!D.r_pos || !D.r_lq || !D.r_flag || !D.r_ncig || !D.r_cig_off || !D.r_seq_off || !D.r_mapq || !D.cig || !D.seq16 || !D.qual)
+        return fail(BCFGPU_E_NOMEM, "device workspace");
+    in.D = D;
+    return BCFGPU_OK;
+}
+
+// The pool pool_copy described, formed on `stream` (behind its copies) and made the context's read pool: the packed forms are
+// expanded to the arrays the stages index; the plain form's arrays are already what the caller handed over.
+static int pool_form(const char *who, bcfgpu_ctx *ctx, const PoolStage &in, hipStream_t stream)
+{
+    auto fail = [&](int code, const char *what) { return pool_fail(who, code, what); };
+    const DevPool &S = in.D;
+    const int n = S.n_reads;
+    if (in.d_rec) {
+        int32_t *a_coff = const_cast<int32_t*>(S.r_cig_off), *a_soff = const_cast<int32_t*>(S.r_seq_off);
+        hipLaunchKernelGGL(pool_expand_kernel, dim3((n + 256) / 256), dim3(256), 0, stream, in.d_rec, n, const_cast<int32_t*>(S.r_pos), const_cast<int32_t*>(S.r_lq),
+                           const_cast<int32_t*>(S.r_flag), const_cast<int32_t*>(S.r_ncig), a_coff, a_soff, S.r_mapq);
         size_t tmp_bytes = 0;
         if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, a_soff, a_soff, n + 1, stream) != hipSuccess) return fail(BCFGPU_E_HIP, "scan");
         void *d_tmp = bcfgpu_internal_ws(ctx, WS_POOL_SCAN_TMP, tmp_bytes + 64);
         if (!d_tmp) return fail(BCFGPU_E_NOMEM, "device workspace");
         if (hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, a_soff, a_soff, n + 1, stream) != hipSuccess ||
             hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, a_coff, a_coff, n + 1, stream) != hipSuccess) return fail(BCFGPU_E_HIP, "scan");
-        D.r_pos = a_pos; D.r_lq = a_lq; D.r_flag = a_flag; D.r_ncig = a_ncig; D.r_cig_off = a_coff; D.r_seq_off = a_soff; D.r_mapq = a_mapq;
-    } else {
-    D.r_pos = (const int32_t*)ws_upload(ctx, WS_POOL_R_POS, rd->r_pos, (size_t)n * 4, 64, stream);
-    D.r_lq = (const int32_t*)ws_upload(ctx, WS_POOL_R_LQ, rd->r_lq, (size_t)n * 4, 64, stream);
-    D.r_flag = (const int32_t*)ws_upload(ctx, WS_POOL_R_FLAG, rd->r_flag, (size_t)n * 4, 64, stream);
-    D.r_ncig = (const int32_t*)ws_upload(ctx, WS_POOL_R_NCIG, rd->r_ncig, (size_t)n * 4, 64, stream);
-    D.r_cig_off = (const int32_t*)ws_upload(ctx, WS_POOL_R_CIG_OFF, rd->r_cig_off, (size_t)n * 4, 64, stream);
-    D.r_seq_off = (const int32_t*)ws_upload(ctx, WS_POOL_R_SEQ_OFF, rd->r_seq_off, (size_t)n * 4, 64, stream);
-    D.r_mapq = (uint8_t*)ws_upload(ctx, WS_POOL_R_MAPQ, r_mapq, (size_t)n, 64, stream);
     }
-    D.cig = (const uint32_t*)ws_upload(ctx, WS_POOL_CIG, rd->cig, ncig * 4, 64, stream);
-    uint8_t *d_seq16 = nullptr, *d_qual = nullptr;
-    if (pk) {
-        const size_t n_in = (nbase + 1) / 2;
-        d_seq16 = (uint8_t*)bcfgpu_internal_ws(ctx, WS_POOL_SEQ16, nbase + 64);
-        const uint8_t *d_seq4 = (const uint8_t*)ws_upload(ctx, WS_POOL_SEQ4, pk->seq4, n_in, 64, stream), *d_qual4 = nullptr;
-        if (pk->qual4) {
-            d_qual = (uint8_t*)bcfgpu_internal_ws(ctx, WS_POOL_QUAL, nbase + 64);
-            d_qual4 = (const uint8_t*)ws_upload(ctx, WS_POOL_QUAL4, pk->qual4, pk->qual_bits == 2 ? (nbase + 3) / 4 : n_in, 64, stream);
-        } else d_qual = (uint8_t*)ws_upload(ctx, WS_POOL_QUAL, rd->qual, nbase, 64, stream);
-        if (!d_seq4 || (pk->qual4 && !d_qual4) || !d_seq16 || !d_qual) return fail(BCFGPU_E_NOMEM, "device workspace");
-        unsigned long long pal[2] = {0, 0};
-        std::memcpy(pal, pk->palette, 16);
-        const size_t nthreads = (n_in + 3) / 4;
+    if (in.d_seq4) {
+        const size_t n_in = ((size_t)S.n_bases + 1) / 2, nthreads = (n_in + 3) / 4;
         if (nthreads) hipLaunchKernelGGL(pileup_unpack_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream,
-                                         d_seq4, d_qual4, pal[0], pal[1], n_in, d_seq16, d_qual, (int)pk->qual_bits);
-    } else {
-        d_seq16 = (uint8_t*)ws_upload(ctx, WS_POOL_SEQ16, rd->seq16, nbase, 64, stream);
-        d_qual = (uint8_t*)ws_upload(ctx, WS_POOL_QUAL, rd->qual, nbase, 64, stream);
+                                         in.d_seq4, in.d_qual4, in.pal[0], in.pal[1], n_in, const_cast<uint8_t*>(S.seq16), S.qual, in.qual_bits);
     }
-    D.seq16 = d_seq16; D.qual = d_qual; D.qual_slot = WS_POOL_QUAL;
-    if (!D.r_pos || !D.r_lq || !D.r_flag || !D.r_ncig || !D.r_cig_off || !D.r_seq_off || !D.r_mapq || !D.cig || !D.seq16 || !D.qual)
-        return fail(BCFGPU_E_NOMEM, "device workspace");
     if (hipGetLastError() != hipSuccess) return fail(BCFGPU_E_HIP, "launch");
+    DevPool &D = *bcfgpu_internal_pool_state(ctx);
+    D = S;
     D.valid = 1;
     return BCFGPU_OK;
+}
+
+static int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bcfgpu_packed *pk, const uint8_t *r_mapq)
+{
+    if (const int rc = pool_check_args(who, ctx, rd, pk, r_mapq)) return rc;
+    hipStream_t stream = nullptr;
+    if (bcfgpu_internal_device(ctx, &stream, nullptr)) return pool_fail(who, BCFGPU_E_ARG, "bad context");
+    bcfgpu_internal_pool_replaced(ctx);
+    // into the set the context's pool is in (a staged pool, in the other one, stays as it is), everything on the context's stream
+    PoolStage in;
+    const int rc = pool_copy(who, ctx, rd, pk, r_mapq, POOL_SET[bcfgpu_internal_pool_stage(ctx, false)->set], PACKED_SCRATCH, stream, in);
+    return rc ? rc : pool_form(who, ctx, in, stream);
 }
 
 namespace bcfgpu {
@@ -901,6 +955,49 @@ extern "C" int bcfgpu_pool_upload(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const
     bcfgpu_internal_device(ctx, &stream, nullptr);
     if (hipStreamSynchronize(stream) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_upload: upload");
     return BCFGPU_OK;
+}
+
+// The read callback running ahead of the column loop (mpileup.c:183-246): the next region's pool comes up on the copy stream while
+// the stages of the current one run on the context's.  Nothing of the current pool is touched: the copies go to the other set.
+extern "C" int bcfgpu_pool_stage(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bcfgpu_packed *pk, const uint8_t *r_mapq)
+{
+    const char *who = "bcfgpu_pool_stage";
+    if (const int rc = pool_check_args(who, ctx, rd, pk, r_mapq)) return rc;
+    if (bcfgpu_internal_device(ctx, nullptr, nullptr)) return pool_fail(who, BCFGPU_E_ARG, "bad context");
+    PoolStage *st = bcfgpu_internal_pool_stage(ctx, true);
+    if (!st) return pool_fail(who, BCFGPU_E_HIP, "copy stream");
+    // a staged pool nobody adopted is replaced: its copies write to the buffers this call reuses (and may regrow)
+    if (st->pending) {
+        st->pending = 0;
+        if (hipEventSynchronize(st->copied) != hipSuccess) return pool_fail(who, BCFGPU_E_HIP, "the staged copies");
+    }
+    // the other set held the pool before the last adopt, and that adopt's kernels read the staging slots: behind both
+    if (st->freed_valid && hipStreamWaitEvent(st->copy, st->freed, 0) != hipSuccess) return pool_fail(who, BCFGPU_E_HIP, "hipStreamWaitEvent");
+    const int rc = pool_copy(who, ctx, rd, pk, r_mapq, POOL_SET[st->set ^ 1], PACKED_STAGED, st->copy, *st);
+    if (rc) { hipStreamSynchronize(st->copy); return rc; }          // (the caller's arrays are its own again after a failure)
+    if (hipEventRecord(st->copied, st->copy) != hipSuccess) { hipStreamSynchronize(st->copy); return pool_fail(who, BCFGPU_E_HIP, "hipEventRecord"); }
+    st->pending = 1;
+    return BCFGPU_OK;
+}
+
+extern "C" int bcfgpu_pool_adopt(bcfgpu_ctx *ctx)
+{
+    const char *who = "bcfgpu_pool_adopt";
+    hipStream_t stream = nullptr;
+    if (!ctx || bcfgpu_internal_device(ctx, &stream, nullptr)) return pool_fail(who, BCFGPU_E_ARG, "bad context");
+    PoolStage *st = bcfgpu_internal_pool_stage(ctx, false);
+    if (!st->pending) return pool_fail(who, BCFGPU_E_ARG, "no staged read pool on this context (bcfgpu_pool_stage)");
+    // the caller's arrays are free again when this call returns: the copies' event, not the context's stream
+    if (hipEventSynchronize(st->copied) != hipSuccess) return pool_fail(who, BCFGPU_E_HIP, "the staged copies");
+    if (hipStreamWaitEvent(stream, st->copied, 0) != hipSuccess) return pool_fail(who, BCFGPU_E_HIP, "hipStreamWaitEvent");
+    st->pending = 0;
+    bcfgpu_internal_pool_replaced(ctx);
+    st->set ^= 1;
+    const int rc = pool_form(who, ctx, *st, stream);
+    // what is queued on the context's stream up to here is all that reads the old pool's set and the staging slots
+    st->freed_valid = hipEventRecord(st->freed, stream) == hipSuccess;
+    if (!st->freed_valid) hipStreamSynchronize(stream);
+    return rc;
 }
 
 extern "C" int bcfgpu_pool_keep(bcfgpu_ctx *ctx, const uint8_t *keep)

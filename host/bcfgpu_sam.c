@@ -6,6 +6,8 @@
  *      options: -a TAG,..  --gvcf INT,..  -O v|z|u|b  -o FILE  -d INT  -s LIST  -S FILE  -G FILE  --ignore-RG
  *               -B  -E  -A  -q INT  -Q INT  -C INT  --ff INT  --rf INT  -I -o INT -e INT -h INT -m INT -F FLOAT -p -L INT   (as `bcftools mpileup`)
  *               --tile COLUMNS  columns per device tile (default 16384);  --gpus N  region shards, a process per shard
+ *               --prefetch  the next tile's reads go to the device (bcfgpu_pool_stage, from page-locked buffers) while the device
+ *                           stages of the current tile run; the same output
  *               --list-samples: print "sample <TAB> reads entering the pileup <TAB> files" and stop (no device needed)
  *
  *  A region is streamed through in TILES: the files are read in step with the tiles -- a position-sorted file no
@@ -19,7 +21,8 @@
  *  filters of mplp_func (mpileup.c:183-246: unmapped, --rf/--ff flags, reads of dropped read groups, -q, orphans), the
  *  iterator's per-file depth cap (bcfgpu_depth_cap_push, its buffer carried from tile to tile) and the pairing of overlapping
  *  mates (htslib overlap_push).  Then per tile, each a call on the flat read pool:
- *      bcfgpu_pool_upload          the tile's reads to HBM, once
+ *      bcfgpu_pool_upload          the tile's reads to HBM, once (--prefetch: bcfgpu_pool_stage under the tile before, then
+ *                                  bcfgpu_pool_adopt -- the read callback running ahead of the column loop, mpileup.c:183-246)
  *      bcfgpu_pool_baq             BAQ (sam_prob_realn, mpileup.c:234)
  *      bcfgpu_pool_overlap_tweak   mate-overlap qualities (bam_mplp_init_overlaps, mpileup.c:640)
  *      bcfgpu_pool_pileup          the pileup columns of the tile, built in HBM
@@ -74,9 +77,19 @@ typedef struct {
     char **qname;
     uint32_t *cig; size_t ncigs, cigcap;
     uint8_t *seq16, *qual, *zq; size_t nbase, basecap;
+    int pinned;                                   /* the arrays are page-locked (bcfgpu_host_alloc): --prefetch copies from them beside kernels */
 } pool_t;
 
 static void *grow(void *p, size_t n) { p = realloc(p, n ? n : 1); if (!p) DIE("out of memory\n"); return p; }
+/* a pool's array of `used` bytes made n bytes long */
+static void *pool_grow(const pool_t *P, void *p, size_t used, size_t n)
+{
+    if (!P->pinned) return grow(p, n);
+    void *q = NULL;
+    if (bcfgpu_host_alloc(n ? n : 1, &q)) DIE("%s\n", bcfgpu_last_error());
+    if (p) { memcpy(q, p, used); bcfgpu_host_free(p); }
+    return q;
+}
 
 static int nt16_of(char c)
 {
@@ -346,8 +359,9 @@ static void pool_add(pool_t *P, int file, int smpl, const char *qname, int flag,
                      const uint32_t *cig, int ncig, int lq, const uint8_t *seq16, const uint8_t *qual)
 {
     if (P->n == P->cap) {
+        const int used = P->cap;
         P->cap = P->cap ? 2 * P->cap : 1024;
-        #define G(a) P->a = grow(P->a, (size_t)P->cap * sizeof *P->a)
+        #define G(a) P->a = pool_grow(P, P->a, (size_t)used * sizeof *P->a, (size_t)P->cap * sizeof *P->a)
         G(pos); G(lq); G(flag); G(ncig); G(cig_off); G(seq_off); G(smpl); G(file); G(end); G(mpos); G(isize); G(rnext_same); G(mapq); G(has_zq); G(qname);
         #undef G
     }
@@ -356,7 +370,7 @@ static void pool_add(pool_t *P, int file, int smpl, const char *qname, int flag,
     P->flag[r] = flag; P->pos[r] = pos; P->mapq[r] = (uint8_t)mapq; P->smpl[r] = smpl; P->file[r] = file; P->has_zq[r] = 0;
     P->rnext_same[r] = rnext_same; P->mpos[r] = mpos; P->isize[r] = isize;
     P->cig_off[r] = (int32_t)P->ncigs; P->ncig[r] = ncig;
-    if (P->ncigs + ncig + 1 > P->cigcap) { P->cigcap = (P->ncigs + ncig + 1) * 2; P->cig = grow(P->cig, P->cigcap * 4); }
+    if (P->ncigs + ncig + 1 > P->cigcap) { P->cigcap = (P->ncigs + ncig + 1) * 2; P->cig = pool_grow(P, P->cig, P->ncigs * 4, P->cigcap * 4); }
     int x = pos;
     for (int c = 0; c < ncig; ++c) {
         const int op = cig[c] & 15;
@@ -367,7 +381,7 @@ static void pool_add(pool_t *P, int file, int smpl, const char *qname, int flag,
     P->lq[r] = lq; P->seq_off[r] = (int32_t)P->nbase;
     if (P->nbase + lq + 1 > P->basecap) {
         P->basecap = (P->nbase + lq + 1) * 2;
-        P->seq16 = grow(P->seq16, P->basecap); P->qual = grow(P->qual, P->basecap); P->zq = grow(P->zq, P->basecap);
+        P->seq16 = pool_grow(P, P->seq16, P->nbase, P->basecap); P->qual = pool_grow(P, P->qual, P->nbase, P->basecap); P->zq = pool_grow(P, P->zq, P->nbase, P->basecap);
     }
     memcpy(P->seq16 + P->nbase, seq16, (size_t)lq); memcpy(P->qual + P->nbase, qual, (size_t)lq); memset(P->zq + P->nbase, 0, (size_t)lq);
     P->nbase += lq;
@@ -876,9 +890,10 @@ typedef struct { char *contig; int beg, end, open; } region_t;                /*
 
 /* ---- the device context, re-created when a tile needs more room than the last one had ---- */
 static bcfgpu_ctx *ctx; static int ctx_S, ctx_sites; static uint64_t ctx_reads; static unsigned long long n_wide_cells;
+static int ctx_fits(int S, int n_sites, uint64_t n_reads) { return ctx && ctx_S == S && n_sites <= ctx_sites && n_reads <= ctx_reads; }
 static void ensure_ctx(int S, int n_sites, uint64_t n_reads)
 {
-    if (ctx && ctx_S == S && n_sites <= ctx_sites && n_reads <= ctx_reads) return;
+    if (ctx_fits(S, n_sites, n_reads)) return;
     uint64_t rng = 0; int have_rng = 0;                                       /* errmod_cal's generator is the process's: it moves to the new context */
     if (ctx) { uint32_t nw = 0; CHECK(bcfgpu_truncated_cells(ctx, &nw)); n_wide_cells += nw; rng = bcfgpu_errmod_state(ctx); have_rng = 1; bcfgpu_destroy(ctx); ctx = NULL; }
     bcfgpu_cfg cfg; memset(&cfg, 0, sizeof cfg);
@@ -931,9 +946,10 @@ static void pending_set(const char *contig, const bcfgpu_gvcf_block *B, char ref
 
 static unsigned long long tot_entries, tot_pairs;
 /* --timing: where the wall time of a run goes (seconds): reading and parsing the files, building a tile's pool, the device
- * stages of a tile (every call up to the records' planes on the host), writing the records */
+ * stages of a tile (every call up to the records' planes on the host), writing the records; with --prefetch the wait inside
+ * bcfgpu_pool_adopt (what of the next tile's copy the current tile's stages did not cover) */
 #include <time.h>
-static int want_timing; static double t_read, t_pool, t_dev, t_emit;
+static int want_timing; static double t_read, t_pool, t_dev, t_emit, t_adopt;
 static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 /* ---- a tile's records, written beside the device stages of the next tile: process_tile() hands everything the record loop reads over
  * as a job (host copies only: sites, planes, the indel columns' results, the gVCF blocks) and goes on; one worker thread takes the
@@ -1070,12 +1086,25 @@ static void emit_finish(void)
 }
 
 /* ---- one tile: columns [t0, t1) of `contig` from the reads in P (all the reads that overlap the tile, file-major; file f =
- * [first[f], first[f+1])).  Every stage on the device; the records of the tile are written in position order. ---- */
-static void process_tile(pool_t *P, const int *first, int F, int S, const char *contig, const char *ref, int ref_len, int t0, int t1)
+ * [first[f], first[f+1])).  Its host preparation (tile_prepare: the mates' pairs, the per-sample position order) is apart from
+ * its device stages (tile_device), so that with --prefetch the next tile is prepared and its pool is on its way to the device
+ * while this tile's stages run; the records of the tiles are written in position order either way. ---- */
+typedef struct {
+    pool_t P;
+    int32_t *pa, *pb; int np;                       /* the overlapping mates */
+    int S, t0, t1, ref_len; const char *contig, *ref;
+} tilejob_t;
+static void pool_reads(const pool_t *P, bcfgpu_reads *rd)
 {
-    const int n_sites = t1 - t0;
+    memset(rd, 0, sizeof *rd);
+    rd->n_reads = P->n; rd->r_pos = P->pos; rd->r_lq = P->lq; rd->r_flag = P->flag; rd->r_ncig = P->ncig; rd->r_cig_off = P->cig_off;
+    rd->r_seq_off = P->seq_off; rd->cig = P->cig; rd->seq16 = P->seq16; rd->qual = P->qual; rd->zq = P->zq; rd->r_has_zq = P->has_zq;
+}
+static void tile_prepare(tilejob_t *T, const int *first, int F)
+{
+    pool_t *P = &T->P;
+    const int S = T->S;
     const double tw0 = want_timing ? now_s() : 0.;
-    ensure_ctx(S, n_sites, (uint64_t)P->nbase + 64);
     /* mate overlaps: htslib pairs the reads inside one file's iterator (bam_mplp_init_overlaps, mpileup.c:640) */
     int32_t *pa = malloc((size_t)(P->n + 1) * sizeof *pa), *pb = malloc((size_t)(P->n + 1) * sizeof *pb);
     int np = 0;
@@ -1112,17 +1141,30 @@ static void process_tile(pool_t *P, const int *first, int F, int S, const char *
             free(ord); free(tmp); free(inv);
         }
     }
+    T->pa = pa; T->pb = pb; T->np = np;
+    if (want_timing) t_dev += now_s() - tw0;
+}
 
-    bcfgpu_reads rd; memset(&rd, 0, sizeof rd);
-    rd.n_reads = P->n; rd.r_pos = P->pos; rd.r_lq = P->lq; rd.r_flag = P->flag; rd.r_ncig = P->ncig; rd.r_cig_off = P->cig_off;
-    rd.r_seq_off = P->seq_off; rd.cig = P->cig; rd.seq16 = P->seq16; rd.qual = P->qual; rd.zq = P->zq; rd.r_has_zq = P->has_zq;
+/* the device stages of a prepared tile.  adopted: its pool is the context's already (bcfgpu_pool_adopt) */
+static void tile_device(tilejob_t *T, int adopted)
+{
+    pool_t *P = &T->P;
+    const int S = T->S, t0 = T->t0, t1 = T->t1, n_sites = t1 - t0, ref_len = T->ref_len, np = T->np;
+    const char *contig = T->contig, *ref = T->ref;
+    int32_t *pa = T->pa, *pb = T->pb;
+    const double tw0 = want_timing ? now_s() : 0.;
+    bcfgpu_reads rd;
+    pool_reads(P, &rd);
 
     /* the pool goes up once and stays in HBM: BAQ (new qualities and ZQ bytes for the reads it applies to; not with -B), the
      * mate-overlap tweak, the pileup of the tile -- each on the copy the stage before left there */
-    CHECK(bcfgpu_pool_upload(ctx, &rd, NULL, P->mapq));
+    if (!adopted) {
+        ensure_ctx(S, n_sites, (uint64_t)P->nbase + 64);
+        CHECK(bcfgpu_pool_upload(ctx, &rd, NULL, P->mapq));
+    }
     if (baq_flag) CHECK(bcfgpu_pool_baq(ctx, ref, ref_len, baq_flag, NULL));
     CHECK(bcfgpu_pool_overlap_tweak(ctx, np, pa, pb));
-    free(pa); free(pb);
+    free(pa); free(pb); T->pa = T->pb = NULL;
     bcfgpu_tile tile;
     int32_t *col_n = malloc((size_t)(n_sites + 1) * sizeof *col_n);
     uint8_t *col_indel = malloc((size_t)n_sites + 1);
@@ -1215,6 +1257,32 @@ static void process_tile(pool_t *P, const int *first, int F, int S, const char *
         J.gv_blk = gv_blk; J.gv_dp = gv_dp; J.gv_block = gv_block; J.gv_pl = gv_pl;
         emit_submit(&J);
     }
+}
+
+/* ---- the tile loop's two orders.  Without --prefetch a tile is prepared, uploaded and run before the next one is read.  With
+ * it the pools alternate between two page-locked sets of buffers: tile i + 1 is read and prepared, its pool staged
+ * (bcfgpu_pool_stage returns with the copies queued), then tile i, whose pool the context holds, runs its device stages under
+ * those copies, and bcfgpu_pool_adopt makes the staged pool the context's.  Tile i's host arrays live until its stages are done
+ * (bcfgpu_pool_pileup reads the sample of each read, -B's bcfgpu_gap_prep_tile the ZQ tags).  The -C side context, the depth
+ * cap and the files are ahead by one tile; the draws of errmod_cal, the gVCF block and the records keep the tiles' order. ---- */
+static int prefetch;
+static tilejob_t TJ[2]; static int tj_fill; static tilejob_t *tj_run;          /* tj_run: staged and adopted, its device stages still to run */
+static void tile_drain(void) { if (tj_run) { tile_device(tj_run, 1); tj_run = NULL; } }
+static void tile_submit(tilejob_t *T, const int *first, int F)
+{
+    tile_prepare(T, first, F);
+    if (!prefetch) { tile_device(T, 0); return; }
+    const int n_sites = T->t1 - T->t0;
+    /* a tile that needs a larger context: the one before runs first, on the context that holds its pool */
+    if (!ctx_fits(T->S, n_sites, (uint64_t)T->P.nbase + 64)) { tile_drain(); ensure_ctx(T->S, n_sites, (uint64_t)T->P.nbase + 64); }
+    bcfgpu_reads rd;
+    pool_reads(&T->P, &rd);
+    CHECK(bcfgpu_pool_stage(ctx, &rd, NULL, T->P.mapq));
+    tile_drain();
+    const double ta0 = want_timing ? now_s() : 0.;
+    CHECK(bcfgpu_pool_adopt(ctx));
+    if (want_timing) t_adopt += now_s() - ta0;
+    tj_run = T; tj_fill ^= 1;
 }
 
 /* ---- the live window: the reads of every file that passed the filters and the depth cap and may still cover a column ---- */
@@ -1367,7 +1435,7 @@ static int run_shards(int n_gpus, int argc0, char **argv0, int first_file, const
             if (!strcmp(o, "-o")) { char *e; strtol(argv0[i + 1], &e, 10); if (*e) { ++i; continue; } }
             if (o[0] != '-') break;                              /* the positional form: ref.fa contig beg end come from -f / -r below */
             av[n++] = argv0[i];
-            if (o[0] == '-' && i + 1 < first_file && argv0[i + 1][0] != '-' && strcmp(o, "-B") && strcmp(o, "-E") && strcmp(o, "-A") && strcmp(o, "-p") && strcmp(o, "-I") && strcmp(o, "-6") && strcmp(o, "--illumina1.3+") && strcmp(o, "--timing") && strcmp(o, "-x") && strcmp(o, "--ignore-overlaps") && strcmp(o, "--no-version")
+            if (o[0] == '-' && i + 1 < first_file && argv0[i + 1][0] != '-' && strcmp(o, "-B") && strcmp(o, "-E") && strcmp(o, "-A") && strcmp(o, "-p") && strcmp(o, "-I") && strcmp(o, "-6") && strcmp(o, "--illumina1.3+") && strcmp(o, "--timing") && strcmp(o, "--prefetch") && strcmp(o, "-x") && strcmp(o, "--ignore-overlaps") && strcmp(o, "--no-version")
                 && strcmp(o, "--ignore-RG") && strcmp(o, "--list-samples")) av[n++] = argv0[++i];
         }
         av[n++] = "-f"; av[n++] = (char *)ref_path; av[n++] = "-r"; av[n++] = rl;
@@ -1494,6 +1562,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[1], "--no-version")) { ++argv; --argc; }                                                          /* (no ##bcftoolsVersion / ##bcftoolsCommand lines are written anyway) */
         else if (!strcmp(argv[1], "--threads")) { argv += 2; argc -= 2; }                                                      /* (the output's compression threads: nothing to do here) */
         else if (!strcmp(argv[1], "--timing")) { want_timing = 1; argv += 1; argc -= 1; }
+        else if (!strcmp(argv[1], "--prefetch")) { prefetch = 1; argv += 1; argc -= 1; }
         else if (!strcmp(argv[1], "--tile")) { tile_cols = atoi(argv[2]); if (tile_cols < 1) DIE("--tile: at least one column\n"); argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-d")) { max_depth = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-s")) { add_samples(argv[2], 0); argv += 2; argc -= 2; }            /* mpileup.c:1058-1059,1087,1016 */
@@ -1666,7 +1735,7 @@ int main(int argc, char **argv)
     bcfgpu_depth_state *dcap = bcfgpu_depth_cap_new(F, max_depth);             /* the iterators' buffers (mpileup -d), one per file */
     if (!dcap) DIE("%s\n", bcfgpu_last_error());
     lwin_t *win = calloc((size_t)F, sizeof *win);
-    pool_t P; memset(&P, 0, sizeof P);
+    TJ[0].P.pinned = TJ[1].P.pinned = prefetch && !list_only;
     int *first = malloc((size_t)(F + 1) * sizeof *first);
     long long *n_in_smpl = calloc((size_t)S, sizeof *n_in_smpl); int *nf_smpl = calloc((size_t)S, sizeof *nf_smpl), *lastf_smpl = malloc((size_t)S * sizeof *lastf_smpl);
     for (int s = 0; s < S; ++s) lastf_smpl[s] = -1;
@@ -1735,15 +1804,17 @@ int main(int argc, char **argv)
             t_read += tr1 - tr0;
             if (!list_only) {
                 /* stage 2: the tile's pool = the reads of the window that overlap the tile, file after file */
-                pool_clear(&P);
+                tilejob_t *T = &TJ[tj_fill];
+                pool_t *P = &T->P;
+                pool_clear(P);
                 for (int f = 0; f < F; ++f) {
-                    first[f] = P.n;
-                    for (int i = 0; i < win[f].n; ++i) { const lrec_t *x = win[f].r[i]; if (overlaps(x->pos, x->end, t0 - margin, t1 + margin)) pool_add_rec(&P, f, x); }
+                    first[f] = P->n;
+                    for (int i = 0; i < win[f].n; ++i) { const lrec_t *x = win[f].r[i]; if (overlaps(x->pos, x->end, t0 - margin, t1 + margin)) pool_add_rec(P, f, x); }
                 }
-                first[F] = P.n;
+                first[F] = P->n;
                 if (want_timing) t_pool += now_s() - tr1;
-                if (P.n) { process_tile(&P, first, F, S, contig, ref, ref_len, t0, t1); ++n_tiles; }
-                else { emit_wait(); pending_flush(); }                      /* columns without a read: a gap ends a gVCF block (gvcf.c:131) */
+                if (P->n) { T->S = S; T->t0 = t0; T->t1 = t1; T->contig = contig; T->ref = ref; T->ref_len = ref_len; tile_submit(T, first, F); ++n_tiles; }
+                else { tile_drain(); emit_wait(); pending_flush(); }        /* columns without a read: a gap ends a gVCF block (gvcf.c:131) */
                 n_cols_tot += (unsigned long long)(t1 - t0);
             }
             /* reads that end before the next tile's pool begins are through */
@@ -1761,6 +1832,7 @@ int main(int argc, char **argv)
                 if (next_pos - margin > t0) t0 = next_pos - margin;         /* a stretch without reads: on to the next read */
             }
         }
+        tile_drain();                                                       /* (the next region may bring another reference sequence) */
         parsers_stop(rdr, F);
         for (int f = 0; f < F; ++f) reader_close(&rdr[f]);
     }
@@ -1777,7 +1849,7 @@ int main(int argc, char **argv)
                                       "instead of errmod_cal's draw\n", n_wide_cells);
     fprintf(stderr, "%llu reads of %d samples, %llu overlapping pairs, %llu pileup entries in %llu columns (%d tiles of <= %d)\n",
             n_reads_tot, S, tot_pairs, tot_entries, n_cols_tot, n_tiles, tile_cols);
-    if (want_timing) fprintf(stderr, "[bcfgpu_sam] seconds: reading and parsing the files %.3f, tile pools %.3f, device stages %.3f, writing records %.3f\n", t_read, t_pool, t_dev, t_emit);
+    if (want_timing) fprintf(stderr, "[bcfgpu_sam] seconds: reading and parsing the files %.3f, tile pools %.3f, device stages %.3f, writing records %.3f, waiting in bcfgpu_pool_adopt %.3f\n", t_read, t_pool, t_dev, t_emit, t_adopt);
     if (vio_close(fout)) DIE("%s\n", vio_error());
     if (ctx) bcfgpu_destroy(ctx);
     if (cap_ctx) bcfgpu_destroy(cap_ctx);
@@ -1786,7 +1858,7 @@ int main(int argc, char **argv)
 usage:
     fprintf(stderr, "usage: bcfgpu_sam [-a TAG,..] [--gvcf INT,..] [-O v|z|u|b] [-o out] [-d INT] [-s LIST | -S FILE] [-G FILE] [--ignore-RG]\n"
                     "                  [-B | -E] [-6] [-x] [-A] [-q INT] [-Q INT] [-C INT] [--ff INT] [--rf INT] [-I] [-o INT] [-e INT] [-h INT] [-m INT] [-F FLOAT] [-p] [-L INT]\n"
-                    "                  [--tile COLUMNS] [--gpus N]\n"
+                    "                  [--tile COLUMNS] [--gpus N] [--prefetch]\n"
                     "                  -f ref.fa [-r CHR[:BEG[-END]],... | -R FILE] [-b FILE] file.sam|file.bam [...]      (as `bcftools mpileup`)\n"
                     "              or  ref.fa contig beg end file.sam|file.bam [...]                    (beg, end 1-based inclusive)\n");
     return 2;

@@ -465,8 +465,27 @@ int  bcfgpu_pileup_packed(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const bcfg
  *   bcfgpu_pool_pileup        the tile, as bcfgpu_pileup builds it (r_smpl, or smpl_off as in bcfgpu_packed)
  *   bcfgpu_pool_download      the pool's current qualities / ZQ bytes / mapping qualities back to the host (any may be NULL): tests,
  *                             and callers that want BQ/ZQ tags written
- * The pool lives in the context's workspace until the next bcfgpu_pool_upload / bcfgpu_pileup[_packed] on that context. */
+ * The pool lives in the context's workspace until the next bcfgpu_pool_upload / bcfgpu_pool_adopt / bcfgpu_pileup[_packed] on that
+ * context. */
 int  bcfgpu_pool_upload(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const bcfgpu_packed *pk, const uint8_t *r_mapq);
+/* The read callback running ahead of the column loop (mpileup.c:183-246: reads are taken off the files while columns are being
+ * called): the pool of the next region comes to the device while the stages of the current one run.
+ *   bcfgpu_pool_stage   arguments, checks and return codes of bcfgpu_pool_upload, in all three forms.  The copies are queued on a
+ *                       copy stream of the context's own and the call returns without waiting for the device.  The context's
+ *                       pool is not touched: the pool, its keep mask, what bcfgpu_pool_baq left, the last pileup's tile, both
+ *                       indel tiles and a draw plan stay valid, and every call gives what it would have given without this one.
+ *                       The caller's arrays must stay unchanged until bcfgpu_pool_adopt has returned.  Arrays from
+ *                       bcfgpu_host_alloc are what lets the copy run beside kernels; with pageable arrays the results are the
+ *                       same, but the call may block for the length of the copy.  A second call before an adopt replaces the
+ *                       staged pool (after waiting for the first one's copies).
+ *   bcfgpu_pool_adopt   waits for the staged copies (not for the context's stream), forms the pool on the context's stream and
+ *                       makes it the context's pool: from there on the context is as bcfgpu_pool_upload of the same arrays would
+ *                       have left it (the old pool, its keep mask and BAQ results gone; bcfgpu_pileup_entries,
+ *                       bcfgpu_pileup_indel_tile and bcfgpu_gap_prep_tile on the old pileup refuse).  BCFGPU_E_ARG when nothing is
+ *                       staged; the context's pool stays usable then.
+ * bcfgpu_destroy with a staged pool pending waits for its copies. */
+int  bcfgpu_pool_stage(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const bcfgpu_packed *pk, const uint8_t *r_mapq);
+int  bcfgpu_pool_adopt(bcfgpu_ctx *ctx);
 int  bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len, int flag, int32_t *ret);
 int  bcfgpu_pool_cap_mapq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len, int32_t thres, int32_t *cap);
 int  bcfgpu_pool_keep(bcfgpu_ctx *ctx, const uint8_t *keep);

@@ -83,49 +83,72 @@ static_assert(NPART == SITE_NSUM + 3, "phase A's partial sums: the site totals a
 // (rank r = qualities above it in the lane's mask):  reverse-strand reads | forward-strand reads << 8 | quality << 16.
 // NRANK qualities per round (binned base qualities give a handful; a lane with more goes round again).
 //   qm      bit q = some read of the source has quality q
-//   src(j)  key7 of source element j, or -1 when the element is not of this base / was rejected
+//   src     the source: key(j) is its j-th key as phase A left it, ok(k) whether a key is one of its reads
 // Returns sum of the qualities of the reads counted (QS).
 #ifndef WR
 #define WR 2            // reads of a run taken per step of the errmod walk
 #endif
-// the sources of count_runs(): key7 of the j-th element or -1 -- the reads of the primary base (rejected reads are zeros), or those
-// of the lane's other reads that show base b
+// the sources of count_runs(): the reads of the primary base (rejected reads are zeros), or those of the lane's other reads
+// that show base b.  operator(): key7 of the j-th element, or -1 when it is not one of the source's reads.
 struct PrimSrc {
     const uint16_t *kpp;
-    __device__ __forceinline__ int operator()(int j) const { const uint32_t k = kpp[j]; return k ? (int)(k & 0x7f) : -1; }
+    __device__ __forceinline__ uint32_t key(int j) const { return kpp[j]; }
+    __device__ __forceinline__ bool ok(uint32_t k) const { return k != 0; }
+    __device__ __forceinline__ int operator()(int j) const { const uint32_t k = key(j); return ok(k) ? (int)(k & 0x7f) : -1; }
 };
 struct BaseSrc {
     const uint16_t *kp; int b;
-    __device__ __forceinline__ int operator()(int i) const { const uint32_t k = kp[i]; return (int)KEY_B(k) == b ? (int)(k & 0x7f) : -1; }
+    __device__ __forceinline__ uint32_t key(int i) const { return kp[i]; }
+    __device__ __forceinline__ bool ok(uint32_t k) const { return KEY_B(k) == (uint32_t)b; }
+    __device__ __forceinline__ int operator()(int i) const { const uint32_t k = key(i); return ok(k) ? (int)(k & 0x7f) : -1; }
 };
+__device__ __forceinline__ uint32_t popc64(uint64_t x) { return (uint32_t)__popc((uint32_t)x) + (uint32_t)__popc((uint32_t)(x >> 32)); }   // (32 bits wide: __popcll's compares are 64)
+// The counting loop.  FIRST: the mask holds every quality of the source (the first round).  CHK: some lane of the wavefront has
+// more than NRANK qualities in its mask, so a read's rank may lie beyond the slots.
+template <bool FIRST, bool CHK, class Src>
+__device__ __forceinline__ void count_keys(uint32_t *s_slot, uint64_t qm, int tid, Src src, int nsrc)
+{
+    const uint64_t qm1 = qm >> 1;                                   // rank of q = qualities above it = popcount(qm >> (q + 1))
+    // FU source elements per trip, read whether or not they are inside the lane's slice (up to FU - 1 keys past it: other
+    // cells' keys or the key array's slack): their reads are in flight before the first count is added, and whether an
+    // element is the lane's own is one term of its count's condition.
+    for (int j = 0; __any(j < nsrc); j += FU) {
+        if (j < nsrc) {
+            uint32_t k4[FU];
+            #pragma unroll
+            for (int u = 0; u < FU; ++u) k4[u] = src.key(j + u);
+            #pragma unroll
+            for (int u = 0; u < FU; ++u) {
+                const uint32_t k = k4[u], q = KEY_Q(k);
+                const uint32_t r = popc64(qm1 >> q);
+                bool take = src.ok(k) && (u == 0 || j + u < nsrc);
+                if (!FIRST) take = take && ((qm >> q) & 1ull);
+                if (CHK) take = take && r < (uint32_t)NRANK;
+                const uint32_t rv = (uint32_t)((int32_t)(k << 31) >> 31);                  // all ones on the reverse strand
+                if (take) atomicAdd(&s_slot[r * WG + tid], (rv & 1u) | (~rv & 0x100u));     // reverse strand: 1, forward: 0x100
+            }
+        }
+    }
+}
 template <bool FIRST, class Src>
 __device__ __forceinline__ uint32_t count_runs(uint32_t *s_slot, uint64_t qm, int tid, Src src, int nsrc)
 {
     #pragma unroll
     for (int k = 0; k < NRANK; ++k) s_slot[k * WG + tid] = 0;
-    const uint64_t qm1 = qm >> 1;                                   // rank of q = qualities above it = popcount(qm >> (q + 1))
-    // FU source elements per trip: their reads are in flight before the first count is added
-    for (int j = 0; __any(j < nsrc); j += FU) {
-        int k4[FU];
-        #pragma unroll
-        for (int u = 0; u < FU; ++u) k4[u] = j + u < nsrc ? src(j + u) : -1;
-        #pragma unroll
-        for (int u = 0; u < FU; ++u) {
-            const int key = k4[u], q = (key >> 1) & 63;
-            if (key >= 0 && (FIRST || ((qm >> q) & 1ull))) {       // first round: the mask holds every quality of the source
-                const int r = __popcll(qm1 >> q);
-                if (r < NRANK) atomicAdd(&s_slot[r * WG + tid], (key & 1) ? 1u : 0x100u);
-            }
-        }
-    }
+    if (__any(popc64(qm) > (uint32_t)NRANK)) count_keys<FIRST, true>(s_slot, qm, tid, src, nsrc);
+    else count_keys<FIRST, false>(s_slot, qm, tid, src, nsrc);
     // the quality of every rank joins its counts
     uint32_t qs = 0;
     uint64_t m = qm;
+    #pragma unroll
     for (int r = 0; r < NRANK && __any(m != 0); ++r) {
-        const int q = 63 - __clzll((long long)(m | 1ull));
-        const uint32_t c = s_slot[r * WG + tid];
-        if (m != 0) { s_slot[r * WG + tid] = c | (uint32_t)q << 16; qs += (uint32_t)q * ((c & 0xffu) + (c >> 8)); }
-        m &= ~(1ull << q);
+        if (m != 0) {
+            const uint32_t q = 63u - (uint32_t)__builtin_clzll(m);
+            const uint32_t c = s_slot[r * WG + tid];                // reverse | forward << 8
+            s_slot[r * WG + tid] = c | q << 16;
+            qs = __builtin_amdgcn_udot4(c, q | q << 8, qs, false);  // + q * (reverse + forward)
+            m &= ~(1ull << q);
+        }
     }
     return qs;
 }
@@ -330,7 +353,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         const uint32_t abase = base & ~3u;                       // key index 0 of this round
         const uint32_t lim = DEEP ? span_end : min(abase + (uint32_t)cap, span_end);
         if (tid == 0) { s_next = 0xffffffffu; s_skip = 0; }
-        if (LDS_HIST) for (int i = tid; i < P.hist_slots * NPART * pcol; i += WG) s_part[i] = 0;
+        if (LDS_HIST) {
+            int i0 = tid;                                        // the first dword's address is formed here, every round: hoisted out of
+            asm volatile("" : "+v"(i0));                         // the rounds it is one more value alive through both phases, and spilled
+            for (int i = i0; i < P.hist_slots * NPART * pcol; i += WG) s_part[i] = 0;
+        }
         __syncthreads();
         const bool cand = !done && !deep && beg >= base && end <= lim;
         if (!done && !cand) atomicMin(&s_next, beg);             // the first cell left for a later round (deep tiles only): one that
@@ -615,9 +642,12 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                 misc_p[cell] = mark;             // read back where the cell's planes are stored (below)
             }
         }
+        // the soft-clipped reads, when SCR is asked for (mpileup's default leaves it out): a pass of its own
+        uint32_t scr = 0;
+        if (want_scr) for (int i = 0; i < cnt_raw; ++i) scr += KEY_SC((uint32_t)kp[i]);
         // pass 1: the quality mask of the primary base; the few other reads are gathered at the front of the slice
         uint64_t qmask = 0;          // qualities seen among the reads of the primary base
-        uint32_t n_prim = 0, scr = 0;
+        uint32_t n_prim = 0;
         uint64_t qs64 = 0;           // QS[0..3], 16 bits each
         uint64_t ad64 = 0;           // ADF[0..3] | ADR[0..3]<<32, 8 bits each
         uint32_t n_b4 = 0;           // reads showing neither A, C, G nor T
@@ -627,11 +657,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
             for (int i = 0; i < cnt_raw; ++i) {
                 const uint32_t k = k_nx;
                 k_nx = kp[i + 1];                               // one past the slice stays inside the key array's slack
-                const uint32_t pb = (k >> 11) & 1u;             // KEY_PRIM
+                const uint32_t pb = k >> 11;                    // KEY_PRIM, the top bit of a key
                 qmask |= (uint64_t)pb << KEY_Q(k);
                 n_prim += pb;
-                if (want_scr) scr += KEY_SC(k);
-                if (k != 0 && !pb) {                            // rare
+                if (k - 1u < KEY_PRIM - 1u) {                   // rare: a read that is neither rejected (0) nor of the primary base
                     // swapped to position n_other <= i (behind the reader): the walks only count reads per (base, quality,
                     // strand), so the order inside a cell is free
                     const uint32_t t = kp_w[n_other], rev = KEY_REV(k), q = KEY_Q(k), b = KEY_B(k);

@@ -1,17 +1,30 @@
 #!/usr/bin/env python3
-"""Register and instruction counts of glfgen_kernel's phase-A loop, from the ISA a --save-temps build leaves (no GPU needed).
+"""Register and instruction counts of glfgen_kernel's loops, from the ISA a --save-temps build leaves (no GPU needed).
 
 usage: python3 tools/glf_isa.py <glfgen-hip-amdgcn-amd-amdhsa-gfx950.s> [kernel name substring, default ILb0ELb1ELb0E]
 
 Build the listing with the Makefile's options for glfgen.hip, e.g. in a scratch copy of csrc/:
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off $(make -s print-flags-glfgen) --save-temps -c glfgen.hip
+(or --cuda-device-only -S -o <listing>).
 
 Phase A's loop is taken from LLVM's loop annotations in the listing ("; =>This Inner Loop Header", "in Loop: Header=BBx",
 "Parent Loop BBx"): the innermost loop whose blocks (nested loops included) hold the byte-plane sums (v_dot4_u32_u8 /
 v_dot2_u32_u16) and no double-precision instruction.  Printed per block of that loop, in listing order: the vector ALU
 instructions (v_*, which is what SQ_INSTS_VALU counts), v_readlane / v_writelane among them, LDS and global/flat memory
 instructions, and the block's IR name.  The totals count every block once (a static count: rare blocks such as the
-tile-tail fetch or the diff-read sums are included); reads per trip: 4 per lane."""
+tile-tail fetch or the diff-read sums are included); reads per trip: 4 per lane.
+
+Phase B's loops follow, each found by what it holds, not by its label (static counts, every block of the loop once):
+  pass 1      the innermost loop with the swap of a rare read (two ds_write_b16) and the 64-bit shift of the quality mask, no
+              global load; keys a trip = its ds_read_u16 outside the swap blocks
+  count_runs  every innermost loop with FU = 4 ds_add_u32 and ds_read_u16 and no byte-plane sum: "first" when it shifts the
+              mask once a key (the rank), "later" when twice (the test of the quality as well); "rank test" when it compares
+              with a constant after the population counts; the nesting depth tells the primary base (the shallower loops) from
+              the other bases
+  rank code   "the quality of every rank joins its counts": the blocks that read and write one slot dword (ds_read_b32 and
+              ds_write_b32) with the v_ffbh_u32 blocks around them -- a loop, or the unrolled copies, then counted per copy
+  walk        the innermost loops with four global_load_dwordx2 and double-precision arithmetic, with the s_waitcnt that
+              opens the trip"""
 import re
 import sys
 
@@ -115,6 +128,86 @@ def main():
                 b["lab"], c["v"], c["rl"], c["wl"], c["ds"], c["gl"], b["name"][:60]))
         print("  loop total (static, every block once): v_*=%d readlane=%d writelane=%d ds=%d mem=%d" % (
             tot["v"], tot["rl"], tot["wl"], tot["ds"], tot["gl"]))
+        phase_b(bl, parent, {id(b) for b in mem})
+
+
+def cnt(ins, *prefix):
+    return sum(i.startswith(prefix) for i in ins)
+
+
+def phase_b(bl, parent, phase_a):
+    """The loops of phase B, by content (see the module's docstring); `phase_a`: the blocks of phase A's loop."""
+    def depth(h):
+        d = 1
+        while parent.get(h) is not None:
+            h, d = parent[h], d + 1
+        return d
+    hdrs = [b["hdr"] for b in bl if b["hdr"] == b["lab"].lstrip(".L")]
+    inner = [h for h in hdrs if h not in parent.values()]
+    loops = {h: [b for b in bl if b["hdr"] == h] for h in inner}
+    def line(tag, h, mem, extra=""):
+        ins = [i for b in mem for i in b["ins"]]
+        print("  %-34s header %-9s depth %d, %2d blocks: v_*=%3d ds=%2d mem=%2d%s" % (
+            tag, h, depth(h), len(mem), cnt(ins, "v_"), cnt(ins, "ds_"), cnt(ins, "global_", "buffer_", "flat_"), extra))
+    print("  phase B:")
+    skip = set(phase_a)
+    for h in inner:
+        mem = loops[h]
+        ins = [i for b in mem for i in b["ins"]]
+        glob, dot = cnt(ins, "global_", "buffer_", "flat_"), sum(bool(re.match(r"v_dot[24]", i)) for i in ins)
+        if cnt(ins, "ds_write_b16") >= 2 and cnt(ins, "v_lshlrev_b64") and not glob and not dot:
+            keys = sum(cnt(b["ins"], "ds_read_u16") for b in mem if not cnt(b["ins"], "ds_write_b16"))
+            # the common path: without the blocks of the rare read, from the one that swaps it (behind an s_cbranch_execz) round
+            # the loop to that branch's target
+            rare = set()
+            for k, b in enumerate(mem):
+                nxt = mem[(k + 1) % len(mem)]
+                m = re.match(r"s_cbranch_execz\s+(\S+)", b["ins"][-1]) if b["ins"] else None
+                if m and cnt(nxt["ins"], "ds_write_b16"):
+                    j = (k + 1) % len(mem)
+                    while mem[j]["lab"] != m.group(1) and len(rare) < len(mem):
+                        rare.add(j)
+                        j = (j + 1) % len(mem)
+            common = [i for k, b in enumerate(mem) if k not in rare for i in b["ins"]]
+            line("pass 1, %d keys a trip" % keys, h, mem, "  common path (no rare read): v_*=%d ds=%d" % (cnt(common, "v_"), cnt(common, "ds_")))
+        elif cnt(ins, "ds_add_u32") == 4 and cnt(ins, "ds_read_") and not dot:
+            skip.update(id(b) for b in mem)
+            later = cnt(ins, "v_lshrrev_b64") > 4
+            chk = any(re.match(r"v_cmpx?_(gt|lt|le|ge)_u(32|64)\S*\s+(vcc|s\[\d+:\d+\]), (10|9), ", i) or
+                      re.match(r"v_cmpx?_(gt|lt|le|ge)_u(32|64)\S*\s+(10|9), ", i) for i in ins)
+            line("count_runs<%s>, %s, 4 keys" % ("false" if later else "true", "rank test" if chk else "no rank test"), h, mem)
+        elif glob >= 4 and any(re.match(r"v_(fma|add|mul)_f64", i) for i in ins):
+            wait = next((i for i in mem[0]["ins"] if i.startswith("s_waitcnt")), "none in the header block")
+            line("walk_runs trip", h, mem, "  opens with: " + wait)
+    # the rank code: slot dwords read and written back
+    upd = [k for k, b in enumerate(bl) if cnt(b["ins"], "ds_read_b32") and cnt(b["ins"], "ds_write_b32") and id(b) not in skip]
+    groups = []
+    for k in upd:
+        if groups and k - groups[-1][-1] <= 4:
+            groups[-1].append(k)
+        else:
+            groups.append([k])
+    done = set()
+    for g in groups:
+        h = bl[g[0]]["hdr"]
+        if h in loops and any(cnt(b["ins"], "v_ffbh_u32") for b in loops[h]):
+            if h not in done:
+                line("rank code, a loop: a trip a rank", h, loops[h])
+                done.add(h)
+            continue
+        # unrolled: a copy = the blocks from one that holds (or follows) the v_ffbh_u32 pair up to the next copy's; the last
+        # copy runs into the code behind it and is left out of the figure
+        first = lambda k: k - 1 if k and cnt(bl[k - 1]["ins"], "v_ffbh_u32") and not cnt(bl[k]["ins"], "v_ffbh_u32") else k
+        if len(g) < 2 or not any(cnt(b["ins"], "v_ffbh_u32") for b in bl[first(g[0]):g[-1] + 1]):
+            continue
+        per = []
+        for k0, k1 in zip(g, g[1:]):
+            ins = [i for b in bl[first(k0):first(k1)] for i in b["ins"]]
+            per.append((cnt(ins, "v_"), cnt(ins, "ds_")))
+        per.sort()
+        v, d = per[len(per) // 2]
+        print("  %-34s from %-9s depth %d, %2d copies: v_*=%3d ds=%2d a rank (the median copy)" % (
+            "rank code, unrolled", bl[first(g[0])]["lab"], depth(h) + 1 if h else 1, len(g), v, d))
 
 
 if __name__ == "__main__":

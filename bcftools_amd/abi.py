@@ -21,6 +21,10 @@ INT32_MISSING = -2147483648
 INT32_VECTOR_END = -2147483647
 GT_MISSING, GT_VECTOR_END = -1, -2
 
+# FORMAT keys of an mpileup record in bcf_call2bcf's order (BCFGPU_BCF_*), each with the fmt_flag bit that selects it (PL: always)
+BCF_KEYS = ("PL", "DP", "DV", "SP", "DP4", "ADF", "ADR", "AD", "DPR", "SCR", "QS")
+BCF_KEY_FLAG = (0, FMT_DP, FMT_DV, FMT_SP, FMT_DP4, FMT_ADF, FMT_ADR, FMT_AD, FMT_DPR, FMT_SCR, FMT_QS)
+
 RD_REV, RD_SCLIP, RD_DEL, RD_SKIP = 1 << 20, 1 << 21, 1 << 22, 1 << 23
 
 
@@ -226,6 +230,8 @@ PROTOTYPES = {
     "bcfgpu_compact_calls_async": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(CallOut), C.c_int32, C.c_int32, C.c_void_p,
                                              C.c_uint64, C.c_void_p]),
     "bcfgpu_compact_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "bcfgpu_mplp_encode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MplpOut), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_comm_init_all": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
     "bcfgpu_comm_destroy": (None, [C.c_void_p]),
     "bcfgpu_gather_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

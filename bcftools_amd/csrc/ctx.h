@@ -81,13 +81,15 @@ enum WsSlot : int {
     // bcfgpu_gvcf_blocks, bcfgpu_compact_calls[_async]: scratch for one call
     WS_GVCF_SCAN = 32, WS_GVCF_SCAN_TMP = 33,
     WS_COMPACT_SIZE = 35, WS_COMPACT_SCAN_TMP = 36, WS_COMPACT_COUNTS = 37,
+    // bcfgpu_mplp_encode_bcf (bcfenc.hip): scratch for one call -- the keys' integer types per site, the scan's temporary storage
+    WS_COMPACT_BCF_TYPES = 167, WS_COMPACT_BCF_SCAN_TMP = 168,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_POOL_STAGE_RECS + 1    // one past the highest slot
+    WS_COUNT = WS_COMPACT_BCF_SCAN_TMP + 1    // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names
@@ -109,7 +111,8 @@ enum PinnedSlot : int {
     PIN_GTILE_KEPT = 2,                 // bcfgpu_gap_prep_tile: the columns that go on
     PIN_PLP_COL_COUNTS = 3,             // bcfgpu_pool_pileup: col_n / col_indel
     PIN_PBAQ_REF = 6,                   // bcfgpu_pool_baq: the reference slice (the call returns with its copy in flight)
-    PINNED_COUNT = PIN_PBAQ_REF + 1     // one past the highest slot
+    PIN_BCF_TOTAL = 7,                  // bcfgpu_mplp_encode_bcf: the size of all blocks
+    PINNED_COUNT = PIN_BCF_TOTAL + 1    // one past the highest slot
 };
 
 // workspace / pinned host buffer `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails

@@ -8,6 +8,8 @@
  *               --tile COLUMNS  columns per device tile (default 16384);  --gpus N  region shards, a process per shard
  *               --prefetch  the next tile's reads go to the device (bcfgpu_pool_stage, from page-locked buffers) while the device
  *                           stages of the current tile run; the same output
+ *               --device-records  with -O u|b: the per-sample part of every SNP and indel record is encoded as BCF2 on the device
+ *                           (bcfgpu_mplp_encode_bcf) and comes to the host as bytes instead of planes; the same output
  *               --list-samples: print "sample <TAB> reads entering the pileup <TAB> files" and stop (no device needed)
  *
  *  A region is streamed through in TILES: the files are read in step with the tiles -- a position-sorted file no
@@ -30,6 +32,7 @@
  *  and for the columns where some read is followed by an indel (mpileup.c:354-365):
  *      bcfgpu_gap_prep_tile (bcf_call_gap_prep on the candidate columns, in HBM) -> bcfgpu_mpileup on its indel tile
  *  with -C INT: bcfgpu_pool_baq + bcfgpu_pool_cap_mapq on every batch of reads as it comes off the files (mpileup.c:234-241),
+ *  with --device-records: bcfgpu_mplp_encode_bcf on the planes of both passes, the writer then frames the bytes (vio_write_record_indiv),
  *  with --gvcf: bcfgpu_gvcf_blocks per tile, the block that reaches a tile's end joined with the next tile's first (gvcf.c:88-226);
  *  and the record loop writes what bcf_call2bcf (bam2bcf.c:756-906) puts in the record, in its order, under mpileup's header
  *  (mpileup.c:510-602), as VCF, bgzipped VCF or BCF (host/vcfio.c).  tests/test_c_host.py compares the whole output with the
@@ -779,8 +782,14 @@ static void put_counts(const char *lead, const int32_t *f, const int32_t *r, int
 }
 
 /* what bcf_call2bcf writes into a record, in its order (bam2bcf.c:756-906); alleles: the ready REF\tALT text */
+/* --device-records: the per-sample part of the records comes from the device as BCF2 bytes (bcfgpu_mplp_encode_bcf) */
+static int device_records, dr_on;                                            /* the option; the option on a BCF output */
+static int32_t dr_key[BCFGPU_BCF_NKEYS];                                     /* the FORMAT keys' indices in the header's dictionary */
+static unsigned long long n_dev_records;                                     /* records written with a block from the device */
+
+/* indiv != NULL: the record's per-sample part, encoded already (l_indiv bytes); the planes are not read then */
 static void print_record(const char *contig, int pos1, const char *alleles, const char *prefix, const bcfgpu_site *c,
-                         const planes_t *pp, size_t k, int S)
+                         const planes_t *pp, size_t k, int S, const uint8_t *indiv, size_t l_indiv)
 {
     const int na = c->n_alleles;
     fprintf(LN, "%s\t%d\t.\t%s\t0\t.\t%sDP=%u", contig, pos1, alleles, prefix, c->ori_depth);
@@ -820,6 +829,13 @@ static void print_record(const char *contig, int pos1, const char *alleles, cons
     if (fmt_flag & BCFGPU_FMT_DPR) fputs(":DPR", LN);
     if (fmt_flag & BCFGPU_FMT_SCR) fputs(":SCR", LN);
     if (fmt_flag & BCFGPU_FMT_QS) fputs(":QS", LN);
+    if (indiv) {
+        fputc(0, LN); fflush(LN);
+        if (vio_write_record_indiv(fout, hdr, ln_buf, indiv, l_indiv)) { fprintf(stderr, "%s\n", vio_error()); exit(1); }
+        rewind(LN);
+        ++n_dev_records;
+        return;
+    }
     const int x = na * (na + 1) / 2;
     const size_t Ss = (size_t)S;
     /* the samples' columns go to the writer as integer arrays, one per FORMAT key in the order of the keys above (a printf call
@@ -853,7 +869,16 @@ static void print_record(const char *contig, int pos1, const char *alleles, cons
 
 /* bcfgpu_mpileup over a tile; the site records and the planes come back to the host.  keep_*: the device copies of the
  * site records / PL / DP4 stay allocated for the caller (--gvcf works on them), else they are freed. */
-static void run_mpileup(bcfgpu_ctx *ctx, const bcfgpu_tile *tile, int n, bcfgpu_site **site, planes_t *pp, void **keep_site, void **keep_pl, void **keep_dp4)
+/* dev != NULL (--device-records): only the site records come back; the planes stay in HBM for bcfgpu_mplp_encode_bcf (and --gvcf) and
+ * are the caller's to free (mplp_out_free) */
+static void mplp_out_free(bcfgpu_ctx *ctx, bcfgpu_mplp_out *mo)
+{
+    bcfgpu_free(ctx, mo->site); bcfgpu_free(ctx, mo->pl); bcfgpu_free(ctx, mo->dp4); bcfgpu_free(ctx, mo->adf); bcfgpu_free(ctx, mo->adr);
+    bcfgpu_free(ctx, mo->qs); bcfgpu_free(ctx, mo->scr); bcfgpu_free(ctx, mo->sp);
+    memset(mo, 0, sizeof *mo);
+}
+static void run_mpileup(bcfgpu_ctx *ctx, const bcfgpu_tile *tile, int n, bcfgpu_site **site, planes_t *pp, void **keep_site, void **keep_pl, void **keep_dp4,
+                        bcfgpu_mplp_out *dev)
 {
     void *d[8]; uint8_t *h[8];
     bcfgpu_mplp_out mo; memset(&mo, 0, sizeof mo);
@@ -865,6 +890,16 @@ static void run_mpileup(bcfgpu_ctx *ctx, const bcfgpu_tile *tile, int n, bcfgpu_
     mo.site = d[0]; mo.pl = d[1]; mo.dp4 = d[2]; mo.adf = d[3]; mo.adr = d[4]; mo.qs = d[5]; mo.scr = d[6]; mo.sp = d[7];
     CHECK(bcfgpu_mpileup(ctx, tile, &mo));
     CHECK(bcfgpu_sync(ctx));
+    if (dev) {
+        const size_t nb = bcfgpu_mplp_out_bytes(ctx, n, 0);
+        *site = malloc(nb ? nb : 1);
+        CHECK(bcfgpu_memcpy_d2h(ctx, *site, d[0], nb));
+        CHECK(bcfgpu_sync(ctx));
+        memset(pp, 0, sizeof *pp);
+        *dev = mo;
+        if (keep_site) { *keep_site = d[0]; *keep_pl = d[1]; *keep_dp4 = d[2]; }
+        return;
+    }
     for (int w = 0; w < 8; ++w) {
         const size_t nb = bcfgpu_mplp_out_bytes(ctx, n, w);
         h[w] = malloc(nb ? nb : 1);
@@ -877,6 +912,26 @@ static void run_mpileup(bcfgpu_ctx *ctx, const bcfgpu_tile *tile, int n, bcfgpu_
     for (int w = 3; w < 8; ++w) bcfgpu_free(ctx, d[w]);
     if (keep_site) { *keep_site = d[0]; *keep_pl = d[1]; *keep_dp4 = d[2]; }
     else { bcfgpu_free(ctx, d[0]); bcfgpu_free(ctx, d[1]); bcfgpu_free(ctx, d[2]); }
+}
+
+/* The per-sample blocks of a tile's records from the planes in HBM: the size pass tells how many bytes, the second call writes them.
+ * emit: HOST [n], which sites have a record.  rec / off: HOST, malloc'ed: the blocks back to back, and where each starts. */
+static void encode_records(bcfgpu_ctx *ctx, int n, const bcfgpu_mplp_out *mo, const uint8_t *emit, uint8_t **rec, uint64_t **off)
+{
+    void *d_emit, *d_off, *d_buf = NULL; uint64_t nb = 0;
+    CHECK(bcfgpu_malloc(ctx, (size_t)n + 1, &d_emit)); CHECK(bcfgpu_malloc(ctx, ((size_t)n + 1) * 8, &d_off));
+    CHECK(bcfgpu_memcpy_h2d(ctx, d_emit, emit, (size_t)n));
+    const int rc = bcfgpu_mplp_encode_bcf(ctx, n, mo, dr_key, d_emit, NULL, 0, d_off, &nb);
+    if (rc && rc != BCFGPU_E_RANGE) { fprintf(stderr, "bcfgpu_mplp_encode_bcf: %s (%d)\n", bcfgpu_last_error(), rc); exit(1); }
+    if (nb) {
+        CHECK(bcfgpu_malloc(ctx, nb, &d_buf));
+        CHECK(bcfgpu_mplp_encode_bcf(ctx, n, mo, dr_key, d_emit, d_buf, nb, d_off, &nb));
+    }
+    *rec = malloc(nb ? nb : 1); *off = malloc(((size_t)n + 1) * 8);
+    if (nb) CHECK(bcfgpu_memcpy_d2h(ctx, *rec, d_buf, nb));
+    CHECK(bcfgpu_memcpy_d2h(ctx, *off, d_off, ((size_t)n + 1) * 8));
+    CHECK(bcfgpu_sync(ctx));
+    bcfgpu_free(ctx, d_emit); bcfgpu_free(ctx, d_off); if (d_buf) bcfgpu_free(ctx, d_buf);
 }
 
 /* ---- options (file scope: the tile loop and its helpers read them) ---- */
@@ -962,6 +1017,7 @@ typedef struct {
     bcfgpu_site *site, *isite; planes_t snp_planes, ind_planes;
     int32_t *g_types, *g_maxins, *g_indelreg, *g_support; float *g_frac; int8_t *g_inscns;
     int32_t *gv_blk, *gv_dp; bcfgpu_gvcf_block *gv_block; uint8_t *gv_pl;
+    uint8_t *snp_rec, *ind_rec; uint64_t *snp_off, *ind_off;      /* --device-records: the records' per-sample blocks instead of the planes */
 } emit_job_t;
 static void emit_tile(emit_job_t *J)
 {
@@ -971,6 +1027,7 @@ static void emit_tile(emit_job_t *J)
     bcfgpu_site *site = J->site, *isite = J->isite; planes_t snp_planes = J->snp_planes, ind_planes = J->ind_planes;
     int32_t *g_types = J->g_types, *g_maxins = J->g_maxins, *g_indelreg = J->g_indelreg, *g_support = J->g_support; float *g_frac = J->g_frac; int8_t *g_inscns = J->g_inscns;
     int32_t *gv_blk = J->gv_blk, *gv_dp = J->gv_dp; bcfgpu_gvcf_block *gv_block = J->gv_block; uint8_t *gv_pl = J->gv_pl;
+    const uint8_t *snp_rec = J->snp_rec, *ind_rec = J->ind_rec; const uint64_t *snp_off = J->snp_off, *ind_off = J->ind_off;
     /* ---- the record loop: the SNP record of a column, then its indel record (mpileup.c:343-366) ---- */
     static const char *nt = "ACGTN";
     int jl = 0;
@@ -1004,7 +1061,7 @@ static void emit_tile(emit_job_t *J)
         }
         if (c->n_alleles < 2) als[o++] = '.';
         als[o] = 0;
-        print_record(contig, t0 + k + 1, als, "", c, &snp_planes, (size_t)k, S);
+        print_record(contig, t0 + k + 1, als, "", c, &snp_planes, (size_t)k, S, snp_rec ? snp_rec + snp_off[k] : NULL, snp_rec ? (size_t)(snp_off[k + 1] - snp_off[k]) : 0);
         }
         while (jl < nlive && cand[live[jl]] < k) ++jl;
         if (jl < nlive && cand[live[jl]] == k && isite[jl].ret == 0) {      /* (site jl of the indel tile = the jl-th candidate with ret == 0) */
@@ -1027,7 +1084,7 @@ static void emit_tile(emit_job_t *J)
             }
             txt[t] = 0;
             snprintf(prefix, sizeof prefix, "INDEL;IDV=%d;IMF=%g;", g_support[i], (double)g_frac[i]);
-            print_record(contig, p + 1, txt, prefix, &isite[jl], &ind_planes, (size_t)jl, S);
+            print_record(contig, p + 1, txt, prefix, &isite[jl], &ind_planes, (size_t)jl, S, ind_rec ? ind_rec + ind_off[jl] : NULL, ind_rec ? (size_t)(ind_off[jl + 1] - ind_off[jl]) : 0);
             free(txt);
         }
     }
@@ -1037,6 +1094,7 @@ static void emit_tile(emit_job_t *J)
     free(col_n); free(col_indel); free(cand); free(live);
     free(g_types); free(g_maxins); free(g_indelreg); free(g_support); free(g_frac); free(g_inscns);
     free(gv_blk); free(gv_block); free(gv_dp); free(gv_pl);
+    free(J->snp_rec); free(J->snp_off); free(J->ind_rec); free(J->ind_off);
     if (want_timing) t_emit += now_s() - tw1;
 }
 
@@ -1213,8 +1271,9 @@ static void tile_device(tilejob_t *T, int adopted)
     void *d_site = NULL, *d_pl = NULL, *d_dp4 = NULL;
     bcfgpu_site *site = NULL;
     planes_t snp_planes;
-    run_mpileup(ctx, &tile, n_sites, &site, &snp_planes, gv_n ? &d_site : NULL, &d_pl, &d_dp4);
-    if (nlive) run_mpileup(ctx, &ti, nlive, &isite, &ind_planes, NULL, NULL, NULL);
+    bcfgpu_mplp_out snp_dev, ind_dev; memset(&snp_dev, 0, sizeof snp_dev); memset(&ind_dev, 0, sizeof ind_dev);
+    run_mpileup(ctx, &tile, n_sites, &site, &snp_planes, gv_n ? &d_site : NULL, &d_pl, &d_dp4, dr_on ? &snp_dev : NULL);
+    if (nlive) run_mpileup(ctx, &ti, nlive, &isite, &ind_planes, NULL, NULL, NULL, dr_on ? &ind_dev : NULL);
     free(gret);
 
     /* ---- --gvcf: reference-only records collapse into blocks (gvcf_write, gvcf.c:88-226) on the planes still in HBM ---- */
@@ -1244,7 +1303,27 @@ static void tile_device(tilejob_t *T, int adopted)
         if (gv_blk[n_sites - 1] >= 0 && !(brk[n_sites - 1] & 1)) open_block = gv_blk[n_sites - 1];
         bcfgpu_free(ctx, d_pos); bcfgpu_free(ctx, d_brk); bcfgpu_free(ctx, d_blk); bcfgpu_free(ctx, d_min); bcfgpu_free(ctx, d_block);
         bcfgpu_free(ctx, d_gdp); bcfgpu_free(ctx, d_gpl); free(pos); free(brk);
-        bcfgpu_free(ctx, d_site); bcfgpu_free(ctx, d_pl); bcfgpu_free(ctx, d_dp4);
+        if (!dr_on) { bcfgpu_free(ctx, d_site); bcfgpu_free(ctx, d_pl); bcfgpu_free(ctx, d_dp4); }       /* (--device-records: freed with the other planes below) */
+    }
+
+    /* ---- --device-records: which sites get a record is what the record loop of emit_tile decides -- not a column without reads, outside
+     * the targets or inside a gVCF block; an indel site where bcf_call_combine found an ALT allele -- and their per-sample blocks come
+     * to the host as BCF2 bytes ---- */
+    uint8_t *snp_rec = NULL, *ind_rec = NULL; uint64_t *snp_off = NULL, *ind_off = NULL;
+    if (dr_on) {
+        uint8_t *se = calloc((size_t)n_sites + 1, 1), *ie = calloc((size_t)nlive + 1, 1);
+        int jl = 0;
+        for (int k = 0; k < n_sites; ++k) {
+            if (col_n[k] == 0 || !target_keeps_column(contig, t0 + k)) continue;
+            se[k] = !(gv_blk && gv_blk[k] >= 0);
+            while (jl < nlive && cand[live[jl]] < k) ++jl;
+            if (jl < nlive && cand[live[jl]] == k && isite[jl].ret == 0) ie[jl] = 1;
+        }
+        encode_records(ctx, n_sites, &snp_dev, se, &snp_rec, &snp_off);
+        if (nlive) encode_records(ctx, nlive, &ind_dev, ie, &ind_rec, &ind_off);
+        free(se); free(ie);
+        mplp_out_free(ctx, &snp_dev);
+        if (nlive) mplp_out_free(ctx, &ind_dev);
     }
 
     /* ---- the records: handed to the writer (emit_tile), which runs beside the next tile's device stages ---- */
@@ -1255,6 +1334,7 @@ static void tile_device(tilejob_t *T, int adopted)
         J.col_n = col_n; J.col_indel = col_indel; J.cand = cand; J.live = live; J.site = site; J.isite = isite; J.snp_planes = snp_planes; J.ind_planes = ind_planes;
         J.g_types = g_types; J.g_maxins = g_maxins; J.g_indelreg = g_indelreg; J.g_support = g_support; J.g_frac = g_frac; J.g_inscns = g_inscns;
         J.gv_blk = gv_blk; J.gv_dp = gv_dp; J.gv_block = gv_block; J.gv_pl = gv_pl;
+        J.snp_rec = snp_rec; J.snp_off = snp_off; J.ind_rec = ind_rec; J.ind_off = ind_off;
         emit_submit(&J);
     }
 }
@@ -1435,7 +1515,7 @@ static int run_shards(int n_gpus, int argc0, char **argv0, int first_file, const
             if (!strcmp(o, "-o")) { char *e; strtol(argv0[i + 1], &e, 10); if (*e) { ++i; continue; } }
             if (o[0] != '-') break;                              /* the positional form: ref.fa contig beg end come from -f / -r below */
             av[n++] = argv0[i];
-            if (o[0] == '-' && i + 1 < first_file && argv0[i + 1][0] != '-' && strcmp(o, "-B") && strcmp(o, "-E") && strcmp(o, "-A") && strcmp(o, "-p") && strcmp(o, "-I") && strcmp(o, "-6") && strcmp(o, "--illumina1.3+") && strcmp(o, "--timing") && strcmp(o, "--prefetch") && strcmp(o, "-x") && strcmp(o, "--ignore-overlaps") && strcmp(o, "--no-version")
+            if (o[0] == '-' && i + 1 < first_file && argv0[i + 1][0] != '-' && strcmp(o, "-B") && strcmp(o, "-E") && strcmp(o, "-A") && strcmp(o, "-p") && strcmp(o, "-I") && strcmp(o, "-6") && strcmp(o, "--illumina1.3+") && strcmp(o, "--timing") && strcmp(o, "--prefetch") && strcmp(o, "--device-records") && strcmp(o, "-x") && strcmp(o, "--ignore-overlaps") && strcmp(o, "--no-version")
                 && strcmp(o, "--ignore-RG") && strcmp(o, "--list-samples")) av[n++] = argv0[++i];
         }
         av[n++] = "-f"; av[n++] = (char *)ref_path; av[n++] = "-r"; av[n++] = rl;
@@ -1563,6 +1643,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[1], "--threads")) { argv += 2; argc -= 2; }                                                      /* (the output's compression threads: nothing to do here) */
         else if (!strcmp(argv[1], "--timing")) { want_timing = 1; argv += 1; argc -= 1; }
         else if (!strcmp(argv[1], "--prefetch")) { prefetch = 1; argv += 1; argc -= 1; }
+        else if (!strcmp(argv[1], "--device-records")) { device_records = 1; argv += 1; argc -= 1; }
         else if (!strcmp(argv[1], "--tile")) { tile_cols = atoi(argv[2]); if (tile_cols < 1) DIE("--tile: at least one column\n"); argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-d")) { max_depth = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-s")) { add_samples(argv[2], 0); argv += 2; argc -= 2; }            /* mpileup.c:1058-1059,1087,1016 */
@@ -1727,6 +1808,12 @@ int main(int argc, char **argv)
         if (!fout || vio_write_hdr(fout, hdr)) DIE("%s\n", vio_error());
         LN = open_memstream(&ln_buf, &ln_len);
         if (!LN) DIE("open_memstream failed\n");
+        /* --device-records: BCF output only (text is formatted from the planes on the host) */
+        dr_on = device_records && (out_mode == 'u' || out_mode == 'b');
+        if (dr_on) {
+            static const char *key[BCFGPU_BCF_NKEYS] = { "PL", "DP", "DV", "SP", "DP4", "ADF", "ADR", "AD", "DPR", "SCR", "QS" };
+            for (int i = 0; i < BCFGPU_BCF_NKEYS; ++i) { dr_key[i] = vio_hdr_fmt_id(hdr, key[i]); if (dr_key[i] < 0) dr_key[i] = 0; }     /* (a key the flags do not select is not read) */
+        }
     }
 
     /* ---- the regions, one after the other (mpileup.c:652-683), each streamed through in tiles of tile_cols columns: the files
@@ -1850,6 +1937,7 @@ int main(int argc, char **argv)
     fprintf(stderr, "%llu reads of %d samples, %llu overlapping pairs, %llu pileup entries in %llu columns (%d tiles of <= %d)\n",
             n_reads_tot, S, tot_pairs, tot_entries, n_cols_tot, n_tiles, tile_cols);
     if (want_timing) fprintf(stderr, "[bcfgpu_sam] seconds: reading and parsing the files %.3f, tile pools %.3f, device stages %.3f, writing records %.3f, waiting in bcfgpu_pool_adopt %.3f\n", t_read, t_pool, t_dev, t_emit, t_adopt);
+    if (want_timing) fprintf(stderr, "[bcfgpu_sam] device records: %llu records with their FORMAT block encoded on the device\n", n_dev_records);
     if (vio_close(fout)) DIE("%s\n", vio_error());
     if (ctx) bcfgpu_destroy(ctx);
     if (cap_ctx) bcfgpu_destroy(cap_ctx);
@@ -1858,7 +1946,7 @@ int main(int argc, char **argv)
 usage:
     fprintf(stderr, "usage: bcfgpu_sam [-a TAG,..] [--gvcf INT,..] [-O v|z|u|b] [-o out] [-d INT] [-s LIST | -S FILE] [-G FILE] [--ignore-RG]\n"
                     "                  [-B | -E] [-6] [-x] [-A] [-q INT] [-Q INT] [-C INT] [--ff INT] [--rf INT] [-I] [-o INT] [-e INT] [-h INT] [-m INT] [-F FLOAT] [-p] [-L INT]\n"
-                    "                  [--tile COLUMNS] [--gpus N] [--prefetch]\n"
+                    "                  [--tile COLUMNS] [--gpus N] [--prefetch] [--device-records]\n"
                     "                  -f ref.fa [-r CHR[:BEG[-END]],... | -R FILE] [-b FILE] file.sam|file.bam [...]      (as `bcftools mpileup`)\n"
                     "              or  ref.fa contig beg end file.sam|file.bam [...]                    (beg, end 1-based inclusive)\n");
     return 2;

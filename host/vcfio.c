@@ -419,7 +419,9 @@ static int count_char(const char *s, size_t n, char c) { int k = 0; for (size_t 
 /* one VCF text record -> BCF2 (l_shared, l_indiv, shared, indiv) appended to `out` */
 /* vals != NULL: the per-sample columns are not in `line` (which ends with the FORMAT keys) but in integer arrays, n_keys of them,
  * vals[k][s * width[k] + j] (vio_write_record_int) */
-static int encode_record(const vio_hdr *h, const char *line, sbuf *out, int n_keys, const int *width, const int32_t *const *vals)
+/* indiv != NULL: the per-sample part is encoded already (vio_write_record_indiv): its l_indiv bytes follow the shared part as they are */
+static int encode_record(const vio_hdr *h, const char *line, sbuf *out, int n_keys, const int *width, const int32_t *const *vals,
+                         const void *indiv, size_t l_indiv)
 {
     const char *fld[10]; size_t fl[10]; int nf = 0;
     const char *p = line;
@@ -478,7 +480,7 @@ static int encode_record(const vio_hdr *h, const char *line, sbuf *out, int n_ke
     int n_fmt = 0, n_sample = 0;
     /* FORMAT keys */
     int fkey[64];
-    if (nf == 9 && (samples || vals) && h->n_smpl) {
+    if (nf == 9 && (samples || vals || indiv) && h->n_smpl) {
         n_sample = h->n_smpl;
         const char *q = fld[8], *qe = fld[8] + fl[8];
         while (q < qe && n_fmt < 64) {
@@ -511,7 +513,8 @@ static int encode_record(const vio_hdr *h, const char *line, sbuf *out, int n_ke
     }
     sb_put(&sh, inf.s ? inf.s : "", inf.l);
     free(inf.s);
-    if (n_fmt && vals) {
+    if (indiv) { if (n_fmt) sb_put(&in, indiv, l_indiv); }
+    else if (n_fmt && vals) {
         /* per-sample fields from the caller's arrays: what the text path below would have parsed out of the line */
         const int S = n_sample;
         if (n_fmt != n_keys) { free(sh.s); return fail("%d FORMAT keys, %d columns of values", n_fmt, n_keys); }
@@ -730,14 +733,14 @@ int vio_write_line(vio_file *f, const vio_hdr *h, const char *line)
 {
     if (!f->bcf) return out_bytes(f, line, strlen(line)) || out_bytes(f, "\n", 1);
     f->rec.l = 0;
-    if (encode_record(h, line, &f->rec, 0, NULL, NULL)) return -1;
+    if (encode_record(h, line, &f->rec, 0, NULL, NULL, NULL, 0)) return -1;
     return out_bytes(f, f->rec.s, f->rec.l);
 }
 int vio_write_record_int(vio_file *f, const vio_hdr *h, const char *head, int n_keys, const int *width, const int32_t *const *vals)
 {
     f->rec.l = 0;
     if (f->bcf) {
-        if (encode_record(h, head, &f->rec, n_keys, width, vals)) return -1;
+        if (encode_record(h, head, &f->rec, n_keys, width, vals, NULL, 0)) return -1;
         return out_bytes(f, f->rec.s, f->rec.l);
     }
     /* VCF text: the head, then every sample's columns (a vector ends at VIO_INT_VEND; an empty one and a missing value are '.');
@@ -766,6 +769,19 @@ int vio_write_record_int(vio_file *f, const vio_hdr *h, const char *head, int n_
         f->rec.l = (size_t)(o - f->rec.s);
     }
     sb_putc(&f->rec, '\n');
+    return out_bytes(f, f->rec.s, f->rec.l);
+}
+int vio_hdr_fmt_id(const vio_hdr *h, const char *id)
+{
+    const int d = dict_find(h, id, strlen(id));
+    return d >= 0 && h->dict[d].fmt_type != T_NONE ? d : -1;
+}
+int vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, const void *indiv, size_t l_indiv)
+{
+    if (!f->bcf) return fail("a ready per-sample block can only go into a BCF file");
+    if (!indiv) return fail("no per-sample block");
+    f->rec.l = 0;
+    if (encode_record(h, head, &f->rec, 0, NULL, NULL, indiv, l_indiv)) return -1;
     return out_bytes(f, f->rec.s, f->rec.l);
 }
 int vio_read_line(vio_file *f, const vio_hdr *h, char **line, size_t *cap)

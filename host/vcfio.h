@@ -42,6 +42,13 @@ int  vio_write_line(vio_file *f, const vio_hdr *h, const char *line);   /* one V
 #define VIO_INT_MISSING INT32_MIN
 #define VIO_INT_VEND    (INT32_MIN + 1)
 int  vio_write_record_int(vio_file *f, const vio_hdr *h, const char *head, int n_keys, const int *width, const int32_t *const *vals);
+/* The dictionary index encode_record writes for FORMAT key `id` (what a device-side encoder puts in front of the key's values), or -1
+ * when the header declares no such FORMAT key. */
+int  vio_hdr_fmt_id(const vio_hdr *h, const char *id);
+/* A BCF record whose per-sample part is encoded already (bcfgpu_mplp_encode_bcf): `head` as for vio_write_record_int -- the shared part
+ * is encoded from it as for every other record, n_fmt being the number of keys in its FORMAT column and n_sample the header's --, then
+ * the l_indiv bytes of `indiv` as they are.  BCF output only: -1 on a text file. */
+int  vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, const void *indiv, size_t l_indiv);
 vio_file *vio_open_read(const char *path);                      /* path "-" = stdin; VCF, bgzipped VCF or BCF2, detected */
 vio_hdr *vio_read_hdr(vio_file *f);
 int  vio_read_line(vio_file *f, const vio_hdr *h, char **line, size_t *cap);   /* 1: a record (as VCF text) in *line, 0: end, <0: error */

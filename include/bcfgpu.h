@@ -25,6 +25,8 @@
  *    bcfgpu_mcall                        <- mcall()                            call.h:131 (mcall.c:1430-1684)
  *                                           incl. the per-record prologue of vcfcall.c:1096-1115
  *    bcfgpu_pipeline                     <- the `mpileup -Ou | call -m` pipe with PL/QS/I16 kept in HBM
+ *    bcfgpu_mplp_encode_bcf              <- the bcf_update_format_int32 calls of bcf_call2bcf (bam2bcf.c:845-903) and the typed-value
+ *                                           encoding bcf_write does to them: the per-sample part of an mpileup record as BCF2 bytes
  *
  *  Memory model: all bulk arrays are *device* pointers (HBM).  Hosts that do
  *  not link HIP use bcfgpu_malloc/free/memcpy_*.  Kernels are enqueued on the
@@ -653,6 +655,35 @@ int  bcfgpu_compact_calls(bcfgpu_ctx *ctx, int32_t n_sites, int32_t site0, const
 int  bcfgpu_compact_calls_async(bcfgpu_ctx *ctx, int32_t n_sites, int32_t site0, const bcfgpu_site *msite, const bcfgpu_call_out *cout,
                                 int32_t n_gt_planes, int32_t variants_only, void *d_buf, uint64_t cap_bytes, uint64_t *d_counts);
 int  bcfgpu_compact_counts(bcfgpu_ctx *ctx, const uint64_t *d_counts, uint64_t *n_bytes, uint32_t *n_rec);
+
+/* ---- mpileup records as BCF2 bytes: the per-sample ("indiv") part of every record of a tile, ready for the writer -------------
+ * `bcftools mpileup` writes a record for every column.  bcf_call2bcf fills its FORMAT fields with bcf_update_format_int32
+ * (bam2bcf.c:845-903: PL, then DP, DV, SP, DP4, ADF, ADR, AD, DPR, SCR, QS under their flags), sample-major int32 arrays that
+ * bcf_write narrows while encoding.  Here that is done on the planes in HBM, and what leaves the device is the bytes.
+ * Per key, by the typed-value rules of the BCF2 specification (section 6.3.3; host/vcfio.c enc_int1 / enc_size / enc_vint follow
+ * the same rules):
+ *     typed key id    0x11 id (id <= 127), 0x12 and two bytes (<= 32767), else 0x13 and four bytes, little-endian
+ *     descriptor      width << 4 | type for width < 15, else 0xF0 | type, 0x11, width (PL of five alleles: 15)
+ *     values          n_smpl x width integers, value[sample][j], little-endian, of type int8 (1) when the largest of them at this
+ *                     site is <= 127, int16 (2) when <= 32767, else int32 (3).  All values are >= 0; no sentinel occurs
+ * Widths with na = site[k].n_alleles: PL na(na+1)/2; DP, DV, SP, SCR 1; DP4 4; ADF, ADR, AD, DPR, QS na.  Values: the planes of the
+ * same name; DP = the sum of the four DP4 planes, DV = DP4 planes 2 + 3, AD = DPR = ADF + ADR.
+ *   planes   DEVICE, the mpileup stage's output for the tile; the keys written are PL and those the context's cfg.fmt_flag selects
+ *            (BCFGPU_FMT_*), in the order above; a plane no selected key reads may be NULL and is not read
+ *   key_id   HOST, indexed by BCFGPU_BCF_*: the keys' indices in the writer's header dictionary (only the selected keys' are read)
+ *   d_emit   DEVICE [n_sites], 0 = the site has no record; NULL = every site has one
+ *   d_buf    DEVICE, cap_bytes: the blocks of the emitted sites back to back in site order, each starting at whatever byte the one
+ *            before ended
+ *   d_off    DEVICE [n_sites + 1], 8-byte aligned: d_off[k] = the start of site k's block, d_off[n_sites] = the size of all; a
+ *            site without a record has d_off[k + 1] == d_off[k].  Set whether or not the blocks fit
+ *   n_bytes  HOST, out: the size of all blocks
+ * When the blocks do not fit cap_bytes nothing is written to d_buf, *n_bytes is the size needed and the call returns
+ * BCFGPU_E_RANGE: a caller may ask with cap_bytes = 0 first, or grow its buffer and call again.  n_sites == 0 is valid.
+ * Runs on the context's stream and synchronises it. */
+enum { BCFGPU_BCF_PL, BCFGPU_BCF_DP, BCFGPU_BCF_DV, BCFGPU_BCF_SP, BCFGPU_BCF_DP4, BCFGPU_BCF_ADF, BCFGPU_BCF_ADR,
+       BCFGPU_BCF_AD, BCFGPU_BCF_DPR, BCFGPU_BCF_SCR, BCFGPU_BCF_QS, BCFGPU_BCF_NKEYS };
+int  bcfgpu_mplp_encode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, const bcfgpu_mplp_out *planes, const int32_t key_id[BCFGPU_BCF_NKEYS],
+                            const uint8_t *d_emit, void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
 
 /* One communicator over the contexts of a node, rank i = ctxs[i] (RCCL ncclCommInitAll; every context on its own device;
  * librccl is loaded at this call, a single context needs none). */

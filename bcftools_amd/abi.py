@@ -164,6 +164,14 @@ class GapStats(C.Structure):
                 ("n_wide", C.c_uint64), ("n_scratch", C.c_uint64), ("band_jobs", C.c_uint32 * 8)]
 
 
+class BcfVec(C.Structure):
+    """bcfgpu_bcf_vec: where one FORMAT key's values of a BCF record lie in the per-sample bytes."""
+    _fields_ = [("off", C.c_uint64), ("type", C.c_int32), ("width", C.c_int32)]
+
+
+BCF_VEC = [("off", "<u8"), ("type", "<i4"), ("width", "<i4")]       # the same as a numpy record
+
+
 class Timing(C.Structure):
     _fields_ = [("glfgen_ms", C.c_float), ("combine_ms", C.c_float),
                 ("mcall_ms", C.c_float), ("total_ms", C.c_float)]
@@ -232,6 +240,8 @@ PROTOTYPES = {
     "bcfgpu_compact_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "bcfgpu_mplp_encode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MplpOut), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bcfgpu_call_decode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(BcfVec), C.POINTER(C.c_int32),
+                                         C.c_int32, C.c_void_p]),
     "bcfgpu_comm_init_all": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
     "bcfgpu_comm_destroy": (None, [C.c_void_p]),
     "bcfgpu_gather_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

@@ -83,13 +83,15 @@ enum WsSlot : int {
     WS_COMPACT_SIZE = 35, WS_COMPACT_SCAN_TMP = 36, WS_COMPACT_COUNTS = 37,
     // bcfgpu_mplp_encode_bcf (bcfenc.hip): scratch for one call -- the keys' integer types per site, the scan's temporary storage
     WS_COMPACT_BCF_TYPES = 167, WS_COMPACT_BCF_SCAN_TMP = 168,
+    // bcfgpu_call_decode_bcf (bcfdec.hip): scratch for one call -- the uploaded copies of the records' vectors and of the sample map
+    WS_COMPACT_BCFDEC_VEC = 169, WS_COMPACT_BCFDEC_COL = 170,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_COMPACT_BCF_SCAN_TMP + 1    // one past the highest slot
+    WS_COUNT = WS_COMPACT_BCFDEC_COL + 1      // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names

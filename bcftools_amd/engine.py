@@ -336,6 +336,33 @@ class Context:
             self.release(bufs)
         return data, offs
 
+    def decode_bcf(self, indiv, vec, n_smpl_in, n_planes, col=None):
+        """bcfgpu_call_decode_bcf: one FORMAT key's vectors of BCF records as int32 planes.  indiv: the records' per-sample blocks
+        (bytes or np.uint8), uploaded here; vec: per record (off, type, width), a sequence of triples or an array of abi.BCF_VEC;
+        col: the input sample of each of the context's n_smpl called samples, or None.  Returns np.int32 [n_sites, n_planes, n_smpl]."""
+        indiv = np.frombuffer(bytes(indiv), np.uint8) if isinstance(indiv, (bytes, bytearray)) else np.ascontiguousarray(indiv, np.uint8)
+        v = np.zeros(len(vec), dtype=abi.BCF_VEC)
+        if len(vec):
+            a = np.asarray(vec)
+            if a.dtype.names:
+                v[:] = a
+            else:
+                v["off"], v["type"], v["width"] = [[int(x[i]) for x in vec] for i in range(3)]
+        n, S = len(v), self.cfg.n_smpl
+        c = None if col is None else np.ascontiguousarray(col, np.int32)
+        assert c is None or len(c) == S
+        out = np.zeros((n, n_planes, S), np.int32)
+        bufs = [self.to_device(indiv), self.buf(out.nbytes)]
+        try:
+            check(self.L.bcfgpu_call_decode_bcf(self.h, n, n_smpl_in, bufs[0].ptr if indiv.nbytes else None, indiv.nbytes,
+                                                v.ctypes.data_as(C.POINTER(abi.BcfVec)), None if c is None else c.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                n_planes, bufs[1].ptr))
+            if out.nbytes:
+                bufs[1].download(out)
+        finally:
+            self.release(bufs)
+        return out
+
     def timing(self, on=True):
         check(self.L.bcfgpu_timing_enable(self.h, 1 if on else 0))
 

@@ -2,13 +2,19 @@
  *  include/bcfgpu.h: the record loop of main_vcfcall (vcfcall.c:1089-1148) with mcall() on the device.
  *
  *      bcfgpu_call [-v] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]]
- *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] <in.vcf>
+ *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--timing] <in.vcf>
  *          -S: the samples to keep, in that order: NAME [PLOIDY|SEX] per line, or a PED file (vcfcall.c:202-344)
  *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c)
  *          -G: sample groups with their own allele frequencies, '-' = every sample alone, or NAME GROUP lines
  *              (mcall.c:258-345); the frequencies come from FORMAT/QS or FORMAT/AD (--group-samples-tag)
  *          -F: INFO tags holding AN and AC of a prior population (mcall.c:1499-1520)
  *          -a: FORMAT/GQ and FORMAT/GP on called variant records (mcall.c:1618-1623)
+ *          --device-input: BCF input is not turned into text and back: the records' per-sample blocks go to the device as the file
+ *              holds them and bcfgpu_call_decode_bcf makes the PL (and, with -G, AD / QS) planes there; the sample columns become
+ *              text only for the records that are written.  Takes effect on BCF input without -C alleles and without -g (both read
+ *              the samples' values on the host); in any other run the option does nothing.  The same output either way.
+ *          --timing: one line of seconds on stderr (reading records, building the planes on the host, uploads and device stages,
+ *              writing records), and how many records' planes were decoded on the device
  *
  *  Host: VCF text in, what mcall() reads from a record (alleles, FORMAT/PL, INFO/QS, INFO/I16) packed into the planes of
  *  bcfgpu_call_in, one bcfgpu_mcall over all records, then what mcall.c:1627-1681 does to the record: alleles trimmed with
@@ -23,6 +29,7 @@
 #include <string.h>
 #include <strings.h>
 #include <stdint.h>
+#include <time.h>
 #include "bcfgpu.h"
 #include "vcfio.h"
 
@@ -31,7 +38,11 @@
 
 static FILE *LN; static char *ln_buf; static size_t ln_len;      /* the record being written: a memory stream, framed by vcfio */
 
-typedef struct { char *line; char **fld; int nfld; char **als; int nals, unseen, pl_idx, ad_idx; uint8_t *ploidy; } rec_t;
+/* with --device-input: line = the first nine columns, the per-sample block = ilen bytes at ioff of the byte buffer, its key headers in keys */
+typedef struct { char *line; char **fld; int nfld; char **als; int nals, unseen, pl_idx, ad_idx; uint8_t *ploidy;
+                 size_t ioff, ilen; int n_fmt, nkeys; vio_indiv_key *keys; } rec_t;
+
+static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 typedef struct { char chrom[256]; int from, to, ploidy; char sex[64]; } preg_t;
 
@@ -382,7 +393,8 @@ int main(int argc, char **argv)
         for (int i = 1; i < argc; ++i)
             for (size_t k = 0; k < sizeof alias / sizeof alias[0]; ++k) if (!strcmp(argv[i], alias[k][0])) argv[i] = (char *)alias[k][1];
     }
-    int varonly = 0, out_tags = 0, keepalt = 0;
+    int varonly = 0, out_tags = 0, keepalt = 0, dev_in = 0, want_timing = 0;
+    double t_read = 0., t_planes = 0., t_dev = 0., t_write = 0.;
     int acgt_only = 1, skip_kind = 0;                           /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
     const char *tgt_file = NULL; double prior = 1.1e-3;
     const char *smpl_file = NULL, *smpl_list = NULL, *ploidy_file = NULL, *ploidy_alias = NULL, *grp_arg = NULL, *grp_tag = NULL;
@@ -403,6 +415,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[1], "--threads") && argc > 3) { argv += 2; argc -= 2; }                                        /* (compression threads: nothing to do here) */
         else if (!strcmp(argv[1], "--no-version")) { ++argv; --argc; }                                                       /* (no ##bcftools_callVersion lines are written anyway) */
         else if (!strcmp(argv[1], "-i")) { insert_missed = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-input")) { dev_in = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--timing")) { want_timing = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "-C") && argc > 3) { if (strcmp(argv[2], "alleles")) DIE("-C: only `alleles` is supported\n"); cals = 1; argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-T") && argc > 3) { tgt_file = argv[2]; argv += 2; argc -= 2; }
         else if ((!strcmp(argv[1], "-t") || !strcmp(argv[1], "--targets") || !strcmp(argv[1], "-r") || !strcmp(argv[1], "--regions")) && argc > 3) {
@@ -456,7 +470,7 @@ int main(int argc, char **argv)
     }
     if (gv_n && varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (gv_n && cals) DIE("-g with -C alleles is not supported\n");
-    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
     /* ploidy definition (ploidy.c): regions per sex, '*' lines = the sex's default; the last sex named is the default sex */
     preg_t *preg = NULL; int npreg = 0; char last_sex[64] = "";
     char *alias_text = NULL;
@@ -504,6 +518,9 @@ int main(int argc, char **argv)
     if (!fin) DIE("%s\n", vio_error());
     vio_hdr *hdr = vio_read_hdr(fin);
     if (!hdr) DIE("%s\n", vio_error());
+    dev_in = dev_in && vio_is_bcf(fin) && !cals && !gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
+    unsigned char *ibuf = NULL; size_t ibuf_l = 0, ibuf_m = 0;   /* --device-input: the records' per-sample blocks, back to back */
+    const double t0 = now_s();
     char *buf = NULL; size_t bufcap = 0;
     rec_t *recs = NULL; int n = 0, cap = 0, S = -1, ngmax = 1, S_in = -1;
     int *col = NULL;                              /* output sample s = input column col[s] (bcf_subset with -S) */
@@ -542,7 +559,10 @@ int main(int argc, char **argv)
     if (cals) { if (!tgt_file) DIE("-C alleles needs -T targets\n"); tgt_parse(tgt_file); }
     else if (tgt_file) site_filter_file(tgt_file);           /* -T without -C alleles: the targets restrict the sites (vcfcall.c:612-617) */
     int rrc;
-    while ((rrc = vio_read_line(fin, hdr, &buf, &bufcap)) > 0) {
+    for (;;) {
+        const void *indiv = NULL; size_t l_indiv = 0; int n_fmt = 0, n_sample = 0;
+        rrc = dev_in ? vio_read_record(fin, hdr, &buf, &bufcap, &indiv, &l_indiv, &n_fmt, &n_sample) : vio_read_line(fin, hdr, &buf, &bufcap);
+        if (rrc <= 0) break;
         size_t l = strlen(buf);
         if (!l) continue;
         char *use = buf, *owned = NULL;
@@ -578,6 +598,15 @@ int main(int argc, char **argv)
         r->line = strdup(use);
         free(owned);
         r->fld = split(r->line, '\t', &r->nfld);
+        r->keys = NULL; r->nkeys = 0;
+        if (dev_in) {                                            /* the block joins the byte buffer; where its keys' values lie */
+            if (r->nfld != 9 || n_sample != S_in) DIE("malformed VCF\n");
+            if (ibuf_l + l_indiv > ibuf_m) { ibuf_m = (ibuf_l + l_indiv) * 2 + (1 << 20); ibuf = realloc(ibuf, ibuf_m); if (!ibuf) DIE("out of memory\n"); }
+            memcpy(ibuf + ibuf_l, indiv, l_indiv);
+            r->ioff = ibuf_l; r->ilen = l_indiv; r->n_fmt = n_fmt; ibuf_l += l_indiv;
+            r->keys = malloc((size_t)(n_fmt > 0 ? (n_fmt < 64 ? n_fmt : 64) : 1) * sizeof *r->keys);
+            if ((r->nkeys = vio_indiv_keys(hdr, indiv, l_indiv, n_fmt, n_sample, r->keys)) < 0) DIE("%s\n", vio_error());
+        } else
         if (S_in < 0 || r->nfld != 9 + S_in) DIE("malformed VCF\n");
         /* alleles; the unseen allele as vcfcall.c:1102-1111 finds it */
         int nalt = 0; char *alt = strdup(r->fld[4]), **alts = split(alt, ',', &nalt);
@@ -612,6 +641,7 @@ int main(int argc, char **argv)
     }
     if (rrc < 0) DIE("%s\n", vio_error());
     vio_close(fin);
+    t_read = now_s() - t0;
     if (cals && insert_missed) {                                 /* the targets behind the last record, then the sequences without any */
         if (prev_chrom) flush_region(prev_chrom, prev_pos0, 1L << 40);
         for (int x = 0; x < n_tgt; ++x) if (!tgt[tgt_sorted[x]].used) flush_region(tgt[tgt_sorted[x]].chrom, 0, 1L << 40);
@@ -647,29 +677,47 @@ int main(int argc, char **argv)
     for (int k = 0; k < n; ++k) if (recs[k].nals > namax) namax = recs[k].nals;
 
     /* ---- what mcall() reads from the records: PL planes (missing / vector_end kept), QS, I16 ---- */
+    const double t1 = now_s();
     int32_t *nals = malloc((size_t)n * 4), *unseen = malloc((size_t)n * 4);
-    int32_t *pl = malloc((size_t)n * ngmax * S * 4);
+    int32_t *pl = dev_in ? NULL : malloc((size_t)n * ngmax * S * 4);
+    /* --device-input: no host planes; per record where the PL vector (and the -G tag's) lies in the byte buffer */
+    const int want_ad = ngrp > 1;
+    bcfgpu_bcf_vec *vec_pl = dev_in ? calloc((size_t)n + 1, sizeof *vec_pl) : NULL, *vec_ad = dev_in && want_ad ? calloc((size_t)n + 1, sizeof *vec_ad) : NULL;
     float *qs = calloc((size_t)n * 5, 4), *i16 = calloc((size_t)n * 16, 4);
-    int32_t *ad = ngrp > 1 ? malloc((size_t)n * namax * S * 4) : NULL;
+    int32_t *ad = want_ad && !dev_in ? malloc((size_t)n * namax * S * 4) : NULL;
     int32_t *pan = prior_an_tag[0] ? malloc((size_t)n * 4) : NULL, *pac = prior_an_tag[0] ? malloc((size_t)n * 4 * 4) : NULL;
     const size_t l_pan = strlen(prior_an_tag), l_pac = strlen(prior_ac_tag);
     for (int k = 0; k < n; ++k) {
         rec_t *r = &recs[k];
         nals[k] = r->nals; unseen[k] = r->unseen;
-        for (size_t i = 0; i < (size_t)ngmax * S; ++i) pl[(size_t)k * ngmax * S + i] = BCFGPU_INT32_VECTOR_END;
+        if (pl) for (size_t i = 0; i < (size_t)ngmax * S; ++i) pl[(size_t)k * ngmax * S + i] = BCFGPU_INT32_VECTOR_END;
         if (ad) for (size_t i = 0; i < (size_t)namax * S; ++i) ad[(size_t)k * namax * S + i] = BCFGPU_INT32_VECTOR_END;
         if (pan) { pan[k] = BCFGPU_INT32_MISSING; for (int i = 0; i < 4; ++i) pac[(size_t)k * 4 + i] = BCFGPU_INT32_VECTOR_END; }
         /* FORMAT/PL */
-        int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
         r->pl_idx = r->ad_idx = -1;
-        for (int i = 0; i < nk; ++i) {
-            if (!strcmp(keys[i], "PL")) r->pl_idx = i;
-            if (ad && !strcmp(keys[i], grp_tag)) r->ad_idx = i;
+        if (dev_in) {
+            for (int i = 0; i < r->nkeys; ++i) {
+                if (!strcmp(r->keys[i].id, "PL")) r->pl_idx = i;
+                if (want_ad && !strcmp(r->keys[i].id, grp_tag)) r->ad_idx = i;
+            }
+        } else {
+            int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
+            for (int i = 0; i < nk; ++i) {
+                if (!strcmp(keys[i], "PL")) r->pl_idx = i;
+                if (want_ad && !strcmp(keys[i], grp_tag)) r->ad_idx = i;
+            }
+            free(keys); free(fmt);
         }
-        free(keys); free(fmt);
         if (r->pl_idx < 0) DIE("no FORMAT/PL at %s:%s\n", r->fld[0], r->fld[1]);
-        if (ad && r->ad_idx < 0) DIE("FORMAT/%s is required with -G (%s:%s)\n", grp_tag, r->fld[0], r->fld[1]);     /* mcall.c:1476 */
-        for (int s = 0; s < S; ++s) {
+        if (want_ad && r->ad_idx < 0) DIE("FORMAT/%s is required with -G (%s:%s)\n", grp_tag, r->fld[0], r->fld[1]);     /* mcall.c:1476 */
+        if (dev_in) {
+            const vio_indiv_key *kp = &r->keys[r->pl_idx], *ka = want_ad ? &r->keys[r->ad_idx] : NULL;
+            if (kp->type < 1 || kp->type > 3) DIE("FORMAT/PL is not an integer vector at %s:%s\n", r->fld[0], r->fld[1]);
+            if (ka && (ka->type < 1 || ka->type > 3)) DIE("FORMAT/%s is not an integer vector at %s:%s\n", grp_tag, r->fld[0], r->fld[1]);
+            vec_pl[k].off = r->ioff + kp->off; vec_pl[k].type = kp->type; vec_pl[k].width = kp->width;
+            if (ka) { vec_ad[k].off = r->ioff + ka->off; vec_ad[k].type = ka->type; vec_ad[k].width = ka->width; }
+        }
+        for (int s = 0; s < S && !dev_in; ++s) {
             char *smp = strdup(r->fld[9 + col[s]]); int nv; char **vals = split(smp, ':', &nv);
             if (r->pl_idx < nv) {
                 int np; char **pv = split(vals[r->pl_idx], ',', &np);
@@ -708,7 +756,10 @@ int main(int argc, char **argv)
         free(iv); free(info);
     }
 
+    t_planes = now_s() - t1;
+
     /* ---- the device ---- */
+    const double t2 = now_s();
     bcfgpu_cfg cfg; memset(&cfg, 0, sizeof cfg);
     cfg.device = 0; cfg.n_smpl = S; cfg.max_sites = n; cfg.max_reads = 64;
     cfg.min_baseQ = 13; cfg.capQ = 60; cfg.call_theta = prior; cfg.call_flag = (varonly ? BCFGPU_CALL_VARONLY : 0) | (keepalt ? BCFGPU_CALL_KEEPALT : 0); cfg.n_grp = ngrp; cfg.ploidy_max = 2;
@@ -718,9 +769,23 @@ int main(int argc, char **argv)
     /* everything goes up once; the records are called in runs of equal ploidy vectors (the ploidy is per call:
      * vcfcall.c:807-825 re-initialises it when it changes) -- the planes are [record][...]: a run is a slice */
     int32_t *d_nals = dev_upload(ctx, nals, (size_t)n * 4), *d_unseen = dev_upload(ctx, unseen, (size_t)n * 4);
-    int32_t *d_plin = dev_upload(ctx, pl, (size_t)n * ngmax * S * 4);
+    int32_t *d_plin = NULL, *d_ad = NULL;
+    if (dev_in) {                                                /* the bytes go up once; the planes are made where mcall() reads them */
+        void *d_indiv = dev_upload(ctx, ibuf, ibuf_l), *dp = NULL;
+        const int32_t *cmap = smpl_file ? (const int32_t *)col : NULL;     /* without -S / -s called sample s is input sample s */
+        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4 + 16, &dp)); d_plin = dp;
+        CHECK(bcfgpu_call_decode_bcf(ctx, n, S_in, d_indiv, ibuf_l, vec_pl, cmap, ngmax, d_plin));
+        if (want_ad) {
+            CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); d_ad = dp;
+            CHECK(bcfgpu_call_decode_bcf(ctx, n, S_in, d_indiv, ibuf_l, vec_ad, cmap, namax, d_ad));
+        }
+        CHECK(bcfgpu_free(ctx, d_indiv));
+    } else {
+        d_plin = dev_upload(ctx, pl, (size_t)n * ngmax * S * 4);
+        if (ad) d_ad = dev_upload(ctx, ad, (size_t)n * namax * S * 4);
+    }
     float *d_qs = dev_upload(ctx, qs, (size_t)n * 5 * 4), *d_i16 = dev_upload(ctx, i16, (size_t)n * 16 * 4);
-    int32_t *d_ad = ad ? dev_upload(ctx, ad, (size_t)n * namax * S * 4) : NULL, *d_grp = grp ? dev_upload(ctx, grp, (size_t)S * 4) : NULL;
+    int32_t *d_grp = grp ? dev_upload(ctx, grp, (size_t)S * 4) : NULL;
     int32_t *d_pan = pan ? dev_upload(ctx, pan, (size_t)n * 4) : NULL, *d_pac = pan ? dev_upload(ctx, pac, (size_t)n * 16) : NULL;
     void *d_site, *d_gt, *d_pl, *d_ploidy, *d_gq = NULL, *d_gp = NULL;
     if (out_tags & BCFGPU_CALL_FMT_GQ) CHECK(bcfgpu_malloc(ctx, (size_t)n * S * 4, &d_gq));
@@ -754,6 +819,8 @@ int main(int argc, char **argv)
     if (gq) CHECK(bcfgpu_memcpy_d2h(ctx, gq, d_gq, (size_t)n * S * 4));
     if (gp) CHECK(bcfgpu_memcpy_d2h(ctx, gp, d_gp, (size_t)n * ngmax * S * 4));
     CHECK(bcfgpu_sync(ctx));
+    t_dev = now_s() - t2;
+    const double t3 = now_s();
 
     /* ---- the output header: the input's, for the samples kept, without the calling-only tags, plus what mcall_init
      * declares (vcfcall.c:670,703-704; mcall.c:382-394) ---- */
@@ -833,6 +900,7 @@ int main(int argc, char **argv)
     }
     /* ---- the record loop (vcfcall.c:1137-1147, mcall.c:1627-1681) ---- */
     const int n_out = cals ? n_events : n;
+    char *smp_text = NULL; size_t smp_cap = 0;
     for (int ev = 0; ev < n_out; ++ev) {
         if (cals && events[ev].is_missed) {                      /* -i: a target that met no record (tgt_flush_region, vcfcall.c:408-424) */
             const tgt_t *t = &tgt[events[ev].tgt];
@@ -915,6 +983,13 @@ int main(int argc, char **argv)
         }
         /* FORMAT: GT first, PL trimmed or dropped, the rest as it came */
         int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
+        char **smp_fld = r->fld + 9;                               /* the input's sample columns */
+        if (dev_in) {                                            /* ... which become text here, for a record that is written */
+            int ns;
+            if (vio_indiv_text(hdr, ibuf + r->ioff, r->ilen, r->n_fmt, S_in, &smp_text, &smp_cap)) DIE("%s\n", vio_error());
+            smp_fld = split(smp_text + 1, '\t', &ns);
+            if (ns != S_in) DIE("malformed VCF\n");
+        }
         fputs("\tGT", LN);
         for (int i = 0; i < nk; ++i) if (i != r->pl_idx || !c->pl_dropped) fprintf(LN, ":%s", keys[i]);
         const int called = nn > 1 && c->ret > 0;               /* mcall_call_genotypes ran: GP and GQ exist (mcall.c:1618-1623) */
@@ -925,7 +1000,7 @@ int main(int argc, char **argv)
             fputc('\t', LN);
             if (g0 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g0);
             if (g1 != BCFGPU_GT_VECTOR_END) { fputc('/', LN); if (g1 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g1); }
-            char *smp = strdup(r->fld[9 + col[s]]); int nv; char **vals = split(smp, ':', &nv);
+            char *smp = strdup(smp_fld[col[s]]); int nv; char **vals = split(smp, ':', &nv);
             for (int i = 0; i < nk; ++i) {
                 if (i == r->pl_idx) {
                     if (c->pl_dropped) continue;
@@ -961,11 +1036,15 @@ int main(int argc, char **argv)
             free(vals); free(smp);
         }
         free(keys); free(fmt);
+        if (dev_in) free(smp_fld);
         fputc(0, LN); fflush(LN);                              /* the record, NUL-terminated, then the stream starts over */
         if (vio_write_line(fout, hdr, ln_buf)) DIE("%s\n", vio_error());
         rewind(LN);
     }
     if (vio_close(fout)) DIE("%s\n", vio_error());
+    t_write = now_s() - t3;
+    if (want_timing) fprintf(stderr, "[bcfgpu_call] seconds: reading records %.3f, building the planes on the host %.3f, uploads and device stages %.3f, writing records %.3f\n", t_read, t_planes, t_dev, t_write);
+    if (want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", dev_in ? n : 0);
     bcfgpu_destroy(ctx);
     return 0;
 }

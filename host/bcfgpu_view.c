@@ -6,6 +6,8 @@
  *  --int-columns: a record whose per-sample columns are all integers (no GT, no '.' inside a vector but as a whole value) is written
  *  through vio_write_record_int -- the columns as integer arrays, the way host/bcfgpu_sam hands them over -- instead of as its text
  *  line; the output must not differ (tests/test_vcfio.py).
+ *  --lazy: BCF input is read through vio_read_record + vio_indiv_text -- the head and the sample columns decoded apart, the way
+ *  host/bcfgpu_call --device-input reads -- instead of vio_read_line; the output must not differ (tests/test_vcfio_lazy.py).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -72,17 +74,18 @@ static int write_int_columns(vio_file *fo, const vio_hdr *h, char *line, long *n
 
 int main(int argc, char **argv)
 {
-    char mode = 'v'; const char *out = "-", *in = NULL; int no_hdr = 0, int_cols = 0;
+    char mode = 'v'; const char *out = "-", *in = NULL; int no_hdr = 0, int_cols = 0, lazy = 0;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-O") && i + 1 < argc) mode = argv[++i][0];
         else if (!strncmp(argv[i], "-O", 2) && argv[i][2]) mode = argv[i][2];
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else if (!strcmp(argv[i], "-H")) no_hdr = 1;
         else if (!strcmp(argv[i], "--int-columns")) int_cols = 1;
+        else if (!strcmp(argv[i], "--lazy")) lazy = 1;
         else if (!strcmp(argv[i], "--int-columns-pad") && i + 1 < argc) { int_cols = 1; int_pad = atoi(argv[++i]); }
         else in = argv[i];
     }
-    if (!in) { fprintf(stderr, "usage: bcfgpu_view [-O v|z|u|b] [-o out] [-H] <in|->\n"); return 2; }
+    if (!in) { fprintf(stderr, "usage: bcfgpu_view [-O v|z|u|b] [-o out] [-H] [--int-columns] [--lazy] <in|->\n"); return 2; }
     vio_file *fi = vio_open_read(in);
     if (!fi) { fprintf(stderr, "%s\n", vio_error()); return 1; }
     vio_hdr *h = vio_read_hdr(fi);
@@ -92,13 +95,22 @@ int main(int argc, char **argv)
     if (!no_hdr && vio_write_hdr(fo, h)) { fprintf(stderr, "%s\n", vio_error()); return 1; }
     char *line = NULL; size_t cap = 0; int rc;
     long n_int = 0;
-    while ((rc = vio_read_line(fi, h, &line, &cap)) > 0) {
+    char *text = NULL; size_t tcap = 0;
+    for (;;) {
+        if (lazy) {
+            const void *indiv; size_t l_indiv; int n_fmt, n_sample;
+            if ((rc = vio_read_record(fi, h, &line, &cap, &indiv, &l_indiv, &n_fmt, &n_sample)) <= 0) break;
+            if (vio_indiv_text(h, indiv, l_indiv, n_fmt, n_sample, &text, &tcap)) { rc = -1; break; }
+            const size_t hl = strlen(line), tl = strlen(text);
+            if (hl + tl + 1 > cap) { cap = hl + tl + 1; line = realloc(line, cap); }
+            memcpy(line + hl, text, tl + 1);
+        } else if ((rc = vio_read_line(fi, h, &line, &cap)) <= 0) break;
         if (int_cols && write_int_columns(fo, h, line, &n_int) == 0) continue;
         if (vio_write_line(fo, h, line)) { fprintf(stderr, "%s\n", vio_error()); return 1; }
     }
     if (int_cols) fprintf(stderr, "%ld records written from integer columns\n", n_int);
     if (rc < 0) { fprintf(stderr, "%s\n", vio_error()); return 1; }
-    free(line);
+    free(line); free(text);
     if (vio_close(fo)) { fprintf(stderr, "%s\n", vio_error()); return 1; }
     vio_close(fi); vio_hdr_free(h);
     return 0;

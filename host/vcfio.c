@@ -643,7 +643,8 @@ static void put_float(sbuf *b, uint32_t u)
     sb_printf(b, "%g", (double)f);
 }
 static int tsz(int t) { return t == BT_INT8 || t == BT_CHAR ? 1 : t == BT_INT16 ? 2 : 4; }
-static int decode_record(const vio_hdr *h, const unsigned char *sh, uint32_t lsh, const unsigned char *in, uint32_t lin, sbuf *b)
+/* the shared part of a record: CHROM .. INFO as text; the counts the per-sample part is read with */
+static int decode_shared(const vio_hdr *h, const unsigned char *sh, uint32_t lsh, sbuf *b, int *n_fmt_out, int *n_sample_out)
 {
     rd_t r = { sh, sh + lsh, 0 };
     if (lsh < 24) return fail("truncated BCF record");
@@ -688,28 +689,40 @@ static int decode_record(const vio_hdr *h, const unsigned char *sh, uint32_t lsh
         }
     }
     if (r.bad) return fail("truncated BCF record");
-    if (!n_sample) return 0;
-    /* FORMAT: the keys, then every sample's values from the per-key blocks */
+    *n_fmt_out = n_fmt; *n_sample_out = n_sample;
+    return 0;
+}
+typedef struct { int d, t, n; const unsigned char *p; } fmt_key;    /* dictionary index, type, values a sample, the values */
+/* the key headers of a per-sample block (at most 64 are read); every key's values lie inside the block */
+static int walk_keys(const vio_hdr *h, const unsigned char *in, size_t lin, int n_fmt, int n_sample, fmt_key *fm)
+{
     rd_t q = { in, in + lin, 0 };
-    struct { int d, t, n; const unsigned char *p; } fm[64];
-    sb_putc(b, '\t');
     for (int k = 0; k < n_fmt && k < 64; ++k) {
         fm[k].d = dec_typed_int(&q);
         if (fm[k].d < 0 || fm[k].d >= h->n_dict || !h->dict[fm[k].d].id) return fail("BCF record with an unknown FORMAT index");
         fm[k].n = dec_size(&q, &fm[k].t); fm[k].p = q.p;
         if (fm[k].n < 0) return fail("truncated BCF record");
         SKIP(&q, (long long)fm[k].n * tsz(fm[k].t) * n_sample);          /* the block of this key lies inside the record */
-        if (k) sb_putc(b, ':');
-        sb_puts(b, h->dict[fm[k].d].id);
     }
     if (q.bad) return fail("truncated BCF record");
+    return 0;
+}
+/* the FORMAT column: tab, the keys' names ('.' without keys) */
+static void put_fmt_column(const vio_hdr *h, const fmt_key *fm, int n_fmt, sbuf *b)
+{
+    sb_putc(b, '\t');
+    for (int k = 0; k < n_fmt && k < 64; ++k) { if (k) sb_putc(b, ':'); sb_puts(b, h->dict[fm[k].d].id); }
     if (!n_fmt) sb_putc(b, '.');
+}
+/* every sample's values from the per-key blocks: the sample columns, a tab in front of each */
+static void put_samples(const vio_hdr *h, const fmt_key *fm, int n_fmt, int n_sample, sbuf *b)
+{
     for (int s = 0; s < n_sample; ++s) {
         sb_putc(b, '\t');
         if (!n_fmt) sb_putc(b, '.');
         for (int k = 0; k < n_fmt && k < 64; ++k) {
             if (k) sb_putc(b, ':');
-            rd_t v = { fm[k].p + (size_t)s * (size_t)fm[k].n * (size_t)tsz(fm[k].t), NULL, 0 };   /* (checked above: inside the record) */
+            rd_t v = { fm[k].p + (size_t)s * (size_t)fm[k].n * (size_t)tsz(fm[k].t), NULL, 0 };   /* (checked by walk_keys: inside the record) */
             const int is_gt = !strcmp(h->dict[fm[k].d].id, "GT");
             if (fm[k].t == BT_CHAR) { const size_t l = strnlen((const char*)v.p, (size_t)fm[k].n); if (l) sb_put(b, v.p, l); else sb_putc(b, '.'); continue; }
             int printed = 0;
@@ -726,6 +739,16 @@ static int decode_record(const vio_hdr *h, const unsigned char *sh, uint32_t lsh
             if (!printed) sb_putc(b, '.');
         }
     }
+}
+static int decode_record(const vio_hdr *h, const unsigned char *sh, uint32_t lsh, const unsigned char *in, uint32_t lin, sbuf *b)
+{
+    int n_fmt, n_sample;
+    if (decode_shared(h, sh, lsh, b, &n_fmt, &n_sample)) return -1;
+    if (!n_sample) return 0;
+    fmt_key fm[64];
+    if (walk_keys(h, in, lin, n_fmt, n_sample, fm)) return -1;
+    put_fmt_column(h, fm, n_fmt, b);
+    put_samples(h, fm, n_fmt, n_sample, b);
     return 0;
 }
 
@@ -816,4 +839,55 @@ int vio_read_line(vio_file *f, const vio_hdr *h, char **line, size_t *cap)
     b.s[b.l] = 0;
     *line = b.s; *cap = b.m;
     return got;
+}
+
+int vio_is_bcf(const vio_file *f) { return f->bcf; }
+int vio_read_record(vio_file *f, const vio_hdr *h, char **head, size_t *cap, const void **indiv, size_t *l_indiv, int *n_fmt, int *n_sample)
+{
+    if (!f->bcf) return fail("a record without its sample text can only be read from a BCF file");
+    sbuf b = { *head, 0, *cap };
+    int got = 0;
+    *indiv = NULL; *l_indiv = 0; *n_fmt = *n_sample = 0;
+    if (fill(f, 8)) return -1;
+    if (f->blk.l - f->rd >= 8) {
+        uint32_t ls, li; memcpy(&ls, f->blk.s + f->rd, 4); memcpy(&li, f->blk.s + f->rd + 4, 4);
+        if (fill(f, 8 + (size_t)ls + li) || f->blk.l - f->rd < 8 + (size_t)ls + li) return fail("truncated BCF record");
+        const unsigned char *p = (const unsigned char*)f->blk.s + f->rd + 8;
+        int rc = decode_shared(h, p, ls, &b, n_fmt, n_sample);
+        if (!rc && *n_sample) {
+            fmt_key fm[64];
+            rc = walk_keys(h, p + ls, li, *n_fmt, *n_sample, fm);
+            if (!rc) put_fmt_column(h, fm, *n_fmt, &b);
+        }
+        if (rc) { *head = b.s; *cap = b.m; return -1; }
+        *indiv = p + ls; *l_indiv = li;
+        f->rd += 8 + (size_t)ls + li;
+        got = 1;
+    }
+    if (!b.s) sb_need(&b, 1);
+    b.s[b.l] = 0;
+    *head = b.s; *cap = b.m;
+    return got;
+}
+int vio_indiv_keys(const vio_hdr *h, const void *indiv, size_t l_indiv, int n_fmt, int n_sample, vio_indiv_key *keys)
+{
+    fmt_key fm[64];
+    if (walk_keys(h, indiv, l_indiv, n_fmt, n_sample, fm)) return -1;
+    const int nk = n_fmt < 64 ? n_fmt : 64;
+    for (int k = 0; k < nk; ++k) {
+        keys[k].dict = fm[k].d; keys[k].id = h->dict[fm[k].d].id; keys[k].type = fm[k].t; keys[k].width = fm[k].n;
+        keys[k].off = (size_t)(fm[k].p - (const unsigned char*)indiv);
+    }
+    return nk;
+}
+int vio_indiv_text(const vio_hdr *h, const void *indiv, size_t l_indiv, int n_fmt, int n_sample, char **text, size_t *cap)
+{
+    sbuf b = { *text, 0, *cap };
+    fmt_key fm[64];
+    const int rc = n_sample ? walk_keys(h, indiv, l_indiv, n_fmt, n_sample, fm) : 0;
+    if (!rc) put_samples(h, fm, n_fmt, n_sample, &b);
+    if (!b.s) sb_need(&b, 1);
+    b.s[b.l] = 0;
+    *text = b.s; *cap = b.m;
+    return rc;
 }

@@ -51,7 +51,23 @@ int  vio_hdr_fmt_id(const vio_hdr *h, const char *id);
 int  vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, const void *indiv, size_t l_indiv);
 vio_file *vio_open_read(const char *path);                      /* path "-" = stdin; VCF, bgzipped VCF or BCF2, detected */
 vio_hdr *vio_read_hdr(vio_file *f);
+int  vio_is_bcf(const vio_file *f);                             /* 1: the stream holds BCF2 records, 0: VCF text */
 int  vio_read_line(vio_file *f, const vio_hdr *h, char **line, size_t *cap);   /* 1: a record (as VCF text) in *line, 0: end, <0: error */
+/* A BCF record without its sample text: vio_read_line up to and including the FORMAT column (the first nine fields; eight when the
+ * file has no samples) in *head, and the record's raw per-sample block where it lies in the file's buffer -- *indiv, *l_indiv bytes,
+ * valid until the next read -- with the counts it is read with.  BCF input only: -1 with a message on a text stream.
+ * vio_indiv_keys: the n_fmt key headers of such a block (at most 64), truncation checked as vio_read_line checks it; the number of keys
+ * filled in, or -1.  vio_indiv_text: the sample columns of the block as text ("\t...\t..."), exactly the bytes vio_read_line puts
+ * behind the FORMAT column: head + text is its line. */
+typedef struct {
+    int dict;               /* the key's index in the header's dictionary */
+    const char *id;         /* its name (the header's string) */
+    int type, width;        /* BCF2 type code (1 int8, 2 int16, 3 int32, 5 float, 7 char) and values a sample */
+    size_t off;             /* byte offset inside the block of value [sample 0][0] */
+} vio_indiv_key;
+int  vio_read_record(vio_file *f, const vio_hdr *h, char **head, size_t *cap, const void **indiv, size_t *l_indiv, int *n_fmt, int *n_sample);
+int  vio_indiv_keys(const vio_hdr *h, const void *indiv, size_t l_indiv, int n_fmt, int n_sample, vio_indiv_key *keys);
+int  vio_indiv_text(const vio_hdr *h, const void *indiv, size_t l_indiv, int n_fmt, int n_sample, char **text, size_t *cap);
 int  vio_close(vio_file *f);
 const char *vio_error(void);
 

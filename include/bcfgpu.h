@@ -27,6 +27,8 @@
  *    bcfgpu_pipeline                     <- the `mpileup -Ou | call -m` pipe with PL/QS/I16 kept in HBM
  *    bcfgpu_mplp_encode_bcf              <- the bcf_update_format_int32 calls of bcf_call2bcf (bam2bcf.c:845-903) and the typed-value
  *                                           encoding bcf_write does to them: the per-sample part of an mpileup record as BCF2 bytes
+ *    bcfgpu_call_decode_bcf              <- the bcf_get_format_int32 calls of mcall() (mcall.c:1444, :1475) and the unpacking of the
+ *                                           per-sample block behind them: FORMAT/PL and AD / QS of BCF records as the planes of bcfgpu_call_in
  *
  *  Memory model: all bulk arrays are *device* pointers (HBM).  Hosts that do
  *  not link HIP use bcfgpu_malloc/free/memcpy_*.  Kernels are enqueued on the
@@ -684,6 +686,27 @@ enum { BCFGPU_BCF_PL, BCFGPU_BCF_DP, BCFGPU_BCF_DV, BCFGPU_BCF_SP, BCFGPU_BCF_DP
        BCFGPU_BCF_AD, BCFGPU_BCF_DPR, BCFGPU_BCF_SCR, BCFGPU_BCF_QS, BCFGPU_BCF_NKEYS };
 int  bcfgpu_mplp_encode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, const bcfgpu_mplp_out *planes, const int32_t key_id[BCFGPU_BCF_NKEYS],
                             const uint8_t *d_emit, void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
+
+/* The other end of the pipe: one FORMAT key's integer vectors of n_sites BCF records as int32 planes [site][plane][called sample], the
+ * layout of bcfgpu_call_in.pl / .ad, made on the device from the records' per-sample blocks as the file holds them (bcfdec.hip).
+ *   d_indiv  DEVICE, n_indiv_bytes: the records' per-sample blocks, back to back (any other bytes may lie between them)
+ *   vec      HOST [n_sites]: where the key's values of each record are (host/vcfio.c vio_indiv_keys finds them)
+ *   col      HOST [cfg.n_smpl] or NULL: the input sample of each called sample (NULL: called sample s is input sample s, cfg.n_smpl <= n_smpl_in)
+ *   d_out    DEVICE [n_sites][n_planes][cfg.n_smpl]
+ * out[(k * n_planes + j) * S + s] follows the rule of the text route (host/vcfio.c dec_int, then the parse of host/bcfgpu_call.c):
+ * for j < min(width, n_planes) the value widened to int32, the smallest two values of int8 and int16 becoming BCFGPU_INT32_MISSING and
+ * BCFGPU_INT32_VECTOR_END; from a sample's first VECTOR_END on and for j >= width VECTOR_END; a sample whose plane 0 would be VECTOR_END
+ * (type 0, width 0, a vector that ends at once: '.' in text) has MISSING there.
+ * BCFGPU_E_ARG for a type outside 0-3, a negative width, a col entry outside [0, n_smpl_in) or NULL pointers; BCFGPU_E_RANGE when
+ * off + n_smpl_in * width * size passes n_indiv_bytes; nothing is written in either case.  n_sites == 0 is valid.
+ * Runs on the context's stream and synchronises it. */
+typedef struct {
+    uint64_t off;     /* byte offset, inside the indiv buffer, of value [sample 0][0] of the key in this record */
+    int32_t  type;    /* BCF2 typed-value code: 1 int8, 2 int16, 3 int32; 0 = the record has no such key */
+    int32_t  width;   /* values a sample, >= 0 */
+} bcfgpu_bcf_vec;
+int  bcfgpu_call_decode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_smpl_in, const void *d_indiv, uint64_t n_indiv_bytes,
+                            const bcfgpu_bcf_vec *vec, const int32_t *col, int32_t n_planes, int32_t *d_out);
 
 /* One communicator over the contexts of a node, rank i = ctxs[i] (RCCL ncclCommInitAll; every context on its own device;
  * librccl is loaded at this call, a single context needs none). */

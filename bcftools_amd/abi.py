@@ -24,6 +24,9 @@ GT_MISSING, GT_VECTOR_END = -1, -2
 # FORMAT keys of an mpileup record in bcf_call2bcf's order (BCFGPU_BCF_*), each with the fmt_flag bit that selects it (PL: always)
 BCF_KEYS = ("PL", "DP", "DV", "SP", "DP4", "ADF", "ADR", "AD", "DPR", "SCR", "QS")
 BCF_KEY_FLAG = (0, FMT_DP, FMT_DV, FMT_SP, FMT_DP4, FMT_ADF, FMT_ADR, FMT_AD, FMT_DPR, FMT_SCR, FMT_QS)
+# FORMAT keys of a call record that bcfgpu_call_encode_bcf writes (BCFGPU_CALL_BCF_*), each with an offset of its own per site
+CALL_BCF_KEYS = ("GT", "PL", "GQ")
+CALL_BCF_GT, CALL_BCF_PL, CALL_BCF_GQ, CALL_BCF_NKEYS = 0, 1, 2, 3
 
 RD_REV, RD_SCLIP, RD_DEL, RD_SKIP = 1 << 20, 1 << 21, 1 << 22, 1 << 23
 
@@ -240,6 +243,8 @@ PROTOTYPES = {
     "bcfgpu_compact_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "bcfgpu_mplp_encode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MplpOut), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bcfgpu_call_encode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_call_decode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(BcfVec), C.POINTER(C.c_int32),
                                          C.c_int32, C.c_void_p]),
     "bcfgpu_comm_init_all": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),

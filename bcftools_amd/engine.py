@@ -255,8 +255,9 @@ class Context:
             self.release(bufs + [b for _, b in outs])
         return nb.value, blk, min_dp, block, bdp
 
-    def mcall(self, cin):
-        """Run the caller on a host CallInput, return a host CallResult."""
+    def mcall_device(self, cin):
+        """Run the caller on a host CallInput and leave its result planes in HBM: (abi.CallOut of device pointers, {plane name:
+        DevBuf}, the host CallResult downloaded from them).  The buffers are the caller's to release (Context.release)."""
         assert cin.n_smpl == self.cfg.n_smpl
         keep = []
         d = abi.CallIn()
@@ -274,8 +275,17 @@ class Context:
             check(self.L.bcfgpu_mcall(self.h, C.byref(d), C.byref(o)))
             self.sync()
             self._download(ob, res)
+        except BaseException:
+            self.release(list(ob.values()))
+            raise
         finally:
-            self.release(keep + list(ob.values()))
+            self.release(keep)
+        return o, ob, res
+
+    def mcall(self, cin):
+        """Run the caller on a host CallInput, return a host CallResult."""
+        o, ob, res = self.mcall_device(cin)
+        self.release(list(ob.values()))
         return res
 
     def pipeline(self, tile, ploidy=None, grp=None):
@@ -329,6 +339,41 @@ class Context:
                 e.needed = n.value
                 raise e
             data, offs = np.zeros(n.value, np.uint8), np.zeros(n_sites + 1, np.uint64)
+            if n.value:
+                out.download(data)
+            off.download(offs)
+        finally:
+            self.release(bufs)
+        return data, offs
+
+    def encode_call_bcf(self, planes, n_sites, n_gt_max, key_id, emit=None, cap_bytes=None):
+        """bcfgpu_call_encode_bcf on call planes already in HBM (an abi.CallOut of device pointers; pl and gq may be None): GT, the
+        trimmed PL and GQ of the call records as BCF2 bytes, every key's block with an offset of its own.  key_id: {key name:
+        dictionary index} or a sequence in abi.CALL_BCF_KEYS order; emit: host u8 [n_sites] or None; cap_bytes: the buffer's size
+        (None: asked from the size pass first).  Returns (bytes as np.uint8, offsets as np.uint64 [n_sites * 3 + 1]); BcfGpuError
+        with code E_RANGE and .needed = the size when cap_bytes is too small."""
+        ids = (C.c_int32 * abi.CALL_BCF_NKEYS)(*([key_id.get(k, 0) for k in abi.CALL_BCF_KEYS] if isinstance(key_id, dict) else key_id))
+        n_off = n_sites * abi.CALL_BCF_NKEYS + 1
+        off, n = self.buf(8 * n_off), C.c_uint64(0)
+        bufs = [off]
+        d_emit = None
+        if emit is not None:
+            bufs.append(self.to_device(np.ascontiguousarray(emit, dtype=np.uint8)))
+            d_emit = bufs[-1].ptr
+        try:
+            if cap_bytes is None:
+                rc = self.L.bcfgpu_call_encode_bcf(self.h, n_sites, n_gt_max, C.byref(planes), ids, d_emit, None, 0, off.ptr, C.byref(n))
+                if rc not in (0, abi.E_RANGE):
+                    check(rc)
+                cap_bytes = n.value
+            out = self.buf(cap_bytes)
+            bufs.append(out)
+            rc = self.L.bcfgpu_call_encode_bcf(self.h, n_sites, n_gt_max, C.byref(planes), ids, d_emit, out.ptr, cap_bytes, off.ptr, C.byref(n))
+            if rc:
+                e = BcfGpuError(rc, self.L.bcfgpu_last_error().decode())
+                e.needed = n.value
+                raise e
+            data, offs = np.zeros(n.value, np.uint8), np.zeros(n_off, np.uint64)
             if n.value:
                 out.download(data)
             off.download(offs)

@@ -2,7 +2,7 @@
  *  include/bcfgpu.h: the record loop of main_vcfcall (vcfcall.c:1089-1148) with mcall() on the device.
  *
  *      bcfgpu_call [-v] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]]
- *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--timing] <in.vcf>
+ *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-records] [--timing] [-O v|z|u|b] <in.vcf>
  *          -S: the samples to keep, in that order: NAME [PLOIDY|SEX] per line, or a PED file (vcfcall.c:202-344)
  *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c)
  *          -G: sample groups with their own allele frequencies, '-' = every sample alone, or NAME GROUP lines
@@ -13,8 +13,16 @@
  *              holds them and bcfgpu_call_decode_bcf makes the PL (and, with -G, AD / QS) planes there; the sample columns become
  *              text only for the records that are written.  Takes effect on BCF input without -C alleles and without -g (both read
  *              the samples' values on the host); in any other run the option does nothing.  The same output either way.
- *          --timing: one line of seconds on stderr (reading records, building the planes on the host, uploads and device stages,
- *              writing records), and how many records' planes were decoded on the device
+ *          --device-records: with -O u|b the records' GT, PL and GQ do not come down as planes to be printed and parsed back: after the
+ *              calls bcfgpu_call_encode_bcf turns them into BCF2 key blocks in HBM, for the records that are written only, and the host
+ *              downloads the site records, the bytes and one offset per record and key.  A record is then its head and
+ *              vio_write_record_indiv of the blocks in the text route's order: GT (device), the input's keys with the device's PL
+ *              block in PL's place (nothing when PL is dropped) and the other keys' blocks made on the host from their text
+ *              (vio_encode_keys; Number=R tags trimmed as ever), GP (host: its bytes are those of the "%g" text), GQ (device).
+ *              Does nothing with -O v|z and with -g (whose block lines read the genotypes on the host).  The same output either way.
+ *          --timing: lines on stderr: the seconds (reading records, building the planes on the host, uploads and device stages,
+ *              writing records), how many records' planes were decoded on the device, and how many records' FORMAT blocks were
+ *              encoded there
  *
  *  Host: VCF text in, what mcall() reads from a record (alleles, FORMAT/PL, INFO/QS, INFO/I16) packed into the planes of
  *  bcfgpu_call_in, one bcfgpu_mcall over all records, then what mcall.c:1627-1681 does to the record: alleles trimmed with
@@ -393,7 +401,7 @@ int main(int argc, char **argv)
         for (int i = 1; i < argc; ++i)
             for (size_t k = 0; k < sizeof alias / sizeof alias[0]; ++k) if (!strcmp(argv[i], alias[k][0])) argv[i] = (char *)alias[k][1];
     }
-    int varonly = 0, out_tags = 0, keepalt = 0, dev_in = 0, want_timing = 0;
+    int varonly = 0, out_tags = 0, keepalt = 0, dev_in = 0, dev_rec = 0, want_timing = 0;
     double t_read = 0., t_planes = 0., t_dev = 0., t_write = 0.;
     int acgt_only = 1, skip_kind = 0;                           /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
     const char *tgt_file = NULL; double prior = 1.1e-3;
@@ -416,6 +424,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[1], "--no-version")) { ++argv; --argc; }                                                       /* (no ##bcftools_callVersion lines are written anyway) */
         else if (!strcmp(argv[1], "-i")) { insert_missed = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-input")) { dev_in = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-records")) { dev_rec = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--timing")) { want_timing = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "-C") && argc > 3) { if (strcmp(argv[2], "alleles")) DIE("-C: only `alleles` is supported\n"); cals = 1; argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-T") && argc > 3) { tgt_file = argv[2]; argv += 2; argc -= 2; }
@@ -470,7 +479,7 @@ int main(int argc, char **argv)
     }
     if (gv_n && varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (gv_n && cals) DIE("-g with -C alleles is not supported\n");
-    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-records] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
     /* ploidy definition (ploidy.c): regions per sex, '*' lines = the sex's default; the last sex named is the default sex */
     preg_t *preg = NULL; int npreg = 0; char last_sex[64] = "";
     char *alias_text = NULL;
@@ -519,6 +528,7 @@ int main(int argc, char **argv)
     vio_hdr *hdr = vio_read_hdr(fin);
     if (!hdr) DIE("%s\n", vio_error());
     dev_in = dev_in && vio_is_bcf(fin) && !cals && !gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
+    dev_rec = dev_rec && (out_mode == 'u' || out_mode == 'b') && !gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
     unsigned char *ibuf = NULL; size_t ibuf_l = 0, ibuf_m = 0;   /* --device-input: the records' per-sample blocks, back to back */
     const double t0 = now_s();
     char *buf = NULL; size_t bufcap = 0;
@@ -812,10 +822,12 @@ int main(int argc, char **argv)
         i = j;
     }
     bcfgpu_call_site *cs = malloc((size_t)n * sizeof *cs);
-    int8_t *gt = malloc((size_t)n * 2 * S); int32_t *opl = malloc((size_t)n * ngmax * S * 4);
-    CHECK(bcfgpu_memcpy_d2h(ctx, cs, d_site, (size_t)n * sizeof *cs)); CHECK(bcfgpu_memcpy_d2h(ctx, gt, d_gt, (size_t)n * 2 * S));
-    CHECK(bcfgpu_memcpy_d2h(ctx, opl, d_pl, (size_t)n * ngmax * S * 4));
-    int32_t *gq = d_gq ? malloc((size_t)n * S * 4) : NULL; float *gp = d_gp ? malloc((size_t)n * ngmax * S * 4) : NULL;
+    /* --device-records: the site records alone come down here (and GP); GT, PL and GQ follow as bytes once the writer's header is known */
+    int8_t *gt = dev_rec ? NULL : malloc((size_t)n * 2 * S); int32_t *opl = dev_rec ? NULL : malloc((size_t)n * ngmax * S * 4);
+    CHECK(bcfgpu_memcpy_d2h(ctx, cs, d_site, (size_t)n * sizeof *cs));
+    if (gt) CHECK(bcfgpu_memcpy_d2h(ctx, gt, d_gt, (size_t)n * 2 * S));
+    if (opl) CHECK(bcfgpu_memcpy_d2h(ctx, opl, d_pl, (size_t)n * ngmax * S * 4));
+    int32_t *gq = d_gq && !dev_rec ? malloc((size_t)n * S * 4) : NULL; float *gp = d_gp ? malloc((size_t)n * ngmax * S * 4) : NULL;
     if (gq) CHECK(bcfgpu_memcpy_d2h(ctx, gq, d_gq, (size_t)n * S * 4));
     if (gp) CHECK(bcfgpu_memcpy_d2h(ctx, gp, d_gp, (size_t)n * ngmax * S * 4));
     CHECK(bcfgpu_sync(ctx));
@@ -838,6 +850,36 @@ int main(int argc, char **argv)
     vio_hdr_append(hdr, "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"Total number of alleles in called genotypes\">");
     vio_hdr_append(hdr, "##INFO=<ID=DP4,Number=4,Type=Integer,Description=\"Number of high-quality ref-forward , ref-reverse, alt-forward and alt-reverse bases\">");
     vio_hdr_append(hdr, "##INFO=<ID=MQ,Number=1,Type=Integer,Description=\"Average mapping quality\">");
+    /* ---- --device-records: GT, PL and GQ of the records that will be written, as BCF2 key blocks made in HBM; the key ids are the
+     * output header's.  One call over all records: the size first, then the bytes; one offset per record and key ---- */
+    unsigned char *kblk = NULL; uint64_t *koff = NULL; int n_enc = 0; double t_enc = 0.;
+    if (dev_rec) {
+        const double te = now_s();
+        uint8_t *emit = malloc((size_t)n + 1);
+        for (int k = 0; k < n; ++k) { emit[k] = !(cs[k].ret < 0 || (varonly && cs[k].ret == 0)); n_enc += emit[k]; }      /* the record loop's rule */
+        int32_t kid[BCFGPU_CALL_BCF_NKEYS];
+        kid[BCFGPU_CALL_BCF_GT] = vio_hdr_fmt_id(hdr, "GT"); kid[BCFGPU_CALL_BCF_PL] = vio_hdr_fmt_id(hdr, "PL");
+        kid[BCFGPU_CALL_BCF_GQ] = d_gq ? vio_hdr_fmt_id(hdr, "GQ") : 0;
+        if (kid[BCFGPU_CALL_BCF_PL] < 0) DIE("FORMAT tag PL is not defined in the header\n");
+        void *d_emit = dev_upload(ctx, emit, (size_t)n), *d_koff = NULL, *d_kblk = NULL;
+        const size_t n_off = (size_t)n * BCFGPU_CALL_BCF_NKEYS + 1;
+        CHECK(bcfgpu_malloc(ctx, n_off * 8, &d_koff));
+        bcfgpu_call_out planes; memset(&planes, 0, sizeof planes);
+        planes.site = d_site; planes.gt = d_gt; planes.pl = d_pl; planes.gq = d_gq;
+        uint64_t need = 0;
+        int rc = bcfgpu_call_encode_bcf(ctx, n, ngmax, &planes, kid, d_emit, NULL, 0, d_koff, &need);
+        if (rc && rc != BCFGPU_E_RANGE) DIE("bcfgpu_call_encode_bcf: %s (%d)\n", bcfgpu_last_error(), rc);
+        koff = malloc(n_off * 8); kblk = malloc(need ? need : 1);
+        if (need) {
+            CHECK(bcfgpu_malloc(ctx, need, &d_kblk));
+            CHECK(bcfgpu_call_encode_bcf(ctx, n, ngmax, &planes, kid, d_emit, d_kblk, need, d_koff, &need));
+            CHECK(bcfgpu_memcpy_d2h(ctx, kblk, d_kblk, need));
+        }
+        CHECK(bcfgpu_memcpy_d2h(ctx, koff, d_koff, n_off * 8));
+        CHECK(bcfgpu_sync(ctx));
+        free(emit);
+        t_enc = now_s() - te;                                    /* a device stage: counted there, not under writing */
+    }
     vio_file *fout = vio_open_write(out_path, out_mode);
     if (!fout || vio_write_hdr(fout, hdr)) DIE("%s\n", vio_error());
     LN = open_memstream(&ln_buf, &ln_len);
@@ -901,6 +943,7 @@ int main(int argc, char **argv)
     /* ---- the record loop (vcfcall.c:1137-1147, mcall.c:1627-1681) ---- */
     const int n_out = cals ? n_events : n;
     char *smp_text = NULL; size_t smp_cap = 0;
+    char *hblk = NULL, *iblk = NULL; size_t hblk_cap = 0, iblk_cap = 0;       /* --device-records: the host keys' blocks, the record's per-sample part */
     for (int ev = 0; ev < n_out; ++ev) {
         if (cals && events[ev].is_missed) {                      /* -i: a target that met no record (tgt_flush_region, vcfcall.c:408-424) */
             const tgt_t *t = &tgt[events[ev].tgt];
@@ -983,8 +1026,11 @@ int main(int argc, char **argv)
         }
         /* FORMAT: GT first, PL trimmed or dropped, the rest as it came */
         int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
+        const int called = nn > 1 && c->ret > 0;               /* mcall_call_genotypes ran: GP and GQ exist (mcall.c:1618-1623) */
+        /* --device-records: GT, PL and GQ are blocks already; the sample text holds the other keys alone (host_keys of them) */
+        const int host_keys = dev_rec ? nk - 1 + (called && gp) : 0, want_text = !dev_rec || host_keys > 0;
         char **smp_fld = r->fld + 9;                               /* the input's sample columns */
-        if (dev_in) {                                            /* ... which become text here, for a record that is written */
+        if (dev_in && want_text) {                               /* ... which become text here, for a record that is written */
             int ns;
             if (vio_indiv_text(hdr, ibuf + r->ioff, r->ilen, r->n_fmt, S_in, &smp_text, &smp_cap)) DIE("%s\n", vio_error());
             smp_fld = split(smp_text + 1, '\t', &ns);
@@ -992,19 +1038,24 @@ int main(int argc, char **argv)
         }
         fputs("\tGT", LN);
         for (int i = 0; i < nk; ++i) if (i != r->pl_idx || !c->pl_dropped) fprintf(LN, ":%s", keys[i]);
-        const int called = nn > 1 && c->ret > 0;               /* mcall_call_genotypes ran: GP and GQ exist (mcall.c:1618-1623) */
         if (called && gp) fputs(":GP", LN);
-        if (called && gq) fputs(":GQ", LN);
-        for (int s = 0; s < S; ++s) {
-            const int g0 = gt[((size_t)k * 2 + 0) * S + s], g1 = gt[((size_t)k * 2 + 1) * S + s];
-            fputc('\t', LN);
-            if (g0 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g0);
-            if (g1 != BCFGPU_GT_VECTOR_END) { fputc('/', LN); if (g1 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g1); }
+        if (called && (gq || (dev_rec && d_gq))) fputs(":GQ", LN);
+        long head_end = 0;
+        if (dev_rec) { fputc(0, LN); head_end = ftell(LN); }    /* the head ends here; the other keys' sample text follows it in the stream */
+        for (int s = 0; s < S && want_text; ++s) {
+            int nf = 0;                                          /* fields of this sample so far: ':' in front of all but the first */
+            if (!dev_rec || s) fputc('\t', LN);
+            if (!dev_rec) {
+                const int g0 = gt[((size_t)k * 2 + 0) * S + s], g1 = gt[((size_t)k * 2 + 1) * S + s];
+                if (g0 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g0);
+                if (g1 != BCFGPU_GT_VECTOR_END) { fputc('/', LN); if (g1 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g1); }
+                ++nf;
+            }
             char *smp = strdup(smp_fld[col[s]]); int nv; char **vals = split(smp, ':', &nv);
             for (int i = 0; i < nk; ++i) {
                 if (i == r->pl_idx) {
-                    if (c->pl_dropped) continue;
-                    fputc(':', LN);
+                    if (c->pl_dropped || dev_rec) continue;
+                    if (nf++) fputc(':', LN);
                     int printed = 0;
                     for (int j = 0; j < ngn; ++j) {
                         const int32_t v = opl[((size_t)k * ngmax + j) * S + s];
@@ -1014,12 +1065,12 @@ int main(int argc, char **argv)
                     }
                     if (!printed) fputc('.', LN);
                 } else if (i < nv && nn != r->nals && is_numberR(fmtR, n_fmtR, keys[i], strlen(keys[i]))) {
-                    fputc(':', LN);
+                    if (nf++) fputc(':', LN);
                     print_numberR(vals[i], c->als_map, r->nals, nn);
-                } else fprintf(LN, ":%s", i < nv ? vals[i] : ".");
+                } else fprintf(LN, "%s%s", nf++ ? ":" : "", i < nv ? vals[i] : ".");
             }
             if (called && gp) {
-                fputc(':', LN);
+                if (nf++) fputc(':', LN);
                 int printed = 0;
                 for (int j = 0; j < ngn; ++j) {
                     uint32_t bits; memcpy(&bits, &gp[((size_t)k * ngmax + j) * S + s], 4);
@@ -1035,6 +1086,35 @@ int main(int argc, char **argv)
             }
             free(vals); free(smp);
         }
+        if (dev_rec) {
+            /* the record's per-sample part: the device's blocks and the host's, in the FORMAT column's order */
+            fputc(0, LN); fflush(LN);
+            int nhost = 0; size_t kend[64];
+            if (host_keys > 0) {
+                char *hf = malloc(strlen(r->fld[8]) + 8), *o = hf;              /* the host's keys as a FORMAT column of their own */
+                for (int i = 0; i < nk; ++i) if (i != r->pl_idx) o += sprintf(o, "%s%s", o > hf ? ":" : "", keys[i]);
+                if (called && gp) o += sprintf(o, "%sGP", o > hf ? ":" : "");
+                if ((nhost = vio_encode_keys(hdr, hf, ln_buf + head_end, S, &hblk, &hblk_cap, kend)) != host_keys) DIE("%s\n", nhost < 0 ? vio_error() : "FORMAT keys lost on the way");
+                free(hf);
+            }
+            const uint64_t *ko = koff + (size_t)k * BCFGPU_CALL_BCF_NKEYS;
+            const size_t need = (size_t)(ko[BCFGPU_CALL_BCF_NKEYS] - ko[0]) + (nhost ? kend[nhost - 1] : 0);
+            if (need > iblk_cap) { iblk_cap = need * 2 + 256; iblk = realloc(iblk, iblk_cap); if (!iblk) DIE("out of memory\n"); }
+            size_t il = 0; int hk = 0;
+            #define PUT_DEV(i) do { memcpy(iblk + il, kblk + ko[i], (size_t)(ko[(i) + 1] - ko[i])); il += (size_t)(ko[(i) + 1] - ko[i]); } while (0)
+            #define PUT_HOST() do { const size_t b0 = hk ? kend[hk - 1] : 0; memcpy(iblk + il, hblk + b0, kend[hk] - b0); il += kend[hk] - b0; ++hk; } while (0)
+            PUT_DEV(BCFGPU_CALL_BCF_GT);
+            for (int i = 0; i < nk; ++i) { if (i == r->pl_idx) PUT_DEV(BCFGPU_CALL_BCF_PL); else PUT_HOST(); }
+            if (called && gp) PUT_HOST();
+            PUT_DEV(BCFGPU_CALL_BCF_GQ);
+            #undef PUT_DEV
+            #undef PUT_HOST
+            if (vio_write_record_indiv(fout, hdr, ln_buf, iblk, il)) DIE("%s\n", vio_error());
+            rewind(LN);
+            free(keys); free(fmt);
+            if (dev_in && want_text) free(smp_fld);
+            continue;
+        }
         free(keys); free(fmt);
         if (dev_in) free(smp_fld);
         fputc(0, LN); fflush(LN);                              /* the record, NUL-terminated, then the stream starts over */
@@ -1042,9 +1122,10 @@ int main(int argc, char **argv)
         rewind(LN);
     }
     if (vio_close(fout)) DIE("%s\n", vio_error());
-    t_write = now_s() - t3;
+    t_write = now_s() - t3 - t_enc; t_dev += t_enc;
     if (want_timing) fprintf(stderr, "[bcfgpu_call] seconds: reading records %.3f, building the planes on the host %.3f, uploads and device stages %.3f, writing records %.3f\n", t_read, t_planes, t_dev, t_write);
     if (want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", dev_in ? n : 0);
+    if (want_timing) fprintf(stderr, "[bcfgpu_call] device records: %d records' FORMAT blocks encoded on the device\n", n_enc);
     bcfgpu_destroy(ctx);
     return 0;
 }

@@ -2,12 +2,16 @@
  *  `bcftools view [-O v|z|u|b]` does for a file that needs no filtering; used the way test.pl:1194-1195 uses it, to turn
  *  the BCF output of the drivers back into text).
  *
- *      bcfgpu_view [-O v|z|u|b] [-o out] [-H] [--int-columns] <in|->            -H: records only, no header
+ *      bcfgpu_view [-O v|z|u|b] [-o out] [-H] [--int-columns] [--lazy] [--key-blocks] <in|->            -H: records only, no header
  *  --int-columns: a record whose per-sample columns are all integers (no GT, no '.' inside a vector but as a whole value) is written
  *  through vio_write_record_int -- the columns as integer arrays, the way host/bcfgpu_sam hands them over -- instead of as its text
  *  line; the output must not differ (tests/test_vcfio.py).
  *  --lazy: BCF input is read through vio_read_record + vio_indiv_text -- the head and the sample columns decoded apart, the way
  *  host/bcfgpu_call --device-input reads -- instead of vio_read_line; the output must not differ (tests/test_vcfio_lazy.py).
+ *  --key-blocks: with BCF output, a record with samples is written as its head and the per-sample part put together from the FORMAT keys'
+ *  blocks, each made on its own by vio_encode_keys (every key with its values cut out of the sample columns), through
+ *  vio_write_record_indiv -- the way host/bcfgpu_call --device-records writes -- instead of as its text line; the output must not
+ *  differ (tests/test_call_indiv_encoder.py).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -72,9 +76,44 @@ static int write_int_columns(vio_file *fo, const vio_hdr *h, char *line, long *n
     return rc;
 }
 
+/* --key-blocks: 0: the record went out as head + key blocks; 1: it has no sample columns (the caller writes the text line); -1: error */
+static int write_key_blocks(vio_file *fo, const vio_hdr *h, char *line)
+{
+    const int S = vio_hdr_nsamples(h);
+    char *f8 = NULL; int tabs = 0;
+    for (char *p = line; *p; ++p) if (*p == '\t' && ++tabs == 8) { f8 = p + 1; break; }
+    char *smp = f8 ? strchr(f8, '\t') : NULL;
+    if (!smp || !S) return 1;
+    *smp = 0;                                                    /* the head: CHROM .. FORMAT */
+    int nk; char *fmt = strdup(f8), *keys[64];
+    nk = 0; for (char *t = strtok(fmt, ":"); t && nk < 64; t = strtok(NULL, ":")) keys[nk++] = t;
+    /* every key alone: its values of all samples as one-key sample columns, its block appended to the record's */
+    char *all = NULL, *one = NULL, *cols = malloc(strlen(smp + 1) + 2); size_t l_all = 0, m_all = 0, cap1 = 0, end[64];
+    int rc = 0;
+    for (int k = 0; k < nk && !rc; ++k) {
+        char *o = cols; const char *q = smp + 1;
+        for (int s = 0; s < S; ++s) {
+            const char *e = strchr(q, '\t'); if (!e) e = q + strlen(q);
+            const char *v = q; int i = 0;
+            while (i < k && v) { const char *c = memchr(v, ':', (size_t)(e - v)); v = c ? c + 1 : NULL; ++i; }
+            if (s) *o++ = '\t';
+            if (!v) *o++ = '.';
+            else { const char *c = memchr(v, ':', (size_t)(e - v)); if (!c) c = e; memcpy(o, v, (size_t)(c - v)); o += c - v; }
+            q = *e ? e + 1 : e;
+        }
+        *o = 0;
+        if (vio_encode_keys(h, keys[k], cols, S, &one, &cap1, end) != 1) { rc = -1; break; }
+        if (l_all + end[0] > m_all) { m_all = (l_all + end[0]) * 2 + 64; all = realloc(all, m_all); }
+        memcpy(all + l_all, one, end[0]); l_all += end[0];
+    }
+    if (!rc && vio_write_record_indiv(fo, h, line, all ? all : "", l_all)) rc = -1;
+    free(all); free(one); free(cols); free(fmt);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
-    char mode = 'v'; const char *out = "-", *in = NULL; int no_hdr = 0, int_cols = 0, lazy = 0;
+    char mode = 'v'; const char *out = "-", *in = NULL; int no_hdr = 0, int_cols = 0, lazy = 0, key_blocks = 0;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-O") && i + 1 < argc) mode = argv[++i][0];
         else if (!strncmp(argv[i], "-O", 2) && argv[i][2]) mode = argv[i][2];
@@ -82,10 +121,11 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-H")) no_hdr = 1;
         else if (!strcmp(argv[i], "--int-columns")) int_cols = 1;
         else if (!strcmp(argv[i], "--lazy")) lazy = 1;
+        else if (!strcmp(argv[i], "--key-blocks")) key_blocks = 1;
         else if (!strcmp(argv[i], "--int-columns-pad") && i + 1 < argc) { int_cols = 1; int_pad = atoi(argv[++i]); }
         else in = argv[i];
     }
-    if (!in) { fprintf(stderr, "usage: bcfgpu_view [-O v|z|u|b] [-o out] [-H] [--int-columns] [--lazy] <in|->\n"); return 2; }
+    if (!in) { fprintf(stderr, "usage: bcfgpu_view [-O v|z|u|b] [-o out] [-H] [--int-columns] [--lazy] [--key-blocks] <in|->\n"); return 2; }
     vio_file *fi = vio_open_read(in);
     if (!fi) { fprintf(stderr, "%s\n", vio_error()); return 1; }
     vio_hdr *h = vio_read_hdr(fi);
@@ -106,6 +146,11 @@ int main(int argc, char **argv)
             memcpy(line + hl, text, tl + 1);
         } else if ((rc = vio_read_line(fi, h, &line, &cap)) <= 0) break;
         if (int_cols && write_int_columns(fo, h, line, &n_int) == 0) continue;
+        if (key_blocks && (mode == 'u' || mode == 'b')) {
+            const int kb = write_key_blocks(fo, h, line);
+            if (kb < 0) { fprintf(stderr, "%s\n", vio_error()); return 1; }
+            if (kb == 0) continue;
+        }
         if (vio_write_line(fo, h, line)) { fprintf(stderr, "%s\n", vio_error()); return 1; }
     }
     if (int_cols) fprintf(stderr, "%ld records written from integer columns\n", n_int);

@@ -416,6 +416,75 @@ static int32_t int_val(const char *s, size_t n)
 }
 static int count_char(const char *s, size_t n, char c) { int k = 0; for (size_t i = 0; i < n; ++i) k += s[i] == c; return k; }
 
+/* the S sample columns of a record (tab separated; NULL: none, every value is '.') split once: value k of sample s = sv[s * n_fmt + k], sl bytes */
+static void split_samples(const char *samples, int S, int n_fmt, const char ***sv_out, size_t **sl_out)
+{
+    const char **sv = malloc((size_t)S * (size_t)n_fmt * sizeof *sv); size_t *sl = calloc((size_t)S * (size_t)n_fmt, sizeof *sl);
+    const char *q = samples;
+    for (int s = 0; s < S; ++s) {
+        const char *e = q ? strchr(q, '\t') : NULL, *qe = q ? (e ? e : q + strlen(q)) : NULL;
+        const char *t = q;
+        for (int k = 0; k < n_fmt; ++k) {
+            if (!t || t > qe) { sv[(size_t)s * n_fmt + k] = "."; sl[(size_t)s * n_fmt + k] = 1; continue; }
+            const char *te = memchr(t, ':', (size_t)(qe - t)); if (!te) te = qe;
+            sv[(size_t)s * n_fmt + k] = t; sl[(size_t)s * n_fmt + k] = (size_t)(te - t);
+            t = te < qe ? te + 1 : NULL;
+        }
+        q = e ? e + 1 : NULL;
+    }
+    *sv_out = sv; *sl_out = sl;
+}
+/* FORMAT key k of a record (dictionary index d) as its BCF2 block -- typed key id, descriptor, the S samples' values -- appended to `in` */
+static void encode_fmt_key(const vio_hdr *h, int d, int k, int n_fmt, int S, const char *const *sv, const size_t *sl, sbuf *in)
+{
+    const int ty = h->dict[d].fmt_type;
+    const int is_gt = !strcmp(h->dict[d].id, "GT");
+    enc_int1(in, d);
+    if (is_gt) {
+        int w = 1;
+        for (int s = 0; s < S; ++s) { const char *v = sv[(size_t)s * n_fmt + k]; const size_t vl = sl[(size_t)s * n_fmt + k]; const int c = 1 + count_char(v, vl, '/') + count_char(v, vl, '|'); if (c > w) w = c; }
+        int32_t *a = malloc((size_t)S * (size_t)w * 4);
+        for (int s = 0; s < S; ++s) {
+            const char *v = sv[(size_t)s * n_fmt + k], *ve = v + sl[(size_t)s * n_fmt + k];
+            int j = 0, phased = 0;
+            while (v <= ve && j < w) {
+                const char *e = v; while (e < ve && *e != '/' && *e != '|') ++e;
+                const int32_t al = (e - v == 1 && v[0] == '.') || e == v ? -1 : int_val(v, (size_t)(e - v));
+                a[(size_t)s * w + j++] = (al + 1) << 1 | phased;
+                if (e >= ve) break;
+                phased = *e == '|'; v = e + 1;
+            }
+            for (; j < w; ++j) a[(size_t)s * w + j] = I_VEND;
+        }
+        enc_vint(in, S * w, a, w);
+        free(a);
+    } else if (ty == T_STR) {
+        size_t w = 0;
+        for (int s = 0; s < S; ++s) if (sl[(size_t)s * n_fmt + k] > w) w = sl[(size_t)s * n_fmt + k];
+        enc_size(in, (int)w, BT_CHAR);
+        for (int s = 0; s < S; ++s) { sb_put(in, sv[(size_t)s * n_fmt + k], sl[(size_t)s * n_fmt + k]); for (size_t z = sl[(size_t)s * n_fmt + k]; z < w; ++z) sb_putc(in, 0); }
+    } else {
+        int w = 1;
+        for (int s = 0; s < S; ++s) { const int c = 1 + count_char(sv[(size_t)s * n_fmt + k], sl[(size_t)s * n_fmt + k], ','); if (c > w) w = c; }
+        int32_t *a = malloc((size_t)S * (size_t)w * 4);
+        for (int s = 0; s < S; ++s) {
+            const char *v = sv[(size_t)s * n_fmt + k], *ve = v + sl[(size_t)s * n_fmt + k];
+            int j = 0;
+            while (j < w) {
+                const char *e = memchr(v, ',', (size_t)(ve - v)); if (!e) e = ve;
+                if (ty == T_INT) a[(size_t)s * w + j] = int_val(v, (size_t)(e - v)); else { const uint32_t u = float_bits(v, (size_t)(e - v)); memcpy(&a[(size_t)s * w + j], &u, 4); }
+                ++j;
+                if (e >= ve) break;
+                v = e + 1;
+            }
+            for (; j < w; ++j) { if (ty == T_INT) a[(size_t)s * w + j] = I_VEND; else memcpy(&a[(size_t)s * w + j], &F_VEND, 4); }
+        }
+        if (ty == T_INT) { if (S * w == 1) { enc_int1(in, a[0]); } else enc_vint(in, S * w, a, w); }
+        else { enc_size(in, w, BT_FLOAT); sb_put(in, a, (size_t)S * (size_t)w * 4); }
+        free(a);
+    }
+}
+
 /* one VCF text record -> BCF2 (l_shared, l_indiv, shared, indiv) appended to `out` */
 /* vals != NULL: the per-sample columns are not in `line` (which ends with the FORMAT keys) but in integer arrays, n_keys of them,
  * vals[k][s * width[k] + j] (vio_write_record_int) */
@@ -542,68 +611,9 @@ static int encode_record(const vio_hdr *h, const char *line, sbuf *out, int n_ke
     } else
     /* per-sample fields: the columns of every sample split once */
     if (n_fmt) {
-        const int S = n_sample;
-        const char **sv = malloc((size_t)S * (size_t)n_fmt * sizeof *sv); size_t *sl = calloc((size_t)S * (size_t)n_fmt, sizeof *sl);
-        const char *q = samples;
-        for (int s = 0; s < S; ++s) {
-            const char *e = q ? strchr(q, '\t') : NULL, *qe = q ? (e ? e : q + strlen(q)) : NULL;
-            const char *t = q;
-            for (int k = 0; k < n_fmt; ++k) {
-                if (!t || t > qe) { sv[(size_t)s * n_fmt + k] = "."; sl[(size_t)s * n_fmt + k] = 1; continue; }
-                const char *te = memchr(t, ':', (size_t)(qe - t)); if (!te) te = qe;
-                sv[(size_t)s * n_fmt + k] = t; sl[(size_t)s * n_fmt + k] = (size_t)(te - t);
-                t = te < qe ? te + 1 : NULL;
-            }
-            q = e ? e + 1 : NULL;
-        }
-        for (int k = 0; k < n_fmt; ++k) {
-            const int d = fkey[k], ty = h->dict[d].fmt_type;
-            const int is_gt = !strcmp(h->dict[d].id, "GT");
-            enc_int1(&in, d);
-            if (is_gt) {
-                int w = 1;
-                for (int s = 0; s < S; ++s) { const char *v = sv[(size_t)s * n_fmt + k]; const size_t vl = sl[(size_t)s * n_fmt + k]; const int c = 1 + count_char(v, vl, '/') + count_char(v, vl, '|'); if (c > w) w = c; }
-                int32_t *a = malloc((size_t)S * (size_t)w * 4);
-                for (int s = 0; s < S; ++s) {
-                    const char *v = sv[(size_t)s * n_fmt + k], *ve = v + sl[(size_t)s * n_fmt + k];
-                    int j = 0, phased = 0;
-                    while (v <= ve && j < w) {
-                        const char *e = v; while (e < ve && *e != '/' && *e != '|') ++e;
-                        const int32_t al = (e - v == 1 && v[0] == '.') || e == v ? -1 : int_val(v, (size_t)(e - v));
-                        a[(size_t)s * w + j++] = (al + 1) << 1 | phased;
-                        if (e >= ve) break;
-                        phased = *e == '|'; v = e + 1;
-                    }
-                    for (; j < w; ++j) a[(size_t)s * w + j] = I_VEND;
-                }
-                enc_vint(&in, S * w, a, w);
-                free(a);
-            } else if (ty == T_STR) {
-                size_t w = 0;
-                for (int s = 0; s < S; ++s) if (sl[(size_t)s * n_fmt + k] > w) w = sl[(size_t)s * n_fmt + k];
-                enc_size(&in, (int)w, BT_CHAR);
-                for (int s = 0; s < S; ++s) { sb_put(&in, sv[(size_t)s * n_fmt + k], sl[(size_t)s * n_fmt + k]); for (size_t z = sl[(size_t)s * n_fmt + k]; z < w; ++z) sb_putc(&in, 0); }
-            } else {
-                int w = 1;
-                for (int s = 0; s < S; ++s) { const int c = 1 + count_char(sv[(size_t)s * n_fmt + k], sl[(size_t)s * n_fmt + k], ','); if (c > w) w = c; }
-                int32_t *a = malloc((size_t)S * (size_t)w * 4);
-                for (int s = 0; s < S; ++s) {
-                    const char *v = sv[(size_t)s * n_fmt + k], *ve = v + sl[(size_t)s * n_fmt + k];
-                    int j = 0;
-                    while (j < w) {
-                        const char *e = memchr(v, ',', (size_t)(ve - v)); if (!e) e = ve;
-                        if (ty == T_INT) a[(size_t)s * w + j] = int_val(v, (size_t)(e - v)); else { const uint32_t u = float_bits(v, (size_t)(e - v)); memcpy(&a[(size_t)s * w + j], &u, 4); }
-                        ++j;
-                        if (e >= ve) break;
-                        v = e + 1;
-                    }
-                    for (; j < w; ++j) { if (ty == T_INT) a[(size_t)s * w + j] = I_VEND; else memcpy(&a[(size_t)s * w + j], &F_VEND, 4); }
-                }
-                if (ty == T_INT) { if (S * w == 1) { enc_int1(&in, a[0]); } else enc_vint(&in, S * w, a, w); }
-                else { enc_size(&in, w, BT_FLOAT); sb_put(&in, a, (size_t)S * (size_t)w * 4); }
-                free(a);
-            }
-        }
+        const char **sv; size_t *sl;
+        split_samples(samples, n_sample, n_fmt, &sv, &sl);
+        for (int k = 0; k < n_fmt; ++k) encode_fmt_key(h, fkey[k], k, n_fmt, n_sample, sv, sl, &in);
         free(sv); free(sl);
     }
     sb_u32(out, (uint32_t)sh.l); sb_u32(out, (uint32_t)in.l);
@@ -806,6 +816,29 @@ int vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, cons
     f->rec.l = 0;
     if (encode_record(h, head, &f->rec, 0, NULL, NULL, indiv, l_indiv)) return -1;
     return out_bytes(f, f->rec.s, f->rec.l);
+}
+int vio_encode_keys(const vio_hdr *h, const char *fmt, const char *samples, int n_sample, char **out, size_t *cap, size_t *key_end)
+{
+    int fkey[64], n_fmt = 0;
+    const char *q = fmt, *qe = fmt + strlen(fmt);
+    while (q < qe) {
+        const char *e = memchr(q, ':', (size_t)(qe - q)); if (!e) e = qe;
+        const int d = dict_find(h, q, (size_t)(e - q));
+        if (d < 0 || h->dict[d].fmt_type == T_NONE) return fail("FORMAT tag %.*s is not defined in the header", (int)(e - q), q);
+        if (n_fmt == 64) return fail("more than 64 FORMAT keys");
+        fkey[n_fmt++] = d;
+        q = e + 1;
+    }
+    sbuf b = { *out, 0, *cap };
+    if (n_fmt && n_sample > 0) {
+        const char **sv; size_t *sl;
+        split_samples(samples, n_sample, n_fmt, &sv, &sl);
+        for (int k = 0; k < n_fmt; ++k) { encode_fmt_key(h, fkey[k], k, n_fmt, n_sample, sv, sl, &b); key_end[k] = b.l; }
+        free(sv); free(sl);
+    } else for (int k = 0; k < n_fmt; ++k) key_end[k] = 0;
+    if (!b.s) sb_need(&b, 1);
+    *out = b.s; *cap = b.m;
+    return n_fmt;
 }
 int vio_read_line(vio_file *f, const vio_hdr *h, char **line, size_t *cap)
 {

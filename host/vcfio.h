@@ -49,6 +49,13 @@ int  vio_hdr_fmt_id(const vio_hdr *h, const char *id);
  * is encoded from it as for every other record, n_fmt being the number of keys in its FORMAT column and n_sample the header's --, then
  * the l_indiv bytes of `indiv` as they are.  BCF output only: -1 on a text file. */
 int  vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, const void *indiv, size_t l_indiv);
+/* FORMAT keys as BCF2 key blocks, without a record around them: `fmt` = the keys as in a FORMAT column ("AD:DP"), `samples` = the
+ * n_sample sample columns holding those keys' values, tab separated ("1,2:3\t0,0:1"; a column that ends early has '.' for the rest).
+ * Every key's block -- typed key id, descriptor, values, exactly the bytes vio_write_line puts into a record's per-sample part for that
+ * key -- is appended to *out (a malloc'ed buffer that grows, *cap its size; overwritten from its start); key_end[k] = the bytes of
+ * *out up to and including key k's block (room for 64).  The number of keys, or -1.  A writer that has other keys' blocks ready
+ * (bcfgpu_call_encode_bcf) puts these between them and hands the whole to vio_write_record_indiv. */
+int  vio_encode_keys(const vio_hdr *h, const char *fmt, const char *samples, int n_sample, char **out, size_t *cap, size_t *key_end);
 vio_file *vio_open_read(const char *path);                      /* path "-" = stdin; VCF, bgzipped VCF or BCF2, detected */
 vio_hdr *vio_read_hdr(vio_file *f);
 int  vio_is_bcf(const vio_file *f);                             /* 1: the stream holds BCF2 records, 0: VCF text */

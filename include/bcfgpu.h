@@ -27,6 +27,8 @@
  *    bcfgpu_pipeline                     <- the `mpileup -Ou | call -m` pipe with PL/QS/I16 kept in HBM
  *    bcfgpu_mplp_encode_bcf              <- the bcf_update_format_int32 calls of bcf_call2bcf (bam2bcf.c:845-903) and the typed-value
  *                                           encoding bcf_write does to them: the per-sample part of an mpileup record as BCF2 bytes
+ *    bcfgpu_call_encode_bcf              <- bcf_update_genotypes / bcf_update_format_int32 of mcall() (mcall.c:1158-1194, :1583, :1618-1623)
+ *                                           and the writer's typed-value encoder, for GT, PL and GQ of the call records
  *    bcfgpu_call_decode_bcf              <- the bcf_get_format_int32 calls of mcall() (mcall.c:1444, :1475) and the unpacking of the
  *                                           per-sample block behind them: FORMAT/PL and AD / QS of BCF records as the planes of bcfgpu_call_in
  *
@@ -707,6 +709,35 @@ typedef struct {
 } bcfgpu_bcf_vec;
 int  bcfgpu_call_decode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_smpl_in, const void *d_indiv, uint64_t n_indiv_bytes,
                             const bcfgpu_bcf_vec *vec, const int32_t *col, int32_t n_planes, int32_t *d_out);
+
+/* The caller's own records: FORMAT/GT, the trimmed FORMAT/PL and FORMAT/GQ of every call record as BCF2 bytes, made on the planes
+ * bcfgpu_mcall / bcfgpu_pipeline left in HBM (bcfcallenc.hip) -- what bcf_update_genotypes and bcf_update_format_int32 (mcall.c:1158-1194,
+ * :1583, :1618-1623) hand to the writer and its typed-value encoder narrows (host/vcfio.c enc_vint).  Every key's block is complete in
+ * itself -- typed key id, descriptor, values, by the rules above bcfgpu_mplp_encode_bcf -- and has an offset of its own, so that a
+ * writer can put other keys' blocks between them.  With nn = site[k].nals_new and ngn = nn(nn+1)/2, per emitted site:
+ *     GT   n_smpl x w int8: (allele + 1) << 1, BCFGPU_GT_MISSING -> 0; w = 2 when any sample's second entry is not
+ *          BCFGPU_GT_VECTOR_END, else 1; in a record with w = 2 a sample whose second entry is VECTOR_END has 0x81 there
+ *     PL   absent when site[k].pl_dropped (or planes->pl is NULL).  A sample's vector: its values of planes 0 .. ngn-1 up to its first
+ *          BCFGPU_INT32_VECTOR_END, one `missing` when there is none; w = the longest vector of the record, shorter ones padded with
+ *          `end of vector`.  The type is int8 when every value that is no sentinel lies in -120 .. 127, int16 when in -32760 .. 32767,
+ *          else int32 (enc_vint); missing / end of vector are 0x80 / 0x81, 0x8000 / 0x8001, or the int32 sentinels as they are
+ *     GQ   only when planes->gq is not NULL and nn > 1 && site[k].ret > 0: n_smpl x 1, the type chosen as PL's
+ *   n_gt_max DEVICE planes' count of `pl` per site, 1 .. 15, as bcfgpu_call_in.n_gt_max
+ *   planes   DEVICE pointers: site and gt are required, pl and gq may be NULL, gp is not read
+ *   key_id   HOST, indexed by BCFGPU_CALL_BCF_*: the keys' indices in the writer's header dictionary
+ *   d_emit   DEVICE [n_sites], 0 = the site has no record; NULL = every site has one
+ *   d_buf    DEVICE, cap_bytes: the blocks back to back, in site order and per site GT, PL, GQ
+ *   d_off    DEVICE [n_sites * BCFGPU_CALL_BCF_NKEYS + 1], 8-byte aligned: d_off[k * NKEYS + i] = the start of key i's block of site k,
+ *            the last entry = the size of all; an absent key and every key of a site without a record have zero length.  Set whether
+ *            or not the blocks fit
+ *   n_bytes  HOST, out: the size of all blocks
+ * When the blocks do not fit cap_bytes nothing is written to d_buf, *n_bytes is the size needed and the call returns BCFGPU_E_RANGE
+ * (cap_bytes = 0 asks for the size).  BCFGPU_E_ARG for NULL pointers, a negative key id or n_gt_max outside 1 .. 15.  n_sites == 0 is
+ * valid.  Runs on the context's stream and synchronises it. */
+enum { BCFGPU_CALL_BCF_GT, BCFGPU_CALL_BCF_PL, BCFGPU_CALL_BCF_GQ, BCFGPU_CALL_BCF_NKEYS };
+int  bcfgpu_call_encode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_gt_max, const bcfgpu_call_out *planes,
+                            const int32_t key_id[BCFGPU_CALL_BCF_NKEYS], const uint8_t *d_emit,
+                            void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
 
 /* One communicator over the contexts of a node, rank i = ctxs[i] (RCCL ncclCommInitAll; every context on its own device;
  * librccl is loaded at this call, a single context needs none). */

@@ -174,6 +174,17 @@ class BcfVec(C.Structure):
 
 BCF_VEC = [("off", "<u8"), ("type", "<i4"), ("width", "<i4")]       # the same as a numpy record
 
+BCF_KEY_MAX_WIDTH = 255
+
+
+class BcfKey(C.Structure):
+    """bcfgpu_bcf_key: one pass-through FORMAT key of one record, a job of bcfgpu_call_remap_bcf (32 bytes)."""
+    _fields_ = [("off", C.c_uint64), ("site", C.c_int32), ("key_id", C.c_int32), ("type", C.c_int32), ("width", C.c_int32),
+                ("nals", C.c_int32), ("flags", C.c_int32)]
+
+
+BCF_KEY = [("off", "<u8"), ("site", "<i4"), ("key_id", "<i4"), ("type", "<i4"), ("width", "<i4"), ("nals", "<i4"), ("flags", "<i4")]
+
 
 class Timing(C.Structure):
     _fields_ = [("glfgen_ms", C.c_float), ("combine_ms", C.c_float),
@@ -247,6 +258,8 @@ PROTOTYPES = {
                                          C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_call_decode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(BcfVec), C.POINTER(C.c_int32),
                                          C.c_int32, C.c_void_p]),
+    "bcfgpu_call_remap_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BcfKey), C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_comm_init_all": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
     "bcfgpu_comm_destroy": (None, [C.c_void_p]),
     "bcfgpu_gather_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

@@ -2,7 +2,7 @@
  *  include/bcfgpu.h: the record loop of main_vcfcall (vcfcall.c:1089-1148) with mcall() on the device.
  *
  *      bcfgpu_call [-v] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]]
- *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-records] [--timing] [-O v|z|u|b] <in.vcf>
+ *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-records] [--device-keys] [--timing] [-O v|z|u|b] <in.vcf>
  *          -S: the samples to keep, in that order: NAME [PLOIDY|SEX] per line, or a PED file (vcfcall.c:202-344)
  *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c)
  *          -G: sample groups with their own allele frequencies, '-' = every sample alone, or NAME GROUP lines
@@ -20,9 +20,17 @@
  *              block in PL's place (nothing when PL is dropped) and the other keys' blocks made on the host from their text
  *              (vio_encode_keys; Number=R tags trimmed as ever), GP (host: its bytes are those of the "%g" text), GQ (device).
  *              Does nothing with -O v|z and with -g (whose block lines read the genotypes on the host).  The same output either way.
+ *          --device-keys: with --device-input and --device-records both in effect, the integer keys the caller passes through (AD, ADF,
+ *              ADR, DP, SP, ...: declared Type=Integer, not PL, not GT, stored as int8 / int16 / int32 or without values, at most 255
+ *              values a sample) are not printed, split, re-ordered and parsed back either: the input records' bytes stay in HBM after
+ *              the decode and bcfgpu_call_remap_bcf makes those keys' blocks of the written records there -- the -S sample choice,
+ *              the Number=R values following als_map, width and type chosen anew -- one size call and one write call over all of
+ *              them.  The host splices them in their keys' places; Float and String keys and GP stay on the host
+ *              (vio_encode_keys), and a record without any of those forms no sample text at all.  In any other run the option does
+ *              nothing.  The same output either way.
  *          --timing: lines on stderr: the seconds (reading records, building the planes on the host, uploads and device stages,
  *              writing records), how many records' planes were decoded on the device, and how many records' FORMAT blocks were
- *              encoded there
+ *              encoded there; with --device-keys given, also how many pass-through key blocks were made on the device and on the host
  *
  *  Host: VCF text in, what mcall() reads from a record (alleles, FORMAT/PL, INFO/QS, INFO/I16) packed into the planes of
  *  bcfgpu_call_in, one bcfgpu_mcall over all records, then what mcall.c:1627-1681 does to the record: alleles trimmed with
@@ -48,7 +56,8 @@ static FILE *LN; static char *ln_buf; static size_t ln_len;      /* the record b
 
 /* with --device-input: line = the first nine columns, the per-sample block = ilen bytes at ioff of the byte buffer, its key headers in keys */
 typedef struct { char *line; char **fld; int nfld; char **als; int nals, unseen, pl_idx, ad_idx; uint8_t *ploidy;
-                 size_t ioff, ilen; int n_fmt, nkeys; vio_indiv_key *keys; } rec_t;
+                 size_t ioff, ilen; int n_fmt, nkeys; vio_indiv_key *keys;
+                 int *kjob; } rec_t;            /* --device-keys, a written record: key i's job of bcfgpu_call_remap_bcf, or -1 (the host's) */
 
 static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
@@ -401,7 +410,7 @@ int main(int argc, char **argv)
         for (int i = 1; i < argc; ++i)
             for (size_t k = 0; k < sizeof alias / sizeof alias[0]; ++k) if (!strcmp(argv[i], alias[k][0])) argv[i] = (char *)alias[k][1];
     }
-    int varonly = 0, out_tags = 0, keepalt = 0, dev_in = 0, dev_rec = 0, want_timing = 0;
+    int varonly = 0, out_tags = 0, keepalt = 0, dev_in = 0, dev_rec = 0, dev_keys = 0, keys_given = 0, want_timing = 0;
     double t_read = 0., t_planes = 0., t_dev = 0., t_write = 0.;
     int acgt_only = 1, skip_kind = 0;                           /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
     const char *tgt_file = NULL; double prior = 1.1e-3;
@@ -425,6 +434,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[1], "-i")) { insert_missed = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-input")) { dev_in = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-records")) { dev_rec = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-keys")) { dev_keys = keys_given = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--timing")) { want_timing = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "-C") && argc > 3) { if (strcmp(argv[2], "alleles")) DIE("-C: only `alleles` is supported\n"); cals = 1; argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-T") && argc > 3) { tgt_file = argv[2]; argv += 2; argc -= 2; }
@@ -479,7 +489,7 @@ int main(int argc, char **argv)
     }
     if (gv_n && varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (gv_n && cals) DIE("-g with -C alleles is not supported\n");
-    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-records] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-records] [--device-keys] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
     /* ploidy definition (ploidy.c): regions per sex, '*' lines = the sex's default; the last sex named is the default sex */
     preg_t *preg = NULL; int npreg = 0; char last_sex[64] = "";
     char *alias_text = NULL;
@@ -529,6 +539,7 @@ int main(int argc, char **argv)
     if (!hdr) DIE("%s\n", vio_error());
     dev_in = dev_in && vio_is_bcf(fin) && !cals && !gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
     dev_rec = dev_rec && (out_mode == 'u' || out_mode == 'b') && !gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
+    dev_keys = dev_keys && dev_in && dev_rec;                  /* the input's bytes in HBM and key blocks to splice: both ends on the device */
     unsigned char *ibuf = NULL; size_t ibuf_l = 0, ibuf_m = 0;   /* --device-input: the records' per-sample blocks, back to back */
     const double t0 = now_s();
     char *buf = NULL; size_t bufcap = 0;
@@ -608,7 +619,7 @@ int main(int argc, char **argv)
         r->line = strdup(use);
         free(owned);
         r->fld = split(r->line, '\t', &r->nfld);
-        r->keys = NULL; r->nkeys = 0;
+        r->keys = NULL; r->nkeys = 0; r->kjob = NULL;
         if (dev_in) {                                            /* the block joins the byte buffer; where its keys' values lie */
             if (r->nfld != 9 || n_sample != S_in) DIE("malformed VCF\n");
             if (ibuf_l + l_indiv > ibuf_m) { ibuf_m = (ibuf_l + l_indiv) * 2 + (1 << 20); ibuf = realloc(ibuf, ibuf_m); if (!ibuf) DIE("out of memory\n"); }
@@ -780,8 +791,10 @@ int main(int argc, char **argv)
      * vcfcall.c:807-825 re-initialises it when it changes) -- the planes are [record][...]: a run is a slice */
     int32_t *d_nals = dev_upload(ctx, nals, (size_t)n * 4), *d_unseen = dev_upload(ctx, unseen, (size_t)n * 4);
     int32_t *d_plin = NULL, *d_ad = NULL;
+    void *d_indiv = NULL;                                        /* --device-keys: kept until the pass-through keys' blocks are made */
     if (dev_in) {                                                /* the bytes go up once; the planes are made where mcall() reads them */
-        void *d_indiv = dev_upload(ctx, ibuf, ibuf_l), *dp = NULL;
+        void *dp = NULL;
+        d_indiv = dev_upload(ctx, ibuf, ibuf_l);
         const int32_t *cmap = smpl_file ? (const int32_t *)col : NULL;     /* without -S / -s called sample s is input sample s */
         CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4 + 16, &dp)); d_plin = dp;
         CHECK(bcfgpu_call_decode_bcf(ctx, n, S_in, d_indiv, ibuf_l, vec_pl, cmap, ngmax, d_plin));
@@ -789,7 +802,7 @@ int main(int argc, char **argv)
             CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); d_ad = dp;
             CHECK(bcfgpu_call_decode_bcf(ctx, n, S_in, d_indiv, ibuf_l, vec_ad, cmap, namax, d_ad));
         }
-        CHECK(bcfgpu_free(ctx, d_indiv));
+        if (!dev_keys) { CHECK(bcfgpu_free(ctx, d_indiv)); d_indiv = NULL; }
     } else {
         d_plin = dev_upload(ctx, pl, (size_t)n * ngmax * S * 4);
         if (ad) d_ad = dev_upload(ctx, ad, (size_t)n * namax * S * 4);
@@ -853,6 +866,7 @@ int main(int argc, char **argv)
     /* ---- --device-records: GT, PL and GQ of the records that will be written, as BCF2 key blocks made in HBM; the key ids are the
      * output header's.  One call over all records: the size first, then the bytes; one offset per record and key ---- */
     unsigned char *kblk = NULL; uint64_t *koff = NULL; int n_enc = 0; double t_enc = 0.;
+    unsigned char *pblk = NULL; uint64_t *poff = NULL; long n_pjob = 0, n_phost = 0;      /* --device-keys: the pass-through keys' blocks, one offset a job */
     if (dev_rec) {
         const double te = now_s();
         uint8_t *emit = malloc((size_t)n + 1);
@@ -877,6 +891,51 @@ int main(int argc, char **argv)
         }
         CHECK(bcfgpu_memcpy_d2h(ctx, koff, d_koff, n_off * 8));
         CHECK(bcfgpu_sync(ctx));
+        /* ---- --device-keys: a job for every integer pass-through key of every record that is written; the blocks are made from the
+         * input's bytes where --device-input left them, with the sample map it passed and the site records' als_map ---- */
+        if (dev_keys) {
+            size_t cap_job = 0; bcfgpu_bcf_key *job = NULL;
+            for (int k = 0; k < n; ++k) {
+                rec_t *r = &recs[k];
+                if (!emit[k]) continue;
+                r->kjob = malloc((size_t)(r->nkeys ? r->nkeys : 1) * sizeof *r->kjob);
+                for (int i = 0; i < r->nkeys; ++i) {
+                    const vio_indiv_key *q = &r->keys[i];
+                    r->kjob[i] = -1;
+                    if (i == r->pl_idx || !strcmp(q->id, "GT") || vio_hdr_fmt_type(hdr, q->dict) != VIO_TYPE_INT) continue;
+                    if (q->type < 0 || q->type > 3 || q->width < 0 || q->width > BCFGPU_BCF_KEY_MAX_WIDTH) continue;
+                    const int id = vio_hdr_fmt_id(hdr, q->id);
+                    if (id < 0) continue;
+                    if ((size_t)n_pjob == cap_job) { cap_job = cap_job ? 2 * cap_job : 4096; job = realloc(job, cap_job * sizeof *job); if (!job) DIE("out of memory\n"); }
+                    bcfgpu_bcf_key *j = &job[n_pjob];
+                    j->off = r->ioff + q->off; j->site = k; j->key_id = id; j->type = q->type; j->width = q->width; j->nals = r->nals;
+                    j->flags = is_numberR(fmtR, n_fmtR, q->id, strlen(q->id));
+                    r->kjob[i] = (int)n_pjob++;
+                }
+            }
+            if (n_pjob > INT32_MAX - 1) DIE("too many pass-through keys for one call\n");
+            poff = calloc((size_t)n_pjob + 1, 8);
+            if (n_pjob) {
+                const int32_t *cmap = smpl_file ? (const int32_t *)col : NULL;
+                void *d_poff = NULL, *d_pblk = NULL;
+                CHECK(bcfgpu_malloc(ctx, ((size_t)n_pjob + 1) * 8, &d_poff));
+                uint64_t pneed = 0;
+                rc = bcfgpu_call_remap_bcf(ctx, (int32_t)n_pjob, job, S_in, d_indiv, ibuf_l, cmap, d_site, n, d_emit, NULL, 0, d_poff, &pneed);
+                if (rc && rc != BCFGPU_E_RANGE) DIE("bcfgpu_call_remap_bcf: %s (%d)\n", bcfgpu_last_error(), rc);
+                pblk = malloc(pneed ? pneed : 1);
+                if (pneed) {
+                    CHECK(bcfgpu_malloc(ctx, pneed, &d_pblk));
+                    CHECK(bcfgpu_call_remap_bcf(ctx, (int32_t)n_pjob, job, S_in, d_indiv, ibuf_l, cmap, d_site, n, d_emit, d_pblk, pneed, d_poff, &pneed));
+                    CHECK(bcfgpu_memcpy_d2h(ctx, pblk, d_pblk, pneed));
+                }
+                CHECK(bcfgpu_memcpy_d2h(ctx, poff, d_poff, ((size_t)n_pjob + 1) * 8));
+                CHECK(bcfgpu_sync(ctx));
+                if (d_pblk) CHECK(bcfgpu_free(ctx, d_pblk));
+                CHECK(bcfgpu_free(ctx, d_poff));
+            }
+            free(job);
+            CHECK(bcfgpu_free(ctx, d_indiv)); d_indiv = NULL;
+        }
         free(emit);
         t_enc = now_s() - te;                                    /* a device stage: counted there, not under writing */
     }
@@ -1028,7 +1087,11 @@ int main(int argc, char **argv)
         int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
         const int called = nn > 1 && c->ret > 0;               /* mcall_call_genotypes ran: GP and GQ exist (mcall.c:1618-1623) */
         /* --device-records: GT, PL and GQ are blocks already; the sample text holds the other keys alone (host_keys of them) */
-        const int host_keys = dev_rec ? nk - 1 + (called && gp) : 0, want_text = !dev_rec || host_keys > 0;
+        const int *kjob = dev_keys && r->kjob && nk == r->nkeys ? r->kjob : NULL;     /* the keys whose blocks the device made */
+        int host_keys = dev_rec ? nk - 1 + (called && gp) : 0;
+        for (int i = 0; kjob && i < nk; ++i) host_keys -= kjob[i] >= 0;
+        const int want_text = !dev_rec || host_keys > 0;
+        if (dev_rec) n_phost += host_keys;
         char **smp_fld = r->fld + 9;                               /* the input's sample columns */
         if (dev_in && want_text) {                               /* ... which become text here, for a record that is written */
             int ns;
@@ -1053,6 +1116,7 @@ int main(int argc, char **argv)
             }
             char *smp = strdup(smp_fld[col[s]]); int nv; char **vals = split(smp, ':', &nv);
             for (int i = 0; i < nk; ++i) {
+                if (kjob && kjob[i] >= 0) continue;
                 if (i == r->pl_idx) {
                     if (c->pl_dropped || dev_rec) continue;
                     if (nf++) fputc(':', LN);
@@ -1092,23 +1156,26 @@ int main(int argc, char **argv)
             int nhost = 0; size_t kend[64];
             if (host_keys > 0) {
                 char *hf = malloc(strlen(r->fld[8]) + 8), *o = hf;              /* the host's keys as a FORMAT column of their own */
-                for (int i = 0; i < nk; ++i) if (i != r->pl_idx) o += sprintf(o, "%s%s", o > hf ? ":" : "", keys[i]);
+                for (int i = 0; i < nk; ++i) if (i != r->pl_idx && !(kjob && kjob[i] >= 0)) o += sprintf(o, "%s%s", o > hf ? ":" : "", keys[i]);
                 if (called && gp) o += sprintf(o, "%sGP", o > hf ? ":" : "");
                 if ((nhost = vio_encode_keys(hdr, hf, ln_buf + head_end, S, &hblk, &hblk_cap, kend)) != host_keys) DIE("%s\n", nhost < 0 ? vio_error() : "FORMAT keys lost on the way");
                 free(hf);
             }
             const uint64_t *ko = koff + (size_t)k * BCFGPU_CALL_BCF_NKEYS;
-            const size_t need = (size_t)(ko[BCFGPU_CALL_BCF_NKEYS] - ko[0]) + (nhost ? kend[nhost - 1] : 0);
+            size_t need = (size_t)(ko[BCFGPU_CALL_BCF_NKEYS] - ko[0]) + (nhost ? kend[nhost - 1] : 0);
+            for (int i = 0; kjob && i < nk; ++i) if (kjob[i] >= 0) need += (size_t)(poff[kjob[i] + 1] - poff[kjob[i]]);
             if (need > iblk_cap) { iblk_cap = need * 2 + 256; iblk = realloc(iblk, iblk_cap); if (!iblk) DIE("out of memory\n"); }
             size_t il = 0; int hk = 0;
             #define PUT_DEV(i) do { memcpy(iblk + il, kblk + ko[i], (size_t)(ko[(i) + 1] - ko[i])); il += (size_t)(ko[(i) + 1] - ko[i]); } while (0)
             #define PUT_HOST() do { const size_t b0 = hk ? kend[hk - 1] : 0; memcpy(iblk + il, hblk + b0, kend[hk] - b0); il += kend[hk] - b0; ++hk; } while (0)
+            #define PUT_KEY(j) do { memcpy(iblk + il, pblk + poff[j], (size_t)(poff[(j) + 1] - poff[j])); il += (size_t)(poff[(j) + 1] - poff[j]); } while (0)
             PUT_DEV(BCFGPU_CALL_BCF_GT);
-            for (int i = 0; i < nk; ++i) { if (i == r->pl_idx) PUT_DEV(BCFGPU_CALL_BCF_PL); else PUT_HOST(); }
+            for (int i = 0; i < nk; ++i) { if (i == r->pl_idx) PUT_DEV(BCFGPU_CALL_BCF_PL); else if (kjob && kjob[i] >= 0) PUT_KEY(kjob[i]); else PUT_HOST(); }
             if (called && gp) PUT_HOST();
             PUT_DEV(BCFGPU_CALL_BCF_GQ);
             #undef PUT_DEV
             #undef PUT_HOST
+            #undef PUT_KEY
             if (vio_write_record_indiv(fout, hdr, ln_buf, iblk, il)) DIE("%s\n", vio_error());
             rewind(LN);
             free(keys); free(fmt);
@@ -1126,6 +1193,7 @@ int main(int argc, char **argv)
     if (want_timing) fprintf(stderr, "[bcfgpu_call] seconds: reading records %.3f, building the planes on the host %.3f, uploads and device stages %.3f, writing records %.3f\n", t_read, t_planes, t_dev, t_write);
     if (want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", dev_in ? n : 0);
     if (want_timing) fprintf(stderr, "[bcfgpu_call] device records: %d records' FORMAT blocks encoded on the device\n", n_enc);
+    if (want_timing && keys_given) fprintf(stderr, "[bcfgpu_call] device keys: %ld pass-through key blocks made on the device, %ld on the host\n", n_pjob, n_phost);
     bcfgpu_destroy(ctx);
     return 0;
 }

@@ -809,6 +809,10 @@ int vio_hdr_fmt_id(const vio_hdr *h, const char *id)
     const int d = dict_find(h, id, strlen(id));
     return d >= 0 && h->dict[d].fmt_type != T_NONE ? d : -1;
 }
+int vio_hdr_fmt_type(const vio_hdr *h, int dict)
+{
+    return dict >= 0 && dict < h->n_dict && h->dict[dict].id ? h->dict[dict].fmt_type : -1;      /* T_* are VIO_TYPE_*, T_NONE is -1 */
+}
 int vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, const void *indiv, size_t l_indiv)
 {
     if (!f->bcf) return fail("a ready per-sample block can only go into a BCF file");

@@ -45,6 +45,11 @@ int  vio_write_record_int(vio_file *f, const vio_hdr *h, const char *head, int n
 /* The dictionary index encode_record writes for FORMAT key `id` (what a device-side encoder puts in front of the key's values), or -1
  * when the header declares no such FORMAT key. */
 int  vio_hdr_fmt_id(const vio_hdr *h, const char *id);
+/* The Type the header declares for the FORMAT key at dictionary index `dict` (vio_indiv_key.dict, vio_hdr_fmt_id): VIO_TYPE_*, or -1
+ * when the index is outside the dictionary or no FORMAT line declares the key.  What a writer needs to know before it takes a key's
+ * stored integers for integers (bcfgpu_call_remap_bcf). */
+enum { VIO_TYPE_FLAG = 0, VIO_TYPE_INT = 1, VIO_TYPE_FLOAT = 2, VIO_TYPE_STR = 3 };
+int  vio_hdr_fmt_type(const vio_hdr *h, int dict);
 /* A BCF record whose per-sample part is encoded already (bcfgpu_mplp_encode_bcf): `head` as for vio_write_record_int -- the shared part
  * is encoded from it as for every other record, n_fmt being the number of keys in its FORMAT column and n_sample the header's --, then
  * the l_indiv bytes of `indiv` as they are.  BCF output only: -1 on a text file. */

@@ -31,6 +31,8 @@
  *                                           and the writer's typed-value encoder, for GT, PL and GQ of the call records
  *    bcfgpu_call_decode_bcf              <- the bcf_get_format_int32 calls of mcall() (mcall.c:1444, :1475) and the unpacking of the
  *                                           per-sample block behind them: FORMAT/PL and AD / QS of BCF records as the planes of bcfgpu_call_in
+ *    bcfgpu_call_remap_bcf               <- mcall_trim_and_update_numberR (mcall.c:1196-1265), bcf_subset's sample choice and the writer's
+ *                                           typed-value encoder, for the integer FORMAT keys a call record passes through (AD, DP, SP, ...)
  *
  *  Memory model: all bulk arrays are *device* pointers (HBM).  Hosts that do
  *  not link HIP use bcfgpu_malloc/free/memcpy_*.  Kernels are enqueued on the
@@ -738,6 +740,55 @@ enum { BCFGPU_CALL_BCF_GT, BCFGPU_CALL_BCF_PL, BCFGPU_CALL_BCF_GQ, BCFGPU_CALL_B
 int  bcfgpu_call_encode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_gt_max, const bcfgpu_call_out *planes,
                             const int32_t key_id[BCFGPU_CALL_BCF_NKEYS], const uint8_t *d_emit,
                             void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
+
+/* The keys the caller passes through: the integer FORMAT keys of the input records other than PL (AD, ADF, ADR, DP, SP, ...) as the BCF2
+ * key blocks of the written records, made on the device from the input records' bytes (bcfkeys.hip) -- what
+ * mcall_trim_and_update_numberR (mcall.c:1196-1265) does to the Number=R keys of a record that lost alleles, and the writer's typed-value
+ * encoder (host/vcfio.c enc_vint) to every key.  One job a key and record; the blocks are complete in themselves (typed key id,
+ * descriptor, values, by the rules above bcfgpu_mplp_encode_bcf) and have an offset each, so that a writer puts them between the blocks
+ * of bcfgpu_call_encode_bcf and its own.  The rule is the text route's (host/vcfio.c vio_indiv_text, the record loop of
+ * host/bcfgpu_call.c with print_numberR, host/vcfio.c encode_fmt_key / enc_vint), byte for byte.  For job j with k = keys[j].site,
+ * nn = d_site[k].nals_new and map = d_site[k].als_map, called sample s reads input sample col ? col[s] : s:
+ *     vector   the sample's `width` values widened as bcfgpu_call_decode_bcf widens them, cut at the first `end of vector`; an empty one
+ *              (type 0, width 0, a vector that ends at once) is the one value `missing`, the '.' of the text
+ *     remap    when flags & 1 and nn != nals and the vector has nals values: [v[0]] when nn == 1, else nn values `missing` with
+ *              out[map[i]] = v[i] for every i < nals with map[i] >= 0.  In every other case the vector stays as it is (an R key whose
+ *              sample has not one value per allele included)
+ *     width    the longest vector over the called samples; shorter ones are padded with `end of vector`
+ *     type     int8 when every output value that is no sentinel lies in -120 .. 127, int16 when in -32760 .. 32767, else int32
+ *              (enc_vint); an all-sentinel key is int8; missing / end of vector are 0x80 / 0x81, 0x8000 / 0x8001 or the int32 sentinels
+ *     block    the typed key id, the descriptor (width >= 15: 0xF0 | type, then the width as a typed int8 or, from 128 on, int16), the
+ *              values sample-major
+ * Width and type are the output's: either can be smaller than the input's (the only large value sat on a dropped allele; an input that
+ * was not minimally encoded).
+ *   keys     HOST [n_keys], in the order of the blocks
+ *   d_indiv  DEVICE, n_indiv_bytes: the input records' per-sample blocks, as for bcfgpu_call_decode_bcf
+ *   col      HOST [cfg.n_smpl] or NULL: the input sample of each called sample (NULL: called sample s is input sample s)
+ *   d_site   DEVICE [n_sites]: the site records of bcfgpu_mcall (nals_new and als_map are read)
+ *   d_emit   DEVICE [n_sites], 0 = the site has no record: its keys' blocks have zero length; NULL = every site has one
+ *   d_buf    DEVICE, cap_bytes: the blocks back to back in the order of keys[]
+ *   d_off    DEVICE [n_keys + 1], 8-byte aligned: d_off[j] = the start of block j, d_off[n_keys] = the size of all.  Set whether or not
+ *            the blocks fit
+ *   n_bytes  HOST, out: the size of all blocks
+ * When the blocks do not fit cap_bytes nothing is written to d_buf, *n_bytes is the size needed and the call returns BCFGPU_E_RANGE
+ * (cap_bytes = 0 asks for the size).  BCFGPU_E_ARG, checked on the host before anything runs: NULL pointers, a type outside 0-3, a width
+ * outside 0 .. BCFGPU_BCF_KEY_MAX_WIDTH, a site outside [0, n_sites), a negative key id, nals outside 1 .. 5 with flags & 1, a col entry
+ * outside [0, n_smpl_in); BCFGPU_E_RANGE when off + n_smpl_in * width * size passes n_indiv_bytes; nothing is written in either case.
+ * n_keys == 0 is valid.  Runs on the context's stream and synchronises it. */
+#define BCFGPU_BCF_KEY_MAX_WIDTH 255
+typedef struct {            /* one pass-through key of one record; 32 bytes */
+    uint64_t off;           /* byte offset in the indiv buffer of value [input sample 0][0] */
+    int32_t  site;          /* index into d_site / d_emit */
+    int32_t  key_id;        /* the key's index in the writer's header dictionary */
+    int32_t  type;          /* 0 (no values), 1 int8, 2 int16, 3 int32 */
+    int32_t  width;         /* values a sample in the input, 0 .. BCFGPU_BCF_KEY_MAX_WIDTH */
+    int32_t  nals;          /* alleles of the input record */
+    int32_t  flags;         /* bit 0: the header declares the key Number=R */
+} bcfgpu_bcf_key;
+int  bcfgpu_call_remap_bcf(bcfgpu_ctx *ctx, int32_t n_keys, const bcfgpu_bcf_key *keys, int32_t n_smpl_in,
+                           const void *d_indiv, uint64_t n_indiv_bytes, const int32_t *col,
+                           const bcfgpu_call_site *d_site, int32_t n_sites, const uint8_t *d_emit,
+                           void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
 
 /* One communicator over the contexts of a node, rank i = ctxs[i] (RCCL ncclCommInitAll; every context on its own device;
  * librccl is loaded at this call, a single context needs none). */

@@ -460,7 +460,7 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
         for (int wgs = 6; wgs >= 3 && !cap; --wgs) {
             const long budget = (long)(128 / wgs) * 1280 - 32;
             long c = (budget - (long)glfgen_lds_bytes(0, g.hist_slots)) / 2;
-            c = std::min(c & ~15L, 16384L);
+            c = std::min(c & ~15L, (long)GLF_MAX_WINDOW);
             if (c >= want || wgs == 3) cap = (int)std::max(c, 2048L);     // the whole window of the tier: `want` only chooses the tier
         }
         g.lds_cap = cap;

@@ -46,7 +46,7 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
     return v;
 }
 
-// LDS layout (bytes): fk[264] f64 | slots[NSLOT][WG] u32 (a dword per quality rank) | hist [slots][HP_SIZE] 2 x u16 | site totals [slots][SITE_NSUM] u64 | keys u16[cap+8]
+// LDS layout (bytes): fk[264] f64 | slots[NSLOT][WG] u32 (a dword per quality rank) | hist [slots][HP_SIZE] 2 x u16 (the workgroup of a listed deep cell: [H_SIZE] i32) | site totals [slots][SITE_NSUM] u64 | keys u16[cap+8]
 #define LDS_FK   0
 #define LDS_CNT  2112
 #ifndef NRANK
@@ -57,12 +57,24 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 #define FU       4         // source elements per trip of the slot counting
 #endif
 #define LDS_HIST_OFF (LDS_CNT + NSLOT * WG * 4)
-// The workgroup's copy of a site's bias-test histograms, two 16-bit counters per dword (a workgroup has fewer than 2^16
-// reads): dword i < 220 = bin i of the REF arrays (kernels.h: POS, MQ, BQ) in the low half and of the ALT arrays in the high
-// half; dword 220 + mq = the forward- and the reverse-strand mapQ histogram.  Half the LDS of plain counters, and the
-// REF / ALT choice is the increment instead of an address.
+// The workgroup's copy of a site's bias-test histograms, two 16-bit counters per dword: dword i < 220 = bin i of the REF arrays
+// (kernels.h: POS, MQ, BQ) in the low half and of the ALT arrays in the high half; dword 220 + mq = the forward- and the
+// reverse-strand mapQ histogram.  Half the LDS of plain counters, and the REF / ALT choice is the increment instead of an
+// address.
+// A half holds 65 535.  A workgroup's span can have more reads than that in one bin (256 cells of 257 reads with mapQ 60 will
+// do: cells past 255 reads count every read), so the copy is added to the global histograms and cleared whenever the reads
+// staged since it was last cleared, plus the window of the round that begins, could pass HP_MAX: a read adds at most one to
+// a half, so no half passes HP_MAX (a window is at most GLF_MAX_WINDOW reads, kernels.h: csrc/api.hip sizes it).  The count
+// is kept in LDS (s_pend) and looked at between two rounds, by every lane alike: a workgroup of one round, the rule, pays
+// one store for it.  The mapQ >= 59 bins, which take whole rounds' counts at once, are not kept here: they go to the
+// global histograms from the partial sums, as 32-bit counts.  The workgroup of a listed deep cell (one cell, one site,
+// its reads in a single round of any length) keeps plain 32-bit counters in the same LDS, laid out as a site's global
+// histograms.  (tests/test_gpu_site_stats.py: bins of exactly 65 535, 65 536 and up to 80 000 reads in every form.)
 #define HP_SIZE 280
 #define HP_MQS  220
+#define HP_MAX  0xffffu
+static_assert(GLF_MAX_WINDOW <= HP_MAX, "one round's window alone must fit a 16-bit half of the packed histograms");
+static_assert(H_SIZE <= 2 * HP_SIZE, "a deep cell's 32-bit histograms take the LDS of two packed slots (hist_slots >= 2 whenever it is not 0)");
 // per-lane partial sums of phase A: the I16 site totals anno[4..15], ori_depth and mq0 (site_sums[0..13]), then the reads of
 // mapQ >= 59: all, REF base, reverse strand (the mapQ 59 bins of the four mapQ histograms).  csrc/api.hip sizes part_cols by it.
 #define NPART 17
@@ -292,7 +304,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
     const int pcol = P.part_cols;                    // columns per value: a power of two, NPART * slots * pcol <= 2048
     uint16_t *s_key = DEEP ? P.deep_keys + P.deep_list[2 * blockIdx.x + 1]
                            : reinterpret_cast<uint16_t*>(s_tot + (size_t)P.hist_slots * SITE_NSUM);
-    __shared__ unsigned int s_next, s_skip;
+    __shared__ unsigned int s_next, s_skip, s_pend;
+    constexpr bool PACKED = LDS_HIST && !DEEP;       // the histograms' LDS copy has two 16-bit counters per dword
 
     const int tid = threadIdx.x;
     const int S = P.n_smpl;
@@ -348,6 +361,23 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         if (slot >= P.deep_cap || !room) { atomicExch(P.err, BCFGPU_E_DEPTH); atomicExch(&P.deep_ctr[2], 1u); }
     }
     uint32_t base = p_off[cell0];
+    // s_pend: the reads staged since the packed histograms were last cleared, the window of the round that begins included
+    if (PACKED && tid == 0) s_pend = min((base & ~3u) + (uint32_t)cap, span_end) - base;
+
+    // the packed histograms of the workgroup's slots: added to the site's global ones and cleared
+    auto flush_packed = [&](const bool clear) {
+        const int nslot = min(P.hist_slots, P.n_sites - site0);
+        for (int i = tid; i < nslot * HP_SIZE; i += WG) {
+            const uint32_t v = (uint32_t)s_hist[i];
+            if (!v) continue;
+            if (clear) s_hist[i] = 0;
+            const int sl = i / HP_SIZE, j = i - sl * HP_SIZE;
+            int *g = P.hist + (long)(site0 + sl) * H_SIZE;
+            const int lo = j < HP_MQS ? j : H_FWD_MQS + (j - HP_MQS), hi = j < HP_MQS ? j + H_ALT_OFF : H_REV_MQS + (j - HP_MQS);
+            if (v & 0xffffu) atomicAdd(&g[lo], (int)(v & 0xffffu));
+            if (v >> 16) atomicAdd(&g[hi], (int)(v >> 16));
+        }
+    };
 
     for (;;) {
         const uint32_t abase = base & ~3u;                       // key index 0 of this round
@@ -471,7 +501,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                     const bool isref = !((nref80 >> (8 * u + 7)) & 1), rev = (F4 >> (8 * u + 4)) & 1;
                     const uint32_t bq = byte_at(B4, u), mapQ = byte_at(Mf4, u), pos = byte_at(e4, u);
                     const bool m59 = (m59_80 >> (8 * u + 7)) & 1;
-                    if (LDS_HIST) {
+                    if (PACKED) {
                         const int inc = isref ? 1 : 0x10000;
                         atomicAdd(&hist[H_REF_POS + pos], inc);
                         atomicAdd(&hist[H_REF_BQ + min(bq, 59u)], inc);
@@ -568,12 +598,12 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                 if ((i & 3) == 0 && x) {
                     const int vi = i >> 2, sl = vi / NPART, j = vi % NPART;
                     if (j < SITE_NSUM) s_tot[sl * SITE_NSUM + j] += x;
-                    else {                                   // the mapQ 59 bins, REF | ALT << 16 and forward | reverse << 16:
-                        const uint32_t c = (uint32_t)x;      // every count adds its share (mod 2^32; the dword's sum is exact)
-                        int *h = s_hist + sl * HP_SIZE;
-                        if (j == SITE_NSUM) { atomicAdd(&h[H_REF_MQ + 59], (int)(c << 16)); atomicAdd(&h[HP_MQS + 59], (int)c); }
-                        else if (j == SITE_NSUM + 1) atomicAdd(&h[H_REF_MQ + 59], (int)(c - (c << 16)));
-                        else atomicAdd(&h[HP_MQS + 59], (int)((c << 16) - c));
+                    else {                                   // the mapQ 59 bins of the site's global histograms: all reads count as
+                        const int c = (int)(uint32_t)x;      // ALT and forward, the REF and the reverse ones are moved over
+                        int *g = P.hist + (long)(site0 + sl) * H_SIZE;
+                        if (j == SITE_NSUM) { atomicAdd(&g[H_ALT_MQ + 59], c); atomicAdd(&g[H_FWD_MQS + 59], c); }
+                        else if (j == SITE_NSUM + 1) { atomicAdd(&g[H_REF_MQ + 59], c); atomicAdd(&g[H_ALT_MQ + 59], -c); }
+                        else { atomicAdd(&g[H_REV_MQS + 59], c); atomicAdd(&g[H_FWD_MQS + 59], -c); }
                     }
                 }
             }
@@ -807,9 +837,18 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         if (!DEEP && !done && deep && beg == base) s_skip = end; // a listed cell at the head of the line: the rounds step over its reads
         __syncthreads();                                         // the slot counters are phase A's partial sums again
         if (!DEEP) {
-            const uint32_t sk = s_skip;
+            const uint32_t sk = s_skip, pend = PACKED ? s_pend : 0u;
             if (sk) { if (deep && beg == base) done = true; base = sk; }
             __syncthreads();                                     // (s_skip is cleared at the top of the round)
+            if (PACKED) {
+                // Another round: the reads it can add to a bin are at most its window.  Could a half pass HP_MAX with them, the
+                // copy is added to the global histograms and cleared first (uniform: every lane has read the same s_pend before
+                // the barrier above; the cleared dwords are seen after the barrier at the top of the round).
+                const uint32_t win = min((base & ~3u) + (uint32_t)cap, span_end) - base, p = pend + win;
+                const bool fl = p > HP_MAX;
+                if (tid == 0) s_pend = fl ? win : p;
+                if (fl) flush_packed(true);
+            }
         }
     }
 
@@ -817,13 +856,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
     if (LDS_HIST) {
         __syncthreads();
         const int nslot = min(P.hist_slots, P.n_sites - site0);
-        for (int i = tid; i < nslot * HP_SIZE; i += WG) {
-            const uint32_t v = (uint32_t)s_hist[i];
-            const int sl = i / HP_SIZE, j = i - sl * HP_SIZE;
-            int *g = P.hist + (long)(site0 + sl) * H_SIZE;
-            const int lo = j < HP_MQS ? j : H_FWD_MQS + (j - HP_MQS), hi = j < HP_MQS ? j + H_ALT_OFF : H_REV_MQS + (j - HP_MQS);
-            if (v & 0xffffu) atomicAdd(&g[lo], (int)(v & 0xffffu));
-            if (v >> 16) atomicAdd(&g[hi], (int)(v >> 16));
+        if (PACKED) flush_packed(false);
+        else {                                                   // a deep cell's site: plain counters in the global layout
+            int *g = P.hist + (long)site0 * H_SIZE;
+            for (int i = tid; i < H_SIZE; i += WG) { const int v = s_hist[i]; if (v) atomicAdd(&g[i], v); }
         }
         for (int i = tid; i < nslot * SITE_NSUM; i += WG) {
             const unsigned long long v = s_tot[i];

@@ -15,6 +15,9 @@ enum : int {
 };
 // site totals glfgen_kernel accumulates read-parallel: anno[4..15] (bam2bcf.c:221-226), then ori_depth and mq0
 enum : int { SITE_NSUM = 14 };
+// the most keys of one staging round of glfgen_kernel's tile launch (csrc/api.hip sizes the LDS window under it; the packed
+// 16-bit histogram counters of csrc/glfgen.hip rely on it)
+enum : int { GLF_MAX_WINDOW = 16384 };
 
 // per (site,sample) result of the glfgen kernel = bcf_callret1_t (bam2bcf.h:90-108), SoA planes over
 // ncells = n_sites*n_smpl.  Everything but p is an exact integer.
@@ -55,7 +58,7 @@ struct GlfgenParams {
     int n_sites, n_smpl, is_indel;
     int min_baseQ, capQ, fmt_flag;
     int hist_slots;                 // >0: per-workgroup LDS histograms with that many site slots; 0: global atomics
-    int lds_cap;                    // read keys held in LDS per workgroup round (multiple of 16, <= 16384)
+    int lds_cap;                    // read keys held in LDS per workgroup round (multiple of 16, <= GLF_MAX_WINDOW)
     int part_cols;                  // LDS columns per partial sum of phase A (power of two >= 4; NPART (17) * hist_slots * part_cols <= 2048: the slot region)
     uint32_t n_reads;               // length of rd/epos (bounds of the vector loads)
     const int8_t   *ref16;

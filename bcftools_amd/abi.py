@@ -254,6 +254,8 @@ PROTOTYPES = {
     "bcfgpu_compact_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "bcfgpu_mplp_encode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MplpOut), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bcfgpu_mplp_encode_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MplpOut), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.POINTER(C.c_uint64)]),
     "bcfgpu_call_encode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
                                          C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_call_decode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(BcfVec), C.POINTER(C.c_int32),

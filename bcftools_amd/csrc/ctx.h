@@ -91,13 +91,15 @@ enum WsSlot : int {
     // bcfgpu_call_remap_bcf (bcfkeys.hip): scratch for one call -- the uploaded copies of the key jobs and of the sample map, one packed
     // word a job (the block's integer type and width), the scan's temporary storage
     WS_COMPACT_BCFKEY_JOBS = 173, WS_COMPACT_BCFKEY_COL = 174, WS_COMPACT_BCFKEY_WORD = 175, WS_COMPACT_BCFKEY_SCAN_TMP = 176,
+    // bcfgpu_mplp_encode_vcf (vcfenc.hip): scratch for one call -- the scan's temporary storage
+    WS_COMPACT_VCF_SCAN_TMP = 177,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_COMPACT_BCFKEY_SCAN_TMP + 1     // one past the highest slot
+    WS_COUNT = WS_COMPACT_VCF_SCAN_TMP + 1     // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names
@@ -122,7 +124,8 @@ enum PinnedSlot : int {
     PIN_BCF_TOTAL = 7,                  // bcfgpu_mplp_encode_bcf: the size of all blocks
     PIN_BCFCALL_TOTAL = 8,              // bcfgpu_call_encode_bcf: the size of all blocks
     PIN_BCFKEY_TOTAL = 9,               // bcfgpu_call_remap_bcf: the size of all blocks
-    PINNED_COUNT = PIN_BCFKEY_TOTAL + 1     // one past the highest slot
+    PIN_VCF_TOTAL = 10,                 // bcfgpu_mplp_encode_vcf: the size of all blocks
+    PINNED_COUNT = PIN_VCF_TOTAL + 1        // one past the highest slot
 };
 
 // workspace / pinned host buffer `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails

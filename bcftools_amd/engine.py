@@ -346,6 +346,38 @@ class Context:
             self.release(bufs)
         return data, offs
 
+    def encode_vcf(self, planes, n_sites, emit=None, cap_bytes=None):
+        """bcfgpu_mplp_encode_vcf on planes already in HBM (an abi.MplpOut of device pointers): the records' sample columns as VCF
+        text.  emit: host u8 [n_sites] or None; cap_bytes: the buffer's size (None: asked from the size pass first).  Returns
+        (bytes as np.uint8, offsets as np.uint64 [n_sites + 1]); BcfGpuError with code E_RANGE and .needed = the size when
+        cap_bytes is too small."""
+        off, n = self.buf(8 * (n_sites + 1)), C.c_uint64(0)
+        bufs = [off]
+        d_emit = None
+        if emit is not None:
+            bufs.append(self.to_device(np.ascontiguousarray(emit, dtype=np.uint8)))
+            d_emit = bufs[-1].ptr
+        try:
+            if cap_bytes is None:
+                rc = self.L.bcfgpu_mplp_encode_vcf(self.h, n_sites, C.byref(planes), d_emit, None, 0, off.ptr, C.byref(n))
+                if rc not in (0, abi.E_RANGE):
+                    check(rc)
+                cap_bytes = n.value
+            out = self.buf(cap_bytes)
+            bufs.append(out)
+            rc = self.L.bcfgpu_mplp_encode_vcf(self.h, n_sites, C.byref(planes), d_emit, out.ptr, cap_bytes, off.ptr, C.byref(n))
+            if rc:
+                e = BcfGpuError(rc, self.L.bcfgpu_last_error().decode())
+                e.needed = n.value
+                raise e
+            data, offs = np.zeros(n.value, np.uint8), np.zeros(n_sites + 1, np.uint64)
+            if n.value:
+                out.download(data)
+            off.download(offs)
+        finally:
+            self.release(bufs)
+        return data, offs
+
     def encode_call_bcf(self, planes, n_sites, n_gt_max, key_id, emit=None, cap_bytes=None):
         """bcfgpu_call_encode_bcf on call planes already in HBM (an abi.CallOut of device pointers; pl and gq may be None): GT, the
         trimmed PL and GQ of the call records as BCF2 bytes, every key's block with an offset of its own.  key_id: {key name:

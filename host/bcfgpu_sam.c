@@ -10,6 +10,8 @@
  *                           stages of the current tile run; the same output
  *               --device-records  with -O u|b: the per-sample part of every SNP and indel record is encoded as BCF2 on the device
  *                           (bcfgpu_mplp_encode_bcf) and comes to the host as bytes instead of planes; the same output
+ *               --device-text  with -O v|z: the sample columns of every SNP and indel record are formatted as VCF text on the device
+ *                           (bcfgpu_mplp_encode_vcf) and come to the host as bytes instead of planes; the same output
  *               --list-samples: print "sample <TAB> reads entering the pileup <TAB> files" and stop (no device needed)
  *
  *  A region is streamed through in TILES: the files are read in step with the tiles -- a position-sorted file no
@@ -33,6 +35,7 @@
  *      bcfgpu_gap_prep_tile (bcf_call_gap_prep on the candidate columns, in HBM) -> bcfgpu_mpileup on its indel tile
  *  with -C INT: bcfgpu_pool_baq + bcfgpu_pool_cap_mapq on every batch of reads as it comes off the files (mpileup.c:234-241),
  *  with --device-records: bcfgpu_mplp_encode_bcf on the planes of both passes, the writer then frames the bytes (vio_write_record_indiv),
+ *  with --device-text: bcfgpu_mplp_encode_vcf on them, the writer then puts the bytes behind the head (vio_write_record_text),
  *  with --gvcf: bcfgpu_gvcf_blocks per tile, the block that reaches a tile's end joined with the next tile's first (gvcf.c:88-226);
  *  and the record loop writes what bcf_call2bcf (bam2bcf.c:756-906) puts in the record, in its order, under mpileup's header
  *  (mpileup.c:510-602), as VCF, bgzipped VCF or BCF (host/vcfio.c).  tests/test_c_host.py compares the whole output with the
@@ -786,8 +789,13 @@ static void put_counts(const char *lead, const int32_t *f, const int32_t *r, int
 static int device_records, dr_on;                                            /* the option; the option on a BCF output */
 static int32_t dr_key[BCFGPU_BCF_NKEYS];                                     /* the FORMAT keys' indices in the header's dictionary */
 static unsigned long long n_dev_records;                                     /* records written with a block from the device */
+/* --device-text: the sample columns of the records come from the device as VCF text (bcfgpu_mplp_encode_vcf) */
+static int device_text, dt_on;                                               /* the option; the option on a text output */
+static unsigned long long n_dev_text;                                        /* records written with sample columns from the device */
+#define DEV_ON (dr_on || dt_on)                                              /* the planes stay in HBM, the records' per-sample part comes as bytes */
 
-/* indiv != NULL: the record's per-sample part, encoded already (l_indiv bytes); the planes are not read then */
+/* indiv != NULL: the record's per-sample part, encoded (--device-records) or formatted (--device-text) already (l_indiv bytes); the
+ * planes are not read then */
 static void print_record(const char *contig, int pos1, const char *alleles, const char *prefix, const bcfgpu_site *c,
                          const planes_t *pp, size_t k, int S, const uint8_t *indiv, size_t l_indiv)
 {
@@ -831,9 +839,9 @@ static void print_record(const char *contig, int pos1, const char *alleles, cons
     if (fmt_flag & BCFGPU_FMT_QS) fputs(":QS", LN);
     if (indiv) {
         fputc(0, LN); fflush(LN);
-        if (vio_write_record_indiv(fout, hdr, ln_buf, indiv, l_indiv)) { fprintf(stderr, "%s\n", vio_error()); exit(1); }
+        if (dt_on ? vio_write_record_text(fout, hdr, ln_buf, indiv, l_indiv) : vio_write_record_indiv(fout, hdr, ln_buf, indiv, l_indiv)) { fprintf(stderr, "%s\n", vio_error()); exit(1); }
         rewind(LN);
-        ++n_dev_records;
+        if (dt_on) ++n_dev_text; else ++n_dev_records;
         return;
     }
     const int x = na * (na + 1) / 2;
@@ -869,7 +877,7 @@ static void print_record(const char *contig, int pos1, const char *alleles, cons
 
 /* bcfgpu_mpileup over a tile; the site records and the planes come back to the host.  keep_*: the device copies of the
  * site records / PL / DP4 stay allocated for the caller (--gvcf works on them), else they are freed. */
-/* dev != NULL (--device-records): only the site records come back; the planes stay in HBM for bcfgpu_mplp_encode_bcf (and --gvcf) and
+/* dev != NULL (--device-records, --device-text): only the site records come back; the planes stay in HBM for bcfgpu_mplp_encode_bcf / _vcf (and --gvcf) and
  * are the caller's to free (mplp_out_free) */
 static void mplp_out_free(bcfgpu_ctx *ctx, bcfgpu_mplp_out *mo)
 {
@@ -916,16 +924,21 @@ static void run_mpileup(bcfgpu_ctx *ctx, const bcfgpu_tile *tile, int n, bcfgpu_
 
 /* The per-sample blocks of a tile's records from the planes in HBM: the size pass tells how many bytes, the second call writes them.
  * emit: HOST [n], which sites have a record.  rec / off: HOST, malloc'ed: the blocks back to back, and where each starts. */
+static int encode_blocks(bcfgpu_ctx *ctx, int n, const bcfgpu_mplp_out *mo, const uint8_t *d_emit, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *nb)
+{
+    return dt_on ? bcfgpu_mplp_encode_vcf(ctx, n, mo, d_emit, d_buf, cap, d_off, nb)             /* VCF text for -O v|z */
+                 : bcfgpu_mplp_encode_bcf(ctx, n, mo, dr_key, d_emit, d_buf, cap, d_off, nb);    /* BCF2 for -O u|b */
+}
 static void encode_records(bcfgpu_ctx *ctx, int n, const bcfgpu_mplp_out *mo, const uint8_t *emit, uint8_t **rec, uint64_t **off)
 {
     void *d_emit, *d_off, *d_buf = NULL; uint64_t nb = 0;
     CHECK(bcfgpu_malloc(ctx, (size_t)n + 1, &d_emit)); CHECK(bcfgpu_malloc(ctx, ((size_t)n + 1) * 8, &d_off));
     CHECK(bcfgpu_memcpy_h2d(ctx, d_emit, emit, (size_t)n));
-    const int rc = bcfgpu_mplp_encode_bcf(ctx, n, mo, dr_key, d_emit, NULL, 0, d_off, &nb);
-    if (rc && rc != BCFGPU_E_RANGE) { fprintf(stderr, "bcfgpu_mplp_encode_bcf: %s (%d)\n", bcfgpu_last_error(), rc); exit(1); }
+    const int rc = encode_blocks(ctx, n, mo, d_emit, NULL, 0, d_off, &nb);
+    if (rc && rc != BCFGPU_E_RANGE) { fprintf(stderr, "%s: %s (%d)\n", dt_on ? "bcfgpu_mplp_encode_vcf" : "bcfgpu_mplp_encode_bcf", bcfgpu_last_error(), rc); exit(1); }
     if (nb) {
         CHECK(bcfgpu_malloc(ctx, nb, &d_buf));
-        CHECK(bcfgpu_mplp_encode_bcf(ctx, n, mo, dr_key, d_emit, d_buf, nb, d_off, &nb));
+        CHECK(encode_blocks(ctx, n, mo, d_emit, d_buf, nb, d_off, &nb));
     }
     *rec = malloc(nb ? nb : 1); *off = malloc(((size_t)n + 1) * 8);
     if (nb) CHECK(bcfgpu_memcpy_d2h(ctx, *rec, d_buf, nb));
@@ -1017,7 +1030,7 @@ typedef struct {
     bcfgpu_site *site, *isite; planes_t snp_planes, ind_planes;
     int32_t *g_types, *g_maxins, *g_indelreg, *g_support; float *g_frac; int8_t *g_inscns;
     int32_t *gv_blk, *gv_dp; bcfgpu_gvcf_block *gv_block; uint8_t *gv_pl;
-    uint8_t *snp_rec, *ind_rec; uint64_t *snp_off, *ind_off;      /* --device-records: the records' per-sample blocks instead of the planes */
+    uint8_t *snp_rec, *ind_rec; uint64_t *snp_off, *ind_off;      /* --device-records, --device-text: the records' per-sample blocks instead of the planes */
 } emit_job_t;
 static void emit_tile(emit_job_t *J)
 {
@@ -1272,8 +1285,8 @@ static void tile_device(tilejob_t *T, int adopted)
     bcfgpu_site *site = NULL;
     planes_t snp_planes;
     bcfgpu_mplp_out snp_dev, ind_dev; memset(&snp_dev, 0, sizeof snp_dev); memset(&ind_dev, 0, sizeof ind_dev);
-    run_mpileup(ctx, &tile, n_sites, &site, &snp_planes, gv_n ? &d_site : NULL, &d_pl, &d_dp4, dr_on ? &snp_dev : NULL);
-    if (nlive) run_mpileup(ctx, &ti, nlive, &isite, &ind_planes, NULL, NULL, NULL, dr_on ? &ind_dev : NULL);
+    run_mpileup(ctx, &tile, n_sites, &site, &snp_planes, gv_n ? &d_site : NULL, &d_pl, &d_dp4, DEV_ON ? &snp_dev : NULL);
+    if (nlive) run_mpileup(ctx, &ti, nlive, &isite, &ind_planes, NULL, NULL, NULL, DEV_ON ? &ind_dev : NULL);
     free(gret);
 
     /* ---- --gvcf: reference-only records collapse into blocks (gvcf_write, gvcf.c:88-226) on the planes still in HBM ---- */
@@ -1303,14 +1316,14 @@ static void tile_device(tilejob_t *T, int adopted)
         if (gv_blk[n_sites - 1] >= 0 && !(brk[n_sites - 1] & 1)) open_block = gv_blk[n_sites - 1];
         bcfgpu_free(ctx, d_pos); bcfgpu_free(ctx, d_brk); bcfgpu_free(ctx, d_blk); bcfgpu_free(ctx, d_min); bcfgpu_free(ctx, d_block);
         bcfgpu_free(ctx, d_gdp); bcfgpu_free(ctx, d_gpl); free(pos); free(brk);
-        if (!dr_on) { bcfgpu_free(ctx, d_site); bcfgpu_free(ctx, d_pl); bcfgpu_free(ctx, d_dp4); }       /* (--device-records: freed with the other planes below) */
+        if (!DEV_ON) { bcfgpu_free(ctx, d_site); bcfgpu_free(ctx, d_pl); bcfgpu_free(ctx, d_dp4); }      /* (--device-records, --device-text: freed with the other planes below) */
     }
 
-    /* ---- --device-records: which sites get a record is what the record loop of emit_tile decides -- not a column without reads, outside
+    /* ---- --device-records, --device-text: which sites get a record is what the record loop of emit_tile decides -- not a column without reads, outside
      * the targets or inside a gVCF block; an indel site where bcf_call_combine found an ALT allele -- and their per-sample blocks come
-     * to the host as BCF2 bytes ---- */
+     * to the host as BCF2 bytes or as VCF text ---- */
     uint8_t *snp_rec = NULL, *ind_rec = NULL; uint64_t *snp_off = NULL, *ind_off = NULL;
-    if (dr_on) {
+    if (DEV_ON) {
         uint8_t *se = calloc((size_t)n_sites + 1, 1), *ie = calloc((size_t)nlive + 1, 1);
         int jl = 0;
         for (int k = 0; k < n_sites; ++k) {
@@ -1515,7 +1528,7 @@ static int run_shards(int n_gpus, int argc0, char **argv0, int first_file, const
             if (!strcmp(o, "-o")) { char *e; strtol(argv0[i + 1], &e, 10); if (*e) { ++i; continue; } }
             if (o[0] != '-') break;                              /* the positional form: ref.fa contig beg end come from -f / -r below */
             av[n++] = argv0[i];
-            if (o[0] == '-' && i + 1 < first_file && argv0[i + 1][0] != '-' && strcmp(o, "-B") && strcmp(o, "-E") && strcmp(o, "-A") && strcmp(o, "-p") && strcmp(o, "-I") && strcmp(o, "-6") && strcmp(o, "--illumina1.3+") && strcmp(o, "--timing") && strcmp(o, "--prefetch") && strcmp(o, "--device-records") && strcmp(o, "-x") && strcmp(o, "--ignore-overlaps") && strcmp(o, "--no-version")
+            if (o[0] == '-' && i + 1 < first_file && argv0[i + 1][0] != '-' && strcmp(o, "-B") && strcmp(o, "-E") && strcmp(o, "-A") && strcmp(o, "-p") && strcmp(o, "-I") && strcmp(o, "-6") && strcmp(o, "--illumina1.3+") && strcmp(o, "--timing") && strcmp(o, "--prefetch") && strcmp(o, "--device-records") && strcmp(o, "--device-text") && strcmp(o, "-x") && strcmp(o, "--ignore-overlaps") && strcmp(o, "--no-version")
                 && strcmp(o, "--ignore-RG") && strcmp(o, "--list-samples")) av[n++] = argv0[++i];
         }
         av[n++] = "-f"; av[n++] = (char *)ref_path; av[n++] = "-r"; av[n++] = rl;
@@ -1644,6 +1657,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[1], "--timing")) { want_timing = 1; argv += 1; argc -= 1; }
         else if (!strcmp(argv[1], "--prefetch")) { prefetch = 1; argv += 1; argc -= 1; }
         else if (!strcmp(argv[1], "--device-records")) { device_records = 1; argv += 1; argc -= 1; }
+        else if (!strcmp(argv[1], "--device-text")) { device_text = 1; argv += 1; argc -= 1; }
         else if (!strcmp(argv[1], "--tile")) { tile_cols = atoi(argv[2]); if (tile_cols < 1) DIE("--tile: at least one column\n"); argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-d")) { max_depth = atoi(argv[2]); argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-s")) { add_samples(argv[2], 0); argv += 2; argc -= 2; }            /* mpileup.c:1058-1059,1087,1016 */
@@ -1810,6 +1824,8 @@ int main(int argc, char **argv)
         if (!LN) DIE("open_memstream failed\n");
         /* --device-records: BCF output only (text is formatted from the planes on the host) */
         dr_on = device_records && (out_mode == 'u' || out_mode == 'b');
+        /* --device-text: text output only (BCF has --device-records) */
+        dt_on = device_text && (out_mode == 'v' || out_mode == 'z');
         if (dr_on) {
             static const char *key[BCFGPU_BCF_NKEYS] = { "PL", "DP", "DV", "SP", "DP4", "ADF", "ADR", "AD", "DPR", "SCR", "QS" };
             for (int i = 0; i < BCFGPU_BCF_NKEYS; ++i) { dr_key[i] = vio_hdr_fmt_id(hdr, key[i]); if (dr_key[i] < 0) dr_key[i] = 0; }     /* (a key the flags do not select is not read) */
@@ -1938,6 +1954,7 @@ int main(int argc, char **argv)
             n_reads_tot, S, tot_pairs, tot_entries, n_cols_tot, n_tiles, tile_cols);
     if (want_timing) fprintf(stderr, "[bcfgpu_sam] seconds: reading and parsing the files %.3f, tile pools %.3f, device stages %.3f, writing records %.3f, waiting in bcfgpu_pool_adopt %.3f\n", t_read, t_pool, t_dev, t_emit, t_adopt);
     if (want_timing) fprintf(stderr, "[bcfgpu_sam] device records: %llu records with their FORMAT block encoded on the device\n", n_dev_records);
+    if (want_timing && device_text) fprintf(stderr, "[bcfgpu_sam] device text: %llu records with their sample columns formatted on the device\n", n_dev_text);
     if (vio_close(fout)) DIE("%s\n", vio_error());
     if (ctx) bcfgpu_destroy(ctx);
     if (cap_ctx) bcfgpu_destroy(cap_ctx);
@@ -1946,7 +1963,7 @@ int main(int argc, char **argv)
 usage:
     fprintf(stderr, "usage: bcfgpu_sam [-a TAG,..] [--gvcf INT,..] [-O v|z|u|b] [-o out] [-d INT] [-s LIST | -S FILE] [-G FILE] [--ignore-RG]\n"
                     "                  [-B | -E] [-6] [-x] [-A] [-q INT] [-Q INT] [-C INT] [--ff INT] [--rf INT] [-I] [-o INT] [-e INT] [-h INT] [-m INT] [-F FLOAT] [-p] [-L INT]\n"
-                    "                  [--tile COLUMNS] [--gpus N] [--prefetch] [--device-records]\n"
+                    "                  [--tile COLUMNS] [--gpus N] [--prefetch] [--device-records] [--device-text]\n"
                     "                  -f ref.fa [-r CHR[:BEG[-END]],... | -R FILE] [-b FILE] file.sam|file.bam [...]      (as `bcftools mpileup`)\n"
                     "              or  ref.fa contig beg end file.sam|file.bam [...]                    (beg, end 1-based inclusive)\n");
     return 2;

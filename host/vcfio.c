@@ -821,6 +821,17 @@ int vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, cons
     if (encode_record(h, head, &f->rec, 0, NULL, NULL, indiv, l_indiv)) return -1;
     return out_bytes(f, f->rec.s, f->rec.l);
 }
+int vio_write_record_text(vio_file *f, const vio_hdr *h, const char *head, const void *text, size_t l_text)
+{
+    (void)h;
+    if (f->bcf) return fail("ready sample columns can only go into a text file");
+    if (!text && l_text) return fail("no sample columns");
+    f->rec.l = 0;
+    sb_put(&f->rec, head, strlen(head));
+    if (l_text) sb_put(&f->rec, text, l_text);
+    sb_putc(&f->rec, '\n');
+    return out_bytes(f, f->rec.s, f->rec.l);
+}
 int vio_encode_keys(const vio_hdr *h, const char *fmt, const char *samples, int n_sample, char **out, size_t *cap, size_t *key_end)
 {
     int fkey[64], n_fmt = 0;

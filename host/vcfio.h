@@ -54,6 +54,10 @@ int  vio_hdr_fmt_type(const vio_hdr *h, int dict);
  * is encoded from it as for every other record, n_fmt being the number of keys in its FORMAT column and n_sample the header's --, then
  * the l_indiv bytes of `indiv` as they are.  BCF output only: -1 on a text file. */
 int  vio_write_record_indiv(vio_file *f, const vio_hdr *h, const char *head, const void *indiv, size_t l_indiv);
+/* The mirror for text: a VCF record whose sample columns are formatted already (bcfgpu_mplp_encode_vcf): `head` as for
+ * vio_write_record_int, then the l_text bytes of `text` ("\t...\t...", what vio_write_record_int's text branch appends after the head)
+ * as they are, then the newline.  Text output ('v', 'z') only: -1 with a message on a BCF file. */
+int  vio_write_record_text(vio_file *f, const vio_hdr *h, const char *head, const void *text, size_t l_text);
 /* FORMAT keys as BCF2 key blocks, without a record around them: `fmt` = the keys as in a FORMAT column ("AD:DP"), `samples` = the
  * n_sample sample columns holding those keys' values, tab separated ("1,2:3\t0,0:1"; a column that ends early has '.' for the rest).
  * Every key's block -- typed key id, descriptor, values, exactly the bytes vio_write_line puts into a record's per-sample part for that

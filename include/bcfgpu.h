@@ -27,6 +27,7 @@
  *    bcfgpu_pipeline                     <- the `mpileup -Ou | call -m` pipe with PL/QS/I16 kept in HBM
  *    bcfgpu_mplp_encode_bcf              <- the bcf_update_format_int32 calls of bcf_call2bcf (bam2bcf.c:845-903) and the typed-value
  *                                           encoding bcf_write does to them: the per-sample part of an mpileup record as BCF2 bytes
+ *    bcfgpu_mplp_encode_vcf              <- the same calls and the text vcf_format writes for them: the sample columns of an mpileup record
  *    bcfgpu_call_encode_bcf              <- bcf_update_genotypes / bcf_update_format_int32 of mcall() (mcall.c:1158-1194, :1583, :1618-1623)
  *                                           and the writer's typed-value encoder, for GT, PL and GQ of the call records
  *    bcfgpu_call_decode_bcf              <- the bcf_get_format_int32 calls of mcall() (mcall.c:1444, :1475) and the unpacking of the
@@ -690,6 +691,20 @@ enum { BCFGPU_BCF_PL, BCFGPU_BCF_DP, BCFGPU_BCF_DV, BCFGPU_BCF_SP, BCFGPU_BCF_DP
        BCFGPU_BCF_AD, BCFGPU_BCF_DPR, BCFGPU_BCF_SCR, BCFGPU_BCF_QS, BCFGPU_BCF_NKEYS };
 int  bcfgpu_mplp_encode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, const bcfgpu_mplp_out *planes, const int32_t key_id[BCFGPU_BCF_NKEYS],
                             const uint8_t *d_emit, void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
+
+/* The same records' per-sample part as VCF text (vcfenc.hip): for every emitted site exactly the bytes the text writer appends after
+ * the record's first nine columns (host/vcfio.c vio_write_record_int, its text branch; vcf_format of htslib vcf.c) for the integer
+ * arrays bcf_call2bcf hands over (bam2bcf.c:845-903).  Per sample, in sample order: a tab, then the keys' values joined by ':', a
+ * key's values joined by ',', every value in decimal without leading zeros.  No newline: the writer adds it
+ * (host/vcfio.c vio_write_record_text).  Keys, order, widths and values are those of bcfgpu_mplp_encode_bcf above: PL and the keys
+ * cfg.fmt_flag selects, in the order of BCFGPU_BCF_*; all values are >= 0 and no sentinel occurs ('.' is never written); QS, the only
+ * int32 plane, reaches ten digits.  A plane no selected key reads may be NULL and is not read.
+ * d_emit, d_buf, cap_bytes, d_off and n_bytes are as for bcfgpu_mplp_encode_bcf: the blocks lie back to back in site order, each
+ * starting at whatever byte the one before ended; d_off [n_sites + 1] is set whether or not the blocks fit; when they do not fit
+ * cap_bytes nothing is written to d_buf, *n_bytes is the size needed and the call returns BCFGPU_E_RANGE (cap_bytes = 0 asks for the
+ * size).  n_sites == 0 is valid.  All offsets are 64-bit.  Runs on the context's stream and synchronises it. */
+int  bcfgpu_mplp_encode_vcf(bcfgpu_ctx *ctx, int32_t n_sites, const bcfgpu_mplp_out *planes, const uint8_t *d_emit,
+                            void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
 
 /* The other end of the pipe: one FORMAT key's integer vectors of n_sites BCF records as int32 planes [site][plane][called sample], the
  * layout of bcfgpu_call_in.pl / .ad, made on the device from the records' per-sample blocks as the file holds them (bcfdec.hip).

@@ -618,6 +618,7 @@ __attribute__((constructor)) static void bcfgpu_runtime_knobs() { setenv("GPU_MA
 namespace bcfgpu {
 
 int bcfgpu_set_error(int code, const char *what) { return set_err(code, what); }
+int bcfgpu_set_error(int code, const char *name, const char *what) { return set_err(code, (std::string(name) + ": " + what).c_str()); }
 
 bcfgpu_gap_stats *bcfgpu_internal_gap_stats(bcfgpu_ctx *c) { return &c->gap; }
 DrawState *bcfgpu_internal_draw_state(bcfgpu_ctx *c) { return &c->draw; }

@@ -4,18 +4,15 @@
 // n_smpl_in x width little-endian integers of 1, 2 or 4 bytes, sample-major, starting at any byte; the planes want them widened to
 // int32 and along samples ([sample][value] -> [plane][sample]).
 //
-//   bcf_decode_kernel  one workgroup a site: the run in slices of samples -- whole 16-byte lines of the slice come into LDS, a lane a
-//                      line, consecutive lanes consecutive addresses (the bytes before the first and after the last whole line one
-//                      by one); the slice sits in LDS at the offset its first byte has inside a 16-byte line, so that the aligned
-//                      lines of both coincide.  Then a lane a called sample: its values out of LDS, the sentinel rule of the text
-//                      route (host/vcfio.c dec_int, then the parse of host/bcfgpu_call.c), 4-byte stores to consecutive addresses
-//                      of each plane.  The planes past the record's width are filled in the same pass.
+//   bcf_decode_kernel  one workgroup a site: the run in slices of samples -- a slice comes into LDS 16 bytes a lane, consecutive lanes
+//                      consecutive addresses, from any byte it starts at (line_load, bcfcodec.h).  Then a lane a called sample:
+//                      its values out of LDS, the sentinel rule of the text route (host/vcfio.c dec_int, then the parse of
+//                      host/bcfgpu_call.c), 4-byte stores to consecutive addresses of each plane.  The planes past the
+//                      record's width are filled in the same pass.
 //                      With a sample map (col) the lanes are the called samples and every slice is one pass over them: a lane
 //                      whose input sample lies in the slice takes it from LDS, the others wait for theirs.
-//                      A sample wider than the stage (width x size > DEC_SLICE: no mpileup record) is read from global memory.
-#include <hip/hip_runtime.h>
-#include <cstdint>
-#include "ctx.h"
+//                      A sample wider than the stage (width x size > COD_SLICE: no mpileup record) is read from global memory.
+#include "bcfcodec.h"
 
 using namespace bcfgpu;
 
@@ -27,87 +24,56 @@ static_assert(sizeof(bcfgpu_bcf_vec) == 16, "bcfgpu_bcf_vec is 16 bytes");
 
 namespace bcfgpu {
 
-constexpr int DEC_THREADS = 256;
-constexpr int DEC_LINE = 16;                                    // bytes a lane loads at once
-constexpr int DEC_SLICE = BCFGPU_MAX_PL * 4 * 256;              // payload bytes of a slice in LDS: 256 samples of the widest PL as int32
-
-// one value, widened (dec_int: the smallest two values of int8 and int16 are `missing` and `end of vector`)
-__device__ __forceinline__ int32_t dec_value(const unsigned char *q, int es, bool aligned)
-{
-    if (es == 1) { const int32_t v = (int8_t)*q; return v == -128 ? BCFGPU_INT32_MISSING : v == -127 ? BCFGPU_INT32_VECTOR_END : v; }
-    if (es == 2) {
-        const int32_t v = aligned ? (int32_t)*reinterpret_cast<const int16_t*>(q) : (int32_t)(int16_t)(uint16_t)(q[0] | q[1] << 8);
-        return v == -32768 ? BCFGPU_INT32_MISSING : v == -32767 ? BCFGPU_INT32_VECTOR_END : v;
-    }
-    if (aligned) return *reinterpret_cast<const int32_t*>(q);
-    return (int32_t)((uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24);
-}
-
 // the planes of one called sample: o = plane 0 at that sample, p = the sample's first value, wr = values to read
 __device__ __forceinline__ void dec_sample(int32_t *o, size_t S, int n_planes, const unsigned char *p, int wr, int es, bool aligned)
 {
     bool ended = false;
     for (int j = 0; j < n_planes; ++j) {
         int32_t x = BCFGPU_INT32_VECTOR_END;
-        if (j < wr && !ended) { x = dec_value(p + j * es, es, aligned); ended = x == BCFGPU_INT32_VECTOR_END; }
+        if (j < wr && !ended) { x = get_int(p + j * es, es, aligned); ended = x == BCFGPU_INT32_VECTOR_END; }
         if (j == 0 && x == BCFGPU_INT32_VECTOR_END) x = BCFGPU_INT32_MISSING;       // an empty vector is '.'
         o[(size_t)j * S] = x;
     }
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void bcf_decode_kernel(const unsigned char *indiv, const bcfgpu_bcf_vec *vec, const int32_t *col,
+__global__ __launch_bounds__(COD_THREADS) void bcf_decode_kernel(const unsigned char *indiv, const bcfgpu_bcf_vec *vec, const int32_t *col,
                                                                  int n_smpl_in, int n_smpl, int n_planes, int32_t *out)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char stage[DEC_LINE + DEC_SLICE];
+    __shared__ __attribute__((aligned(16))) unsigned char stage[COD_LINE + COD_SLICE];
     const int k = blockIdx.x, tid = threadIdx.x;
     const bcfgpu_bcf_vec v = vec[k];
     const size_t S = (size_t)n_smpl;
     int32_t *o = out + (size_t)k * n_planes * S;
-    const int es = v.type == 3 ? 4 : v.type, w = v.type ? v.width : 0, wr = w < n_planes ? w : n_planes;
+    const int es = elem_bytes(v.type), w = v.type ? v.width : 0, wr = w < n_planes ? w : n_planes;
     if (wr == 0) {                                                          // no such key, or no values: '.'
-        for (int s = tid; s < n_smpl; s += DEC_THREADS) dec_sample(o + s, S, n_planes, nullptr, 0, 1, true);
+        for (int s = tid; s < n_smpl; s += COD_THREADS) dec_sample(o + s, S, n_planes, nullptr, 0, 1, true);
         return;
     }
     const size_t per = (size_t)w * es;                                      // bytes a sample
     const unsigned char *run = indiv + v.off;
     const bool aligned = ((uintptr_t)run & (es - 1)) == 0;                  // per is a multiple of es: every value of the run alike
-    const int slice = per > DEC_SLICE ? 0 : (int)(DEC_SLICE / per);         // samples a slice
+    const int slice = per > COD_SLICE ? 0 : (int)(COD_SLICE / per);         // samples a slice
     if (slice == 0 || (BCFDEC_COL_GLOBAL && col && slice < n_smpl_in)) {
-        for (int s = tid; s < n_smpl; s += DEC_THREADS) dec_sample(o + s, S, n_planes, run + (size_t)(col ? col[s] : s) * per, wr, es, aligned);
+        for (int s = tid; s < n_smpl; s += COD_THREADS) dec_sample(o + s, S, n_planes, run + (size_t)(col ? col[s] : s) * per, wr, es, aligned);
         return;
     }
     for (int s0 = 0; s0 < n_smpl_in; s0 += slice) {
         const int cs = n_smpl_in - s0 < slice ? n_smpl_in - s0 : slice, nb = cs * (int)per;
         if (!col && s0 >= n_smpl) break;                                    // the input samples past the called ones
-        const unsigned char *g = run + (size_t)s0 * per;                    // the slice's first byte
-        const int sh = (int)((uintptr_t)g & (DEC_LINE - 1));
-        // global bytes g - sh + [sh, sh + nb) -> the same offsets of LDS: whole 16-byte lines in the middle, single bytes at both ends
-        const int lo = sh, hi = sh + nb;
-        const int l0 = (lo + DEC_LINE - 1) / DEC_LINE, l1 = hi / DEC_LINE;  // whole lines [l0, l1)
-        const unsigned char *ga = g - sh;
-        if (l0 < l1) {
-            for (int x = l0 + tid; x < l1; x += DEC_THREADS)
-                reinterpret_cast<uint4*>(stage)[x] = reinterpret_cast<const uint4*>(ga)[x];
-            const int head = l0 * DEC_LINE - lo, tail = hi - l1 * DEC_LINE; // each < 16
-            if (tid < head) stage[lo + tid] = ga[lo + tid];
-            else if (tid >= 32 && tid - 32 < tail) stage[l1 * DEC_LINE + tid - 32] = ga[l1 * DEC_LINE + tid - 32];
-        } else {
-            for (int x = lo + tid; x < hi; x += DEC_THREADS) stage[x] = ga[x];  // fewer than 31 bytes, no whole line
-        }
+        const unsigned char *l = stage + line_load(stage, run + (size_t)s0 * per, nb, tid);
         __syncthreads();
         // Lanes read `per` bytes apart.  By the bank rule (ds_read_b32 and narrower: 32 banks of 4 bytes, the two halves of a
         // wavefront apart) an odd number of dwords a sample -- PL of 1, 2 and 5 alleles as int32 -- is free of conflicts, 6 and
         // 10 dwords meet two lanes on a bank; the narrow types put several lanes on one dword.  Not measured: the plane stores,
         // n_planes x 4 bytes a sample whatever the type, are the larger part of the traffic.
-        const unsigned char *l = stage + sh;
         if (col) {
-            for (int s = tid; s < n_smpl; s += DEC_THREADS) {
+            for (int s = tid; s < n_smpl; s += COD_THREADS) {
                 const int c = col[s] - s0;
                 if (c >= 0 && c < cs) dec_sample(o + s, S, n_planes, l + (size_t)c * per, wr, es, aligned);
             }
         } else {
             const int ce = s0 + cs < n_smpl ? cs : n_smpl - s0;
-            for (int c = tid; c < ce; c += DEC_THREADS) dec_sample(o + s0 + c, S, n_planes, l + (size_t)c * per, wr, es, aligned);
+            for (int c = tid; c < ce; c += COD_THREADS) dec_sample(o + s0 + c, S, n_planes, l + (size_t)c * per, wr, es, aligned);
         }
         __syncthreads();
     }
@@ -136,7 +102,7 @@ extern "C" int bcfgpu_call_decode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t 
     const bcfgpu_bcf_vec *d_vec = (const bcfgpu_bcf_vec*)ws_upload(ctx, WS_COMPACT_BCFDEC_VEC, vec, (size_t)n_sites * sizeof *vec, 64, st);
     const int32_t *d_col = col ? (const int32_t*)ws_upload(ctx, WS_COMPACT_BCFDEC_COL, col, (size_t)S * 4, 64, st) : nullptr;
     if (!d_vec || (col && !d_col)) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_call_decode_bcf: workspace");
-    hipLaunchKernelGGL(bcf_decode_kernel, dim3(n_sites), dim3(DEC_THREADS), 0, st, (const unsigned char*)d_indiv, d_vec, d_col, n_smpl_in, S, n_planes, d_out);
+    hipLaunchKernelGGL(bcf_decode_kernel, dim3(n_sites), dim3(COD_THREADS), 0, st, (const unsigned char*)d_indiv, d_vec, d_col, n_smpl_in, S, n_planes, d_out);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_call_decode_bcf: decode pass");
     return 0;
 }

@@ -81,25 +81,25 @@ enum WsSlot : int {
     // bcfgpu_gvcf_blocks, bcfgpu_compact_calls[_async]: scratch for one call
     WS_GVCF_SCAN = 32, WS_GVCF_SCAN_TMP = 33,
     WS_COMPACT_SIZE = 35, WS_COMPACT_SCAN_TMP = 36, WS_COMPACT_COUNTS = 37,
-    // bcfgpu_mplp_encode_bcf (bcfenc.hip): scratch for one call -- the keys' integer types per site, the scan's temporary storage
-    WS_COMPACT_BCF_TYPES = 167, WS_COMPACT_BCF_SCAN_TMP = 168,
-    // bcfgpu_call_decode_bcf (bcfdec.hip): scratch for one call -- the uploaded copies of the records' vectors and of the sample map
+    // the device codecs of the records' per-sample bytes (bcfcodec.h): scratch for one call.  The four encoders' size passes
+    // (enc_offsets) share the scan's temporary storage: each entry synchronises the context's stream before it returns
+    WS_COMPACT_ENC_SCAN_TMP = 167,
+    // bcfgpu_mplp_encode_bcf (bcfenc.hip): the keys' integer types per site
+    WS_COMPACT_BCF_TYPES = 168,
+    // bcfgpu_call_decode_bcf (bcfdec.hip): the uploaded copies of the records' vectors and of the sample map
     WS_COMPACT_BCFDEC_VEC = 169, WS_COMPACT_BCFDEC_COL = 170,
-    // bcfgpu_call_encode_bcf (bcfcallenc.hip): scratch for one call -- one packed word a site (the three keys' integer types, GT's
-    // and PL's widths), the scan's temporary storage
-    WS_COMPACT_BCFCALL_WORD = 171, WS_COMPACT_BCFCALL_SCAN_TMP = 172,
-    // bcfgpu_call_remap_bcf (bcfkeys.hip): scratch for one call -- the uploaded copies of the key jobs and of the sample map, one packed
-    // word a job (the block's integer type and width), the scan's temporary storage
-    WS_COMPACT_BCFKEY_JOBS = 173, WS_COMPACT_BCFKEY_COL = 174, WS_COMPACT_BCFKEY_WORD = 175, WS_COMPACT_BCFKEY_SCAN_TMP = 176,
-    // bcfgpu_mplp_encode_vcf (vcfenc.hip): scratch for one call -- the scan's temporary storage
-    WS_COMPACT_VCF_SCAN_TMP = 177,
+    // bcfgpu_call_encode_bcf (bcfcallenc.hip): one packed word a site (the three keys' integer types, GT's and PL's widths)
+    WS_COMPACT_BCFCALL_WORD = 171,
+    // bcfgpu_call_remap_bcf (bcfkeys.hip): the uploaded copies of the key jobs and of the sample map, one packed word a job (the
+    // block's integer type and width)
+    WS_COMPACT_BCFKEY_JOBS = 172, WS_COMPACT_BCFKEY_COL = 173, WS_COMPACT_BCFKEY_WORD = 174,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_COMPACT_VCF_SCAN_TMP + 1     // one past the highest slot
+    WS_COUNT = WS_COMPACT_BCFKEY_WORD + 1      // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names
@@ -121,11 +121,8 @@ enum PinnedSlot : int {
     PIN_GTILE_KEPT = 2,                 // bcfgpu_gap_prep_tile: the columns that go on
     PIN_PLP_COL_COUNTS = 3,             // bcfgpu_pool_pileup: col_n / col_indel
     PIN_PBAQ_REF = 6,                   // bcfgpu_pool_baq: the reference slice (the call returns with its copy in flight)
-    PIN_BCF_TOTAL = 7,                  // bcfgpu_mplp_encode_bcf: the size of all blocks
-    PIN_BCFCALL_TOTAL = 8,              // bcfgpu_call_encode_bcf: the size of all blocks
-    PIN_BCFKEY_TOTAL = 9,               // bcfgpu_call_remap_bcf: the size of all blocks
-    PIN_VCF_TOTAL = 10,                 // bcfgpu_mplp_encode_vcf: the size of all blocks
-    PINNED_COUNT = PIN_VCF_TOTAL + 1        // one past the highest slot
+    PIN_ENC_TOTAL = 7,                  // enc_offsets: the size of all blocks of an encoder entry (each synchronises before it returns)
+    PINNED_COUNT = PIN_ENC_TOTAL + 1        // one past the highest slot
 };
 
 // workspace / pinned host buffer `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails
@@ -175,9 +172,16 @@ PoolStage *bcfgpu_internal_pool_stage(bcfgpu_ctx *c, bool with_stream);
 // that address) is dropped, so that the new tile in the same buffer does not take it for its own.
 void bcfgpu_internal_drop_plan(bcfgpu_ctx *c, WsSlot recs);
 int bcfgpu_set_error(int code, const char *what);               // bcfgpu_last_error() becomes `what`; returns `code`
+int bcfgpu_set_error(int code, const char *name, const char *what);     // ... becomes "`name`: `what`"
 
 // [lowest start, highest end) of the pool's reads (pileup.hip)
 int bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, int *lo, int *hi);
+// The size pass of an encoder entry `name` behind its size kernel (gather.hip): d_off[0 .. n_off) holds the blocks' sizes and a
+// last 0 and becomes their exclusive sum, the offsets; *n_bytes = their total, d_off[n_off - 1].  The stream is synchronised.
+// n_off == 1 (nothing to encode, no size kernel): the one offset is set to 0.  Returns 0 -- the caller goes on to its write
+// kernel unless *n_bytes is 0 --, or the entry's error: BCFGPU_E_RANGE when the total is above cap_bytes (nothing is written, the
+// caller learns the size and may come back with a larger buffer).  Takes WS_COMPACT_ENC_SCAN_TMP and PIN_ENC_TOTAL.
+int enc_offsets(bcfgpu_ctx *ctx, hipStream_t st, const char *name, uint64_t *d_off, int n_off, uint64_t cap_bytes, uint64_t *n_bytes);
 // bcf_call_gap_prep on inputs already in HBM (gap_prep.hip)
 int bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_ent, uint32_t *d_aux, const bcfgpu_indel_out *out, int inscns_cap);
 

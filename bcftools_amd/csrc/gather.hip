@@ -72,6 +72,35 @@ __global__ __launch_bounds__(256) void compact_copy_kernel(const bcfgpu_call_sit
     for (int i = tid; i < ng * n_smpl; i += 256) p[i] = pl[(size_t)k * n_gt_planes * n_smpl + i];
 }
 
+// d[0 .. n) becomes its exclusive sum, queued on st; the scan's temporary storage is workspace `slot`.  0, BCFGPU_E_HIP or
+// BCFGPU_E_NOMEM.  The one instance of the device scan over 64-bit sizes in the library.
+static int scan_sizes(bcfgpu_ctx *ctx, hipStream_t st, WsSlot slot, unsigned long long *d, int n)
+{
+    size_t tmp = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d, d, n, st) != hipSuccess) return BCFGPU_E_HIP;
+    void *d_tmp = bcfgpu_internal_ws(ctx, slot, tmp + 64);
+    if (!d_tmp) return BCFGPU_E_NOMEM;
+    return hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, d, d, n, st) != hipSuccess ? BCFGPU_E_HIP : 0;
+}
+
+int enc_offsets(bcfgpu_ctx *ctx, hipStream_t st, const char *name, uint64_t *d_off, int n_off, uint64_t cap_bytes, uint64_t *n_bytes)
+{
+    *n_bytes = 0;
+    if (n_off == 1) {
+        if (hipMemsetAsync(d_off, 0, sizeof(uint64_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, name, "offsets");
+        return 0;
+    }
+    uint64_t *h_total = (uint64_t*)bcfgpu_internal_pinned(ctx, PIN_ENC_TOTAL, sizeof(uint64_t));
+    if (!h_total) return bcfgpu_set_error(BCFGPU_E_NOMEM, name, "workspace");
+    const int rc = scan_sizes(ctx, st, WS_COMPACT_ENC_SCAN_TMP, reinterpret_cast<unsigned long long*>(d_off), n_off);
+    if (rc) return bcfgpu_set_error(rc, name, rc == BCFGPU_E_HIP ? "scan" : "workspace");
+    if (hipMemcpyAsync(h_total, d_off + n_off - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return bcfgpu_set_error(BCFGPU_E_HIP, name, "size pass");
+    *n_bytes = *h_total;
+    if (*n_bytes > cap_bytes) return bcfgpu_set_error(BCFGPU_E_RANGE, name, "the buffer is too small for the blocks (n_bytes tells the size)");
+    return 0;
+}
+
 }  // namespace bcfgpu
 
 // Everything is queued on the context's stream; nothing comes back to the host here.
@@ -89,11 +118,8 @@ extern "C" int bcfgpu_compact_calls_async(bcfgpu_ctx *ctx, int32_t n_sites, int3
     if (!d_size) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_compact_calls_async: device workspace");
     hipLaunchKernelGGL(compact_size_kernel, dim3((n_sites + 256) / 256), dim3(256), 0, st, cout->site, n_sites, S, variants_only, d_size,
                        reinterpret_cast<unsigned long long*>(d_counts));
-    size_t tmp = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_size, d_size, n_sites + 1, st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "scan");
-    void *d_tmp = bcfgpu_internal_ws(ctx, WS_COMPACT_SCAN_TMP, tmp + 64);
-    if (!d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_compact_calls_async: device workspace");
-    if (hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, d_size, d_size, n_sites + 1, st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "scan");
+    const int rc = scan_sizes(ctx, st, WS_COMPACT_SCAN_TMP, d_size, n_sites + 1);
+    if (rc) return bcfgpu_set_error(rc, rc == BCFGPU_E_HIP ? "scan" : "bcfgpu_compact_calls_async: device workspace");
     hipLaunchKernelGGL(compact_copy_kernel, dim3(n_sites), dim3(256), 0, st, cout->site, msite, cout->gt, cout->pl, n_gt_planes, S, n_sites, site0,
                        variants_only, d_size, (unsigned char*)d_buf, (unsigned long long)cap_bytes, reinterpret_cast<unsigned long long*>(d_counts));
     if (hipGetLastError() != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_compact_calls_async: launch");

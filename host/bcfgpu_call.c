@@ -45,21 +45,15 @@
 #include <string.h>
 #include <strings.h>
 #include <stdint.h>
-#include <time.h>
+#include <stdarg.h>
 #include "bcfgpu.h"
 #include "vcfio.h"
-
-#define CHECK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "%s: %s (%d)\n", #call, bcfgpu_last_error(), rc_); exit(1); } } while (0)
-#define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(1); } while (0)
-
-static FILE *LN; static char *ln_buf; static size_t ln_len;      /* the record being written: a memory stream, framed by vcfio */
+#include "drv.h"
 
 /* with --device-input: line = the first nine columns, the per-sample block = ilen bytes at ioff of the byte buffer, its key headers in keys */
 typedef struct { char *line; char **fld; int nfld; char **als; int nals, unseen, pl_idx, ad_idx; uint8_t *ploidy;
                  size_t ioff, ilen; int n_fmt, nkeys; vio_indiv_key *keys;
                  int *kjob; } rec_t;            /* --device-keys, a written record: key i's job of bcfgpu_call_remap_bcf, or -1 (the host's) */
-
-static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 typedef struct { char chrom[256]; int from, to, ploidy; char sex[64]; } preg_t;
 
@@ -110,14 +104,6 @@ static void print_numberR(const char *vals, const int32_t *als_map, int nals, in
         for (int i = 0; i < nn; ++i) fprintf(LN, "%s%s", i ? "," : "", o[i]);
     }
     free(v); free(c);
-}
-
-static void *dev_upload(bcfgpu_ctx *ctx, const void *src, size_t bytes)
-{
-    void *d = NULL;
-    CHECK(bcfgpu_malloc(ctx, bytes ? bytes : 16, &d));
-    if (bytes) CHECK(bcfgpu_memcpy_h2d(ctx, d, src, bytes));
-    return d;
 }
 
 /* ---- call -C alleles -T targets [-i]: the record is re-expressed in the alleles of the target file before mcall() sees it
@@ -209,6 +195,8 @@ static void flush_region(const char *chrom, long beg0, long end0)
     }
 }
 
+typedef struct { char *p; size_t o, cap; } obuf_t;              /* the line constrain_line writes */
+static void outf(obuf_t *b, const char *fmt, ...) { va_list ap; va_start(ap, fmt); b->o += (size_t)vsnprintf(b->p + b->o, b->cap - b->o, fmt, ap); va_end(ap); }
 /* The record `line` (S_in sample columns) in the alleles of target t: a new malloc'ed line, the same line when nothing
  * changes, or NULL when mcall() would return -2 (the site is skipped).  *unseen: in/out. */
 static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *unseen_io)
@@ -246,28 +234,27 @@ static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *uns
         if (ipl < snv[s]) { int w = 1; for (const char *q = sv[s][ipl]; *q; ++q) w += *q == ','; if (w > width) width = w; }
     }
     const size_t cap = strlen(line) * 4 + 4096 + (size_t)S_in * (size_t)npl * 12;
-    char *out = malloc(cap); size_t o = 0;
-    #define OUT(...) do { o += (size_t)snprintf(out + o, cap - o, __VA_ARGS__); } while (0)
-    OUT("%s\t%s\t%s\t%s\t", f[0], f[1], f[2], als[0]);
-    if (nals == 1) OUT("."); else for (int i = 1; i < nals; ++i) OUT("%s%s", i > 1 ? "," : "", als[i]);
-    OUT("\t%s\t%s\t", f[5], f[6]);
+    obuf_t ob = { malloc(cap), 0, cap };
+    outf(&ob, "%s\t%s\t%s\t%s\t", f[0], f[1], f[2], als[0]);
+    if (nals == 1) outf(&ob, "."); else for (int i = 1; i < nals; ++i) outf(&ob, "%s%s", i > 1 ? "," : "", als[i]);
+    outf(&ob, "\t%s\t%s\t", f[5], f[6]);
     {   /* INFO: QS follows the alleles (absent alleles: 0) */
         int ni; char *info = strdup(f[7]), **iv = split(info, ';', &ni);
         for (int i = 0; i < ni; ++i) {
-            if (i) OUT(";");
+            if (i) outf(&ob, ";");
             if (!strncmp(iv[i], "QS=", 3)) {
                 int nq; char *qc = strdup(iv[i] + 3), **qv = split(qc, ',', &nq);
-                OUT("QS=");
-                for (int k = 0; k < nals; ++k) OUT("%s%.9g", k ? "," : "", amap[k] < nq ? (double)(float)atof(qv[amap[k]]) : 0.);
+                outf(&ob, "QS=");
+                for (int k = 0; k < nals; ++k) outf(&ob, "%s%.9g", k ? "," : "", amap[k] < nq ? (double)(float)atof(qv[amap[k]]) : 0.);
                 free(qv); free(qc);
-            } else OUT("%s", iv[i]);
+            } else outf(&ob, "%s", iv[i]);
         }
         free(iv); free(info);
     }
-    OUT("\t%s", f[8]);
+    outf(&ob, "\t%s", f[8]);
     int32_t *ori = malloc((size_t)width * 4);
     for (int s = 0; s < S_in; ++s) {
-        OUT("\t");
+        outf(&ob, "\t");
         for (int w = 0; w < width; ++w) ori[w] = BCFGPU_INT32_VECTOR_END;
         if (ipl < snv[s]) {
             int np; char *pc = strdup(sv[s][ipl]), **pv = split(pc, ',', &np);
@@ -275,7 +262,7 @@ static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *uns
             free(pv); free(pc);
         } else ori[0] = BCFGPU_INT32_MISSING;
         for (int k = 0; k < nk; ++k) {
-            if (k) OUT(":");
+            if (k) outf(&ob, ":");
             if (k == ipl) {
                 int printed = 0;
                 for (int g = 0; g < npl; ++g) {
@@ -289,22 +276,21 @@ static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *uns
                     }
                     if (g == 0 && v == BCFGPU_INT32_VECTOR_END) v = BCFGPU_INT32_MISSING;
                     if (v == BCFGPU_INT32_VECTOR_END) break;
-                    if (printed++) OUT(",");
-                    if (v == BCFGPU_INT32_MISSING) OUT("."); else OUT("%d", v);
+                    if (printed++) outf(&ob, ",");
+                    if (v == BCFGPU_INT32_MISSING) outf(&ob, "."); else outf(&ob, "%d", v);
                 }
             } else if (k < snv[s] && is_numberR(fmtR, n_fmtR, keys[k], strlen(keys[k])) && strcmp(sv[s][k], ".")) {
                 int nv; char *vc2 = strdup(sv[s][k]), **vv = split(vc2, ',', &nv);      /* Number=R: new[k] = old[als_map[k]] */
-                for (int a = 0; a < nals; ++a) OUT("%s%s", a ? "," : "", amap[a] < nv ? vv[amap[a]] : ".");
+                for (int a = 0; a < nals; ++a) outf(&ob, "%s%s", a ? "," : "", amap[a] < nv ? vv[amap[a]] : ".");
                 free(vv); free(vc2);
-            } else OUT("%s", k < snv[s] ? sv[s][k] : ".");
+            } else outf(&ob, "%s", k < snv[s] ? sv[s][k] : ".");
         }
     }
-    #undef OUT
     free(ori);
     for (int s = 0; s < S_in; ++s) { free(sv[s]); free(sc[s]); }
     free(sv); free(snv); free(sc); free(keys); free(fmt); free(unseen_al); free(alts); free(altc); free(f); free(c);
     *unseen_io = unseen ? nals - 1 : unseen;
-    return out;
+    return ob.p;
 }
 
 /* next_line (vcfcall.c:501-605): the target of this record, or -1 when the record is not to be called */
@@ -399,7 +385,41 @@ static int unwanted_site(const char *line, int acgt_only, int skip_kind)
     return acgt_only && (ref[0] == 'N' || ref[0] == 'n');
 }
 
-int main(int argc, char **argv)
+
+/* ---- the state of a run, stage by stage ---- */
+typedef struct {                                                /* the command line */
+    int varonly, out_tags, keepalt, dev_in, dev_rec, dev_keys, keys_given, want_timing;
+    int acgt_only, skip_kind;                                   /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
+    const char *tgt_file, *smpl_file, *smpl_list, *ploidy_file, *ploidy_alias, *grp_arg, *grp_tag, *out_path, *in_path;
+    double prior; char out_mode, prior_an_tag[64], prior_ac_tag[64];
+    int32_t gv_range[16]; int gv_n;                             /* -g INT,...: gvcf_init (gvcf.c:47-73) */
+} opt_t;
+/* ploidy definition (ploidy.c): regions per sex, '*' lines = the sex's default; the last sex named is the default sex */
+typedef struct { preg_t *reg; int n; char last_sex[64]; } ploidy_t;
+/* the samples called, S of the input's S_in: output sample s = input column col[s] (bcf_subset with -S); the names of the input
+ * columns; a sample's ploidy ("0", "1", "2") or sex name; -G: the group of every sample */
+typedef struct { int S, S_in, *col; char **names, (*spec)[64]; int32_t *grp; int ngrp; } smap_t;
+/* the records that are called; --device-input: their per-sample blocks, back to back; -i: where the last record lay */
+typedef struct { rec_t *rec; int n, cap, ngmax, namax; unsigned char *ibuf; size_t ibuf_l, ibuf_m; char *prev_chrom; long prev_pos0; } recs_t;
+/* what mcall() reads from the records: PL planes (missing / vector_end kept), QS, I16.
+ * --device-input: no host PL / AD planes; per record where the PL vector (and the -G tag's) lies in the byte buffer */
+typedef struct { int32_t *nals, *unseen, *pl, *ad, *pan, *pac; float *qs, *i16; bcfgpu_bcf_vec *vec_pl, *vec_ad; int want_ad; } hplanes_t;
+typedef struct {                                                /* the planes in HBM, and what came down of the results */
+    bcfgpu_ctx *ctx;
+    int32_t *d_nals, *d_unseen, *d_plin, *d_ad, *d_grp, *d_pan, *d_pac; float *d_qs, *d_i16;
+    void *d_indiv;                                              /* --device-keys: kept until the pass-through keys' blocks are made */
+    void *d_site, *d_gt, *d_pl, *d_ploidy, *d_gq, *d_gp;
+    bcfgpu_call_site *cs; int8_t *gt; int32_t *opl, *gq; float *gp;
+} dev_t;
+typedef struct {                                                /* --device-records, --device-keys: the blocks made in HBM */
+    uint8_t *emit; void *d_emit;                                /* which records are written */
+    unsigned char *kblk; uint64_t *koff; int n_enc;
+    unsigned char *pblk; uint64_t *poff; long n_pjob, n_phost;  /* --device-keys: the pass-through keys' blocks, one offset a job */
+} blocks_t;
+typedef struct { int32_t *w, *blk, *min, *dp; bcfgpu_gvcf_block *block; } gvcf_t;   /* -g: record k is written record w[k], or -1 */
+static void gvcf_option(opt_t *o, const char *arg, const char *echo) { if ((o->gv_n = parse_gvcf_limits(arg, o->gv_range)) < 0) DIE("Could not parse: --gvcf %s\n", echo); }
+/* 0, or 2 after the usage text */
+static int parse_options(int argc, char **argv, opt_t *o)
 {
     {   /* call's long option names (vcfcall.c:946-981) are read as their short forms; -f is the old spelling of -a (vcfcall.c:995) */
         static const char *alias[][2] = {
@@ -410,34 +430,27 @@ int main(int argc, char **argv)
         for (int i = 1; i < argc; ++i)
             for (size_t k = 0; k < sizeof alias / sizeof alias[0]; ++k) if (!strcmp(argv[i], alias[k][0])) argv[i] = (char *)alias[k][1];
     }
-    int varonly = 0, out_tags = 0, keepalt = 0, dev_in = 0, dev_rec = 0, dev_keys = 0, keys_given = 0, want_timing = 0;
-    double t_read = 0., t_planes = 0., t_dev = 0., t_write = 0.;
-    int acgt_only = 1, skip_kind = 0;                           /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
-    const char *tgt_file = NULL; double prior = 1.1e-3;
-    const char *smpl_file = NULL, *smpl_list = NULL, *ploidy_file = NULL, *ploidy_alias = NULL, *grp_arg = NULL, *grp_tag = NULL;
-    char prior_an_tag[64] = "", prior_ac_tag[64] = "";
-    char out_mode = 'v'; const char *out_path = "-";
-    int32_t gv_range[16]; int gv_n = 0;                         /* -g INT,...: gvcf_init (gvcf.c:47-73) */
+    memset(o, 0, sizeof *o); o->acgt_only = 1; o->prior = 1.1e-3; o->out_mode = 'v'; o->out_path = "-";
     while (argc > 2 && argv[1][0] == '-') {
-        if (!strcmp(argv[1], "-v")) { varonly = 1; ++argv; --argc; }
+        if (!strcmp(argv[1], "-v")) { o->varonly = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "-m")) { ++argv; --argc; }                                     /* the multiallelic caller: the only one here */
-        else if (!strcmp(argv[1], "-A")) { keepalt = 1; ++argv; --argc; }
-        else if (!strcmp(argv[1], "-M") || !strcmp(argv[1], "--keep-masked-refs")) { acgt_only = 0; ++argv; --argc; }      /* vcfcall.c:1000 */
-        else if (!strcmp(argv[1], "-N") || !strcmp(argv[1], "--skip-Ns")) { acgt_only = 1; ++argv; --argc; }               /* vcfcall.c:1001: the default */
+        else if (!strcmp(argv[1], "-A")) { o->keepalt = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "-M") || !strcmp(argv[1], "--keep-masked-refs")) { o->acgt_only = 0; ++argv; --argc; }      /* vcfcall.c:1000 */
+        else if (!strcmp(argv[1], "-N") || !strcmp(argv[1], "--skip-Ns")) { o->acgt_only = 1; ++argv; --argc; }               /* vcfcall.c:1001: the default */
         else if ((!strcmp(argv[1], "-V") || !strcmp(argv[1], "--skip-variants")) && argc > 3) {                              /* vcfcall.c:1032-1036 */
-            if (!strcasecmp(argv[2], "snps")) skip_kind = 1; else if (!strcasecmp(argv[2], "indels")) skip_kind = 2;
+            if (!strcasecmp(argv[2], "snps")) o->skip_kind = 1; else if (!strcasecmp(argv[2], "indels")) o->skip_kind = 2;
             else DIE("Unknown skip category \"%s\" (-V argument must be \"snps\" or \"indels\")\n", argv[2]);
             argv += 2; argc -= 2;
         }
         else if (!strcmp(argv[1], "--threads") && argc > 3) { argv += 2; argc -= 2; }                                        /* (compression threads: nothing to do here) */
         else if (!strcmp(argv[1], "--no-version")) { ++argv; --argc; }                                                       /* (no ##bcftools_callVersion lines are written anyway) */
         else if (!strcmp(argv[1], "-i")) { insert_missed = 1; ++argv; --argc; }
-        else if (!strcmp(argv[1], "--device-input")) { dev_in = 1; ++argv; --argc; }
-        else if (!strcmp(argv[1], "--device-records")) { dev_rec = 1; ++argv; --argc; }
-        else if (!strcmp(argv[1], "--device-keys")) { dev_keys = keys_given = 1; ++argv; --argc; }
-        else if (!strcmp(argv[1], "--timing")) { want_timing = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-input")) { o->dev_in = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-records")) { o->dev_rec = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-keys")) { o->dev_keys = o->keys_given = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--timing")) { o->want_timing = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "-C") && argc > 3) { if (strcmp(argv[2], "alleles")) DIE("-C: only `alleles` is supported\n"); cals = 1; argv += 2; argc -= 2; }
-        else if (!strcmp(argv[1], "-T") && argc > 3) { tgt_file = argv[2]; argv += 2; argc -= 2; }
+        else if (!strcmp(argv[1], "-T") && argc > 3) { o->tgt_file = argv[2]; argv += 2; argc -= 2; }
         else if ((!strcmp(argv[1], "-t") || !strcmp(argv[1], "--targets") || !strcmp(argv[1], "-r") || !strcmp(argv[1], "--regions")) && argc > 3) {
             /* -t / -r CHR[:POS | :BEG-END],...: only the records whose POS lies there (bcf_sr_set_targets / _regions, vcfcall.c:612-626; -r without
              * an index is a filter over the stream here) */
@@ -446,63 +459,56 @@ int main(int argc, char **argv)
             free(t); free(c); argv += 2; argc -= 2;
         }
         else if ((!strcmp(argv[1], "-R") || !strcmp(argv[1], "--regions-file")) && argc > 3) { site_filter_file(argv[2]); argv += 2; argc -= 2; }
-        else if (!strcmp(argv[1], "-P") && argc > 3) { prior = atof(argv[2]); argv += 2; argc -= 2; }      /* vcfcall.c:931-943 */
-        else if (!strcmp(argv[1], "-O") && argc > 3) { out_mode = argv[2][0]; argv += 2; argc -= 2; }      /* version.c:67-82 */
-        else if (!strncmp(argv[1], "-O", 2) && argv[1][2]) { out_mode = argv[1][2]; ++argv; --argc; }
-        else if (!strcmp(argv[1], "-o") && argc > 3) { out_path = argv[2]; argv += 2; argc -= 2; }
-        else if (!strcmp(argv[1], "-G") && argc > 3) { grp_arg = argv[2]; argv += 2; argc -= 2; }
-        else if (!strcmp(argv[1], "--group-samples-tag") && argc > 3) { grp_tag = argv[2]; argv += 2; argc -= 2; }
+        else if (!strcmp(argv[1], "-P") && argc > 3) { o->prior = atof(argv[2]); argv += 2; argc -= 2; }      /* vcfcall.c:931-943 */
+        else if (!strcmp(argv[1], "-O") && argc > 3) { o->out_mode = argv[2][0]; argv += 2; argc -= 2; }      /* version.c:67-82 */
+        else if (!strncmp(argv[1], "-O", 2) && argv[1][2]) { o->out_mode = argv[1][2]; ++argv; --argc; }
+        else if (!strcmp(argv[1], "-o") && argc > 3) { o->out_path = argv[2]; argv += 2; argc -= 2; }
+        else if (!strcmp(argv[1], "-G") && argc > 3) { o->grp_arg = argv[2]; argv += 2; argc -= 2; }
+        else if (!strcmp(argv[1], "--group-samples-tag") && argc > 3) { o->grp_tag = argv[2]; argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-F") && argc > 3) {
             const char *c = strchr(argv[2], ',');
             if (!c || c == argv[2] || !c[1] || c - argv[2] > 63 || strlen(c + 1) > 63) DIE("-F: expected AN_TAG,AC_TAG\n");
-            memcpy(prior_an_tag, argv[2], (size_t)(c - argv[2])); prior_an_tag[c - argv[2]] = 0; strcpy(prior_ac_tag, c + 1);
+            memcpy(o->prior_an_tag, argv[2], (size_t)(c - argv[2])); o->prior_an_tag[c - argv[2]] = 0; strcpy(o->prior_ac_tag, c + 1);
             argv += 2; argc -= 2;
         }
         else if (!strcmp(argv[1], "-a") && argc > 3) {
             char *c = strdup(argv[2]); int nt; char **t = split(c, ',', &nt);
             for (int i = 0; i < nt; ++i)
-                if (!strcmp(t[i], "GQ")) out_tags |= BCFGPU_CALL_FMT_GQ;
-                else if (!strcmp(t[i], "GP")) out_tags |= BCFGPU_CALL_FMT_GP;
+                if (!strcmp(t[i], "GQ")) o->out_tags |= BCFGPU_CALL_FMT_GQ;
+                else if (!strcmp(t[i], "GP")) o->out_tags |= BCFGPU_CALL_FMT_GP;
                 else DIE("-a: unknown tag %s\n", t[i]);
             free(t); free(c); argv += 2; argc -= 2;
         }
-        else if ((!strcmp(argv[1], "-g") || !strcmp(argv[1], "--gvcf")) && argc > 3) {
-            char *c = strdup(argv[2]); int nt; char **t = split(c, ',', &nt);
-            if (nt < 1 || nt > 16) DIE("Could not parse: --gvcf %s\n", argv[2]);
-            for (int i = 0; i < nt; ++i) { char *e; gv_range[i] = (int32_t)strtol(t[i], &e, 10); if (e == t[i] || *e) DIE("Could not parse: --gvcf %s\n", argv[2]); }
-            gv_n = nt; free(t); free(c); argv += 2; argc -= 2;
-        }
+        else if ((!strcmp(argv[1], "-g") || !strcmp(argv[1], "--gvcf")) && argc > 3) { gvcf_option(o, argv[2], argv[2]); argv += 2; argc -= 2; }
         else if ((!strncmp(argv[1], "-g", 2) && argv[1][2]) || (!strncmp(argv[1], "-mg", 3) && argv[1][3])) {   /* -g0,2,5; the `-mg0` of test.pl:277 */
-            char *c = strdup(argv[1] + (argv[1][1] == 'm' ? 3 : 2)); int nt; char **t = split(c, ',', &nt);
-            if (nt < 1 || nt > 16) DIE("Could not parse: --gvcf %s\n", argv[1] + 2);
-            for (int i = 0; i < nt; ++i) { char *e; gv_range[i] = (int32_t)strtol(t[i], &e, 10); if (e == t[i] || *e) DIE("Could not parse: --gvcf %s\n", argv[1] + 2); }
-            gv_n = nt; free(t); free(c); ++argv; --argc;
+            gvcf_option(o, argv[1] + (argv[1][1] == 'm' ? 3 : 2), argv[1] + 2); ++argv; --argc;
         }
-        else if (!strcmp(argv[1], "-S") && argc > 3) { smpl_file = argv[2]; argv += 2; argc -= 2; }
-        else if (!strcmp(argv[1], "-s") && argc > 3) { smpl_list = argv[2]; smpl_file = argv[2]; argv += 2; argc -= 2; }          /* -s LIST: the names, comma-separated (vcfcall.c:1050) */
+        else if (!strcmp(argv[1], "-S") && argc > 3) { o->smpl_file = argv[2]; argv += 2; argc -= 2; }
+        else if (!strcmp(argv[1], "-s") && argc > 3) { o->smpl_list = argv[2]; o->smpl_file = argv[2]; argv += 2; argc -= 2; }          /* -s LIST: the names, comma-separated (vcfcall.c:1050) */
         else if (!strcmp(argv[1], "-p") && argc > 3) { argv += 2; argc -= 2; }                                                 /* --pval-threshold: read by the consensus caller only (vcfcall.c:1038) */
-        else if (!strcmp(argv[1], "--ploidy-file") && argc > 3) { ploidy_file = argv[2]; argv += 2; argc -= 2; }
-        else if (!strcmp(argv[1], "--ploidy") && argc > 3) { ploidy_alias = argv[2]; argv += 2; argc -= 2; }                       /* vcfcall.c:976, 827-855 */
-        else if (!strcmp(argv[1], "-X")) { ploidy_alias = "X"; ++argv; --argc; }                                                  /* vcfcall.c:991 */
-        else if (!strcmp(argv[1], "-Y")) { ploidy_alias = "Y"; ++argv; --argc; }                                                  /* vcfcall.c:992 */
+        else if (!strcmp(argv[1], "--ploidy-file") && argc > 3) { o->ploidy_file = argv[2]; argv += 2; argc -= 2; }
+        else if (!strcmp(argv[1], "--ploidy") && argc > 3) { o->ploidy_alias = argv[2]; argv += 2; argc -= 2; }                       /* vcfcall.c:976, 827-855 */
+        else if (!strcmp(argv[1], "-X")) { o->ploidy_alias = "X"; ++argv; --argc; }                                                  /* vcfcall.c:991 */
+        else if (!strcmp(argv[1], "-Y")) { o->ploidy_alias = "Y"; ++argv; --argc; }                                                  /* vcfcall.c:992 */
         else break;
     }
-    if (gv_n && varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
-    if (gv_n && cals) DIE("-g with -C alleles is not supported\n");
+    if (o->gv_n && o->varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
+    if (o->gv_n && cals) DIE("-g with -C alleles is not supported\n");
     if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-records] [--device-keys] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
-    /* ploidy definition (ploidy.c): regions per sex, '*' lines = the sex's default; the last sex named is the default sex */
-    preg_t *preg = NULL; int npreg = 0; char last_sex[64] = "";
-    char *alias_text = NULL;
-    if (ploidy_alias) {
+    o->in_path = argv[1]; return 0;
+}
+static void load_ploidy(opt_t *o, ploidy_t *P)
+{
+    memset(P, 0, sizeof *P); char *alias_text = NULL;
+    if (o->ploidy_alias) {
         /* --ploidy ALIAS: the definitions `call` carries with it (vcfcall.c:138-199), in the format of a --ploidy-file: the
          * haploid stretches of the human sex chromosomes outside the pseudo-autosomal regions and the mitochondrion, by assembly;
          * "X" / "Y" / "1": males haploid / males haploid and females absent / everybody haploid, whatever the sequence */
         static const struct { const char *name; long x_par1_end, x_par2_beg, x_end, y_end; } asm_[2] = {
             { "GRCh37", 60000, 2699521, 154931043, 59373566 }, { "GRCh38", 9999, 2781480, 155701381, 57227415 } };
-        size_t al = 0; FILE *m = open_memstream(&alias_text, &al);
-        int known = 0;
+        size_t al = 0; FILE *m = open_memstream(&alias_text, &al); int known = 0;
         for (int k = 0; k < 2; ++k)
-            if (!strcmp(ploidy_alias, asm_[k].name)) {
+            if (!strcmp(o->ploidy_alias, asm_[k].name)) {
                 for (int pre = 0; pre < 2; ++pre) {
                     const char *c = pre ? "chr" : "";
                     fprintf(m, "%sX 1 %ld M 1\n%sX %ld %ld M 1\n%sY 1 %ld M 1\n%sY 1 %ld F 0\n", c, asm_[k].x_par1_end, c, asm_[k].x_par2_beg, asm_[k].x_end, c, asm_[k].y_end, c, asm_[k].y_end);
@@ -511,689 +517,743 @@ int main(int argc, char **argv)
                 fprintf(m, "* * * M 2\n* * * F 2\n");
                 known = 1;
             }
-        if (!strcmp(ploidy_alias, "X")) { fprintf(m, "* * * M 1\n* * * F 2\n"); known = 1; }
-        if (!strcmp(ploidy_alias, "Y")) { fprintf(m, "* * * M 1\n* * * F 0\n"); known = 1; }
-        if (!strcmp(ploidy_alias, "1")) { fprintf(m, "* * * * 1\n"); known = 1; }
+        if (!strcmp(o->ploidy_alias, "X")) { fprintf(m, "* * * M 1\n* * * F 2\n"); known = 1; }
+        if (!strcmp(o->ploidy_alias, "Y")) { fprintf(m, "* * * M 1\n* * * F 0\n"); known = 1; }
+        if (!strcmp(o->ploidy_alias, "1")) { fprintf(m, "* * * * 1\n"); known = 1; }
         fclose(m);
         if (!known) DIE("--ploidy: GRCh37, GRCh38, X, Y or 1 (or a --ploidy-file)\n");
-        if (ploidy_file) DIE("--ploidy and --ploidy-file exclude each other\n");
-        ploidy_file = "--ploidy";
+        if (o->ploidy_file) DIE("--ploidy and --ploidy-file exclude each other\n");
+        o->ploidy_file = "--ploidy";
     }
-    if (ploidy_file) {
-        FILE *pf = alias_text ? fmemopen(alias_text, strlen(alias_text), "r") : fopen(ploidy_file, "r");
-        if (!pf) DIE("cannot open %s\n", ploidy_file);
-        char ln[1024], c[256], a[64], b[64], sx[64]; int pl;
-        while (fgets(ln, sizeof ln, pf))
-            if (sscanf(ln, "%255s %63s %63s %63s %d", c, a, b, sx, &pl) == 5) {
-                preg = realloc(preg, (size_t)(npreg + 1) * sizeof *preg);
-                preg_t *q = &preg[npreg++];
-                strcpy(q->chrom, c); strcpy(q->sex, sx); q->ploidy = pl;
-                q->from = !strcmp(a, "*") ? -1 : atoi(a); q->to = !strcmp(b, "*") ? -1 : atoi(b);
-                strcpy(last_sex, sx);
-            }
-        fclose(pf);
-    }
-    vio_file *fin = vio_open_read(argv[1]);                  /* VCF, bgzipped VCF or BCF (hts_open of vcfcall.c) */
+    if (!o->ploidy_file) return;
+    FILE *pf = alias_text ? fmemopen(alias_text, strlen(alias_text), "r") : fopen(o->ploidy_file, "r");
+    if (!pf) DIE("cannot open %s\n", o->ploidy_file);
+    char ln[1024], c[256], a[64], b[64], sx[64]; int pl;
+    while (fgets(ln, sizeof ln, pf))
+        if (sscanf(ln, "%255s %63s %63s %63s %d", c, a, b, sx, &pl) == 5) {
+            P->reg = realloc(P->reg, (size_t)(P->n + 1) * sizeof *P->reg);
+            preg_t *q = &P->reg[P->n++];
+            strcpy(q->chrom, c); strcpy(q->sex, sx); q->ploidy = pl;
+            q->from = !strcmp(a, "*") ? -1 : atoi(a); q->to = !strcmp(b, "*") ? -1 : atoi(b);
+            strcpy(P->last_sex, sx);
+        }
+    fclose(pf);
+}
+/* the input and its header; which of the device options take effect in this run */
+static vio_file *open_input(opt_t *o, vio_hdr **hdr)
+{
+    vio_file *fin = vio_open_read(o->in_path);               /* VCF, bgzipped VCF or BCF (hts_open of vcfcall.c) */
     if (!fin) DIE("%s\n", vio_error());
-    vio_hdr *hdr = vio_read_hdr(fin);
-    if (!hdr) DIE("%s\n", vio_error());
-    dev_in = dev_in && vio_is_bcf(fin) && !cals && !gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
-    dev_rec = dev_rec && (out_mode == 'u' || out_mode == 'b') && !gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
-    dev_keys = dev_keys && dev_in && dev_rec;                  /* the input's bytes in HBM and key blocks to splice: both ends on the device */
-    unsigned char *ibuf = NULL; size_t ibuf_l = 0, ibuf_m = 0;   /* --device-input: the records' per-sample blocks, back to back */
-    const double t0 = now_s();
-    char *buf = NULL; size_t bufcap = 0;
-    rec_t *recs = NULL; int n = 0, cap = 0, S = -1, ngmax = 1, S_in = -1;
-    int *col = NULL;                              /* output sample s = input column col[s] (bcf_subset with -S) */
-    char **names = NULL;                          /* names of the input columns */
-    char (*spec)[64] = NULL;                      /* its ploidy ("0", "1", "2") or sex name */
-    for (int i = 0; i < vio_hdr_nlines(hdr); ++i) header_line(vio_hdr_line(hdr, i));
-    {
-        S_in = S = vio_hdr_nsamples(hdr);
-        names = malloc((size_t)(S > 0 ? S : 1) * sizeof *names);
-        for (int s = 0; s < S; ++s) names[s] = strdup(vio_hdr_sample(hdr, s));
-        col = malloc((size_t)(S > 0 ? S : 1) * sizeof *col);
-        spec = malloc((size_t)(S > 0 ? S : 1) * sizeof *spec);
-        for (int s = 0; s < S; ++s) { col[s] = s; strcpy(spec[s], ploidy_file ? last_sex : "2"); }   /* vcfcall.c:645-650 */
-        if (smpl_file) {
-            char *lbuf = NULL;
-            if (smpl_list) { lbuf = strdup(smpl_list); for (char *c = lbuf; *c; ++c) if (*c == ',') *c = '\n'; }
-            FILE *sf = smpl_list ? fmemopen(lbuf, strlen(lbuf), "r") : fopen(smpl_file, "r");
-            if (!sf) DIE("cannot open %s\n", smpl_file);
-            char ln[1024]; int m = 0;
-            while (fgets(ln, sizeof ln, sf)) {
-                char w[6][256]; const int nw = sscanf(ln, "%255s %255s %255s %255s %255s %255s", w[0], w[1], w[2], w[3], w[4], w[5]);
-                if (nw < 1 || w[0][0] == '#') continue;
-                const char *name = nw >= 5 ? w[1] : w[0];                   /* PED: family, sample, father, mother, sex */
-                const char *sp = nw >= 5 ? (!strcmp(w[4], "1") ? "M" : "F") : nw >= 2 ? w[1] : "2";
-                int i;
-                for (i = 0; i < S_in; ++i) if (!strcmp(names[i], name)) break;
-                if (i == S_in) continue;                                    /* not in the VCF: ignored */
-                if (m == S_in) DIE("too many samples in %s\n", smpl_file);
-                col[m] = i; strcpy(spec[m], sp); ++m;
-            }
-            fclose(sf); free(lbuf);
-            S = m;
+    if (!(*hdr = vio_read_hdr(fin))) DIE("%s\n", vio_error());
+    o->dev_in = o->dev_in && vio_is_bcf(fin) && !cals && !o->gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
+    o->dev_rec = o->dev_rec && (o->out_mode == 'u' || o->out_mode == 'b') && !o->gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
+    o->dev_keys = o->dev_keys && o->dev_in && o->dev_rec;      /* the input's bytes in HBM and key blocks to splice: both ends on the device */
+    return fin;
+}
+/* the samples of the header, or those of -S / -s in that order (vcfcall.c:202-344) */
+static void map_samples(const opt_t *o, const ploidy_t *P, const vio_hdr *hdr, smap_t *M)
+{
+    memset(M, 0, sizeof *M); M->ngrp = 1;
+    const int S_in = M->S_in = M->S = vio_hdr_nsamples(hdr);
+    M->names = malloc((size_t)(S_in > 0 ? S_in : 1) * sizeof *M->names);
+    for (int s = 0; s < S_in; ++s) M->names[s] = strdup(vio_hdr_sample(hdr, s));
+    M->col = malloc((size_t)(S_in > 0 ? S_in : 1) * sizeof *M->col);
+    M->spec = malloc((size_t)(S_in > 0 ? S_in : 1) * sizeof *M->spec);
+    for (int s = 0; s < S_in; ++s) { M->col[s] = s; strcpy(M->spec[s], o->ploidy_file ? P->last_sex : "2"); }   /* vcfcall.c:645-650 */
+    if (!o->smpl_file) return;
+    char *lbuf = NULL;
+    if (o->smpl_list) { lbuf = strdup(o->smpl_list); for (char *c = lbuf; *c; ++c) if (*c == ',') *c = '\n'; }
+    FILE *sf = o->smpl_list ? fmemopen(lbuf, strlen(lbuf), "r") : fopen(o->smpl_file, "r");
+    if (!sf) DIE("cannot open %s\n", o->smpl_file);
+    char ln[1024]; int m = 0;
+    while (fgets(ln, sizeof ln, sf)) {
+        char w[6][256]; const int nw = sscanf(ln, "%255s %255s %255s %255s %255s %255s", w[0], w[1], w[2], w[3], w[4], w[5]);
+        if (nw < 1 || w[0][0] == '#') continue;
+        const char *name = nw >= 5 ? w[1] : w[0];                   /* PED: family, sample, father, mother, sex */
+        const char *sp = nw >= 5 ? (!strcmp(w[4], "1") ? "M" : "F") : nw >= 2 ? w[1] : "2";
+        int i;
+        for (i = 0; i < S_in; ++i) if (!strcmp(M->names[i], name)) break;
+        if (i == S_in) continue;                                    /* not in the VCF: ignored */
+        if (m == S_in) DIE("too many samples in %s\n", o->smpl_file);
+        M->col[m] = i; strcpy(M->spec[m], sp); ++m;
+    }
+    fclose(sf); free(lbuf); M->S = m;
+}
+/* the unseen allele as vcfcall.c:1102-1111 finds it: 1 + the index of the first ALT that is X, <X> or <*>, or 0 */
+static int unseen_allele(char **alts, int nalt)
+{
+    for (int i = 0; i < nalt; ++i) { const char *a = alts[i]; if (a[0] == 'X' || (a[0] == '<' && (a[1] == 'X' || a[1] == '*') && a[2] == '>')) return 1 + i; }
+    return 0;
+}
+/* -C alleles: pair the record with a target, rewrite it.  The line to call (malloc'ed), or NULL: the record is passed over */
+static char *pair_with_target(const opt_t *o, const char *buf, int S_in, recs_t *R)
+{
+    char *owned = NULL, *c2 = strdup(buf); int nf2; char **f2 = split(c2, '\t', &nf2);
+    if (nf2 != 9 + S_in) DIE("malformed VCF\n");
+    int nalt2 = 0; char *ac = strdup(f2[4]), **av = split(ac, ',', &nalt2);
+    if (!strcmp(f2[4], ".")) nalt2 = 0;
+    const int pos2 = atoi(f2[1]), ti = pick_target(f2[0], pos2, f2[3], av, nalt2);
+    if (ti >= 0) {
+        tgt[ti].used = 1; int un = unseen_allele(av, nalt2);
+        owned = constrain_line(buf, &tgt[ti], S_in, &un);
+        if (owned && unwanted_site(owned, o->acgt_only, o->skip_kind)) { free(owned); owned = NULL; }   /* (the skipped record flushes no targets either: vcfcall.c:1095-1099 come before tgt_flush) */
+        if (owned && insert_missed) {                    /* tgt_flush (vcfcall.c:426-455) */
+            const long p0 = pos2 - 1;
+            if (!R->prev_chrom) flush_region(f2[0], 0, p0 - 1);
+            else if (strcmp(R->prev_chrom, f2[0])) { flush_region(R->prev_chrom, R->prev_pos0 + 1, 1L << 40); flush_region(f2[0], 0, p0 - 1); }
+            else flush_region(R->prev_chrom, R->prev_pos0, p0 - 1);
+            free(R->prev_chrom); R->prev_chrom = strdup(f2[0]); R->prev_pos0 = p0;
         }
     }
-    char *prev_chrom = NULL; long prev_pos0 = 0;
-    if (cals) { if (!tgt_file) DIE("-C alleles needs -T targets\n"); tgt_parse(tgt_file); }
-    else if (tgt_file) site_filter_file(tgt_file);           /* -T without -C alleles: the targets restrict the sites (vcfcall.c:612-617) */
-    int rrc;
+    free(av); free(ac); free(f2); free(c2);
+    return owned;
+}
+/* alleles; the unseen allele */
+static void record_alleles(rec_t *r)
+{
+    int nalt = 0; char *alt = strdup(r->fld[4]), **alts = split(alt, ',', &nalt);
+    if (!strcmp(r->fld[4], ".")) nalt = 0;
+    r->nals = 1 + nalt; r->als = malloc((size_t)r->nals * sizeof *r->als); r->als[0] = r->fld[3];
+    for (int i = 0; i < nalt; ++i) r->als[1 + i] = alts[i];
+    r->unseen = unseen_allele(alts, nalt);
+    free(alts);
+    if (r->nals > 5) DIE("more than 5 alleles at %s:%s\n", r->fld[0], r->fld[1]);
+}
+/* the ploidy of every sample at this record (set_ploidy, vcfcall.c:807-825) */
+static void record_ploidy(rec_t *r, const ploidy_t *P, const smap_t *M)
+{
+    const preg_t *preg = P->reg; const int npreg = P->n, S = M->S, pos1 = atoi(r->fld[1]);
+    uint8_t *ploidy = r->ploidy = malloc((size_t)S);
+    for (int s = 0; s < S; ++s) {
+        const char *spec = M->spec[s]; int pl = 2;
+        if (!strcmp(spec, "0") || !strcmp(spec, "1") || !strcmp(spec, "2")) pl = atoi(spec);
+        else {
+            int found = 0;
+            for (int i = 0; i < npreg && !found; ++i)
+                if (preg[i].from >= 0 && !strcmp(preg[i].chrom, r->fld[0]) && !strcmp(preg[i].sex, spec) && preg[i].from <= pos1 && pos1 <= preg[i].to) { pl = preg[i].ploidy; found = 1; }
+            for (int i = 0; i < npreg && !found; ++i)
+                if (preg[i].from < 0 && !strcmp(preg[i].sex, spec)) { pl = preg[i].ploidy; found = 1; }
+            for (int i = 0; i < npreg && !found; ++i)                       /* a sex without a default of its own takes the "*" sex's (ploidy.c:122-127) */
+                if (preg[i].from < 0 && !strcmp(preg[i].sex, "*")) { pl = preg[i].ploidy; found = 1; }
+        }
+        ploidy[s] = (uint8_t)pl;
+    }
+}
+/* the read loop: the records that are called, split into fields; closes the input */
+static void read_records(const opt_t *o, const ploidy_t *P, const smap_t *M, vio_file *fin, vio_hdr *hdr, recs_t *R)
+{
+    memset(R, 0, sizeof *R); R->ngmax = 1;
+    const int S_in = M->S_in;
+    char *buf = NULL; size_t bufcap = 0; int rrc;
+    if (cals) { if (!o->tgt_file) DIE("-C alleles needs -T targets\n"); tgt_parse(o->tgt_file); }
+    else if (o->tgt_file) site_filter_file(o->tgt_file);     /* -T without -C alleles: the targets restrict the sites (vcfcall.c:612-617) */
     for (;;) {
         const void *indiv = NULL; size_t l_indiv = 0; int n_fmt = 0, n_sample = 0;
-        rrc = dev_in ? vio_read_record(fin, hdr, &buf, &bufcap, &indiv, &l_indiv, &n_fmt, &n_sample) : vio_read_line(fin, hdr, &buf, &bufcap);
+        rrc = o->dev_in ? vio_read_record(fin, hdr, &buf, &bufcap, &indiv, &l_indiv, &n_fmt, &n_sample) : vio_read_line(fin, hdr, &buf, &bufcap);
         if (rrc <= 0) break;
-        size_t l = strlen(buf);
-        if (!l) continue;
+        if (!strlen(buf)) continue;
         char *use = buf, *owned = NULL;
-        if (cals) {                                              /* -C alleles: pair the record with a target, rewrite it */
-            char *c2 = strdup(buf); int nf2; char **f2 = split(c2, '\t', &nf2);
-            if (nf2 != 9 + S_in) DIE("malformed VCF\n");
-            int nalt2 = 0; char *ac = strdup(f2[4]), **av = split(ac, ',', &nalt2);
-            if (!strcmp(f2[4], ".")) nalt2 = 0;
-            const int pos2 = atoi(f2[1]);
-            const int ti = pick_target(f2[0], pos2, f2[3], av, nalt2);
-            int skip = ti < 0;
-            if (!skip) {
-                tgt[ti].used = 1;
-                int un = 0;
-                for (int i = 0; i < nalt2; ++i) { const char *a = av[i]; if (!un && (a[0] == 'X' || (a[0] == '<' && (a[1] == 'X' || a[1] == '*') && a[2] == '>'))) un = 1 + i; }
-                owned = constrain_line(buf, &tgt[ti], S_in, &un);
-                if (!owned) skip = 1; else use = owned;
-                if (!skip && unwanted_site(use, acgt_only, skip_kind)) { free(owned); owned = NULL; skip = 1; }   /* (the skipped record flushes no targets either: vcfcall.c:1095-1099 come before tgt_flush) */
-                if (!skip && insert_missed) {                    /* tgt_flush (vcfcall.c:426-455) */
-                    const long p0 = pos2 - 1;
-                    if (!prev_chrom) flush_region(f2[0], 0, p0 - 1);
-                    else if (strcmp(prev_chrom, f2[0])) { flush_region(prev_chrom, prev_pos0 + 1, 1L << 40); flush_region(f2[0], 0, p0 - 1); }
-                    else flush_region(prev_chrom, prev_pos0, p0 - 1);
-                    free(prev_chrom); prev_chrom = strdup(f2[0]); prev_pos0 = p0;
-                }
-            }
-            free(av); free(ac); free(f2); free(c2);
-            if (skip) continue;
-        } else if (unwanted_site(use, acgt_only, skip_kind)) continue;
-        if (n == cap) { cap = cap ? 2 * cap : 1024; recs = realloc(recs, (size_t)cap * sizeof *recs); }
-        if (cals) push_event(0, n);
-        rec_t *r = &recs[n++];
-        r->line = strdup(use);
-        free(owned);
+        if (cals) { if (!(use = owned = pair_with_target(o, buf, S_in, R))) continue; }
+        else if (unwanted_site(use, o->acgt_only, o->skip_kind)) continue;
+        if (R->n == R->cap) { R->cap = R->cap ? 2 * R->cap : 1024; R->rec = realloc(R->rec, (size_t)R->cap * sizeof *R->rec); }
+        if (cals) push_event(0, R->n);
+        rec_t *r = &R->rec[R->n++];
+        r->line = strdup(use); free(owned);
         r->fld = split(r->line, '\t', &r->nfld);
         r->keys = NULL; r->nkeys = 0; r->kjob = NULL;
-        if (dev_in) {                                            /* the block joins the byte buffer; where its keys' values lie */
+        if (o->dev_in) {                                         /* the block joins the byte buffer; where its keys' values lie */
             if (r->nfld != 9 || n_sample != S_in) DIE("malformed VCF\n");
-            if (ibuf_l + l_indiv > ibuf_m) { ibuf_m = (ibuf_l + l_indiv) * 2 + (1 << 20); ibuf = realloc(ibuf, ibuf_m); if (!ibuf) DIE("out of memory\n"); }
-            memcpy(ibuf + ibuf_l, indiv, l_indiv);
-            r->ioff = ibuf_l; r->ilen = l_indiv; r->n_fmt = n_fmt; ibuf_l += l_indiv;
+            if (R->ibuf_l + l_indiv > R->ibuf_m) { R->ibuf_m = (R->ibuf_l + l_indiv) * 2 + (1 << 20); R->ibuf = realloc(R->ibuf, R->ibuf_m); if (!R->ibuf) DIE("out of memory\n"); }
+            memcpy(R->ibuf + R->ibuf_l, indiv, l_indiv);
+            r->ioff = R->ibuf_l; r->ilen = l_indiv; r->n_fmt = n_fmt; R->ibuf_l += l_indiv;
             r->keys = malloc((size_t)(n_fmt > 0 ? (n_fmt < 64 ? n_fmt : 64) : 1) * sizeof *r->keys);
             if ((r->nkeys = vio_indiv_keys(hdr, indiv, l_indiv, n_fmt, n_sample, r->keys)) < 0) DIE("%s\n", vio_error());
         } else
         if (S_in < 0 || r->nfld != 9 + S_in) DIE("malformed VCF\n");
-        /* alleles; the unseen allele as vcfcall.c:1102-1111 finds it */
-        int nalt = 0; char *alt = strdup(r->fld[4]), **alts = split(alt, ',', &nalt);
-        if (!strcmp(r->fld[4], ".")) nalt = 0;
-        r->nals = 1 + nalt; r->als = malloc((size_t)r->nals * sizeof *r->als); r->als[0] = r->fld[3]; r->unseen = 0;
-        for (int i = 0; i < nalt; ++i) {
-            r->als[1 + i] = alts[i];
-            const char *a = alts[i];
-            if (!r->unseen && (a[0] == 'X' || (a[0] == '<' && (a[1] == 'X' || a[1] == '*') && a[2] == '>'))) r->unseen = 1 + i;
-        }
-        free(alts);
-        if (r->nals > 5) DIE("more than 5 alleles at %s:%s\n", r->fld[0], r->fld[1]);
-        const int ng = r->nals * (r->nals + 1) / 2;
-        if (ng > ngmax) ngmax = ng;
-        /* the ploidy of every sample at this record (set_ploidy, vcfcall.c:807-825) */
-        r->ploidy = malloc((size_t)S);
-        const int pos1 = atoi(r->fld[1]);
-        for (int s = 0; s < S; ++s) {
-            int pl = 2;
-            if (!strcmp(spec[s], "0") || !strcmp(spec[s], "1") || !strcmp(spec[s], "2")) pl = atoi(spec[s]);
-            else {
-                int found = 0;
-                for (int i = 0; i < npreg && !found; ++i)
-                    if (preg[i].from >= 0 && !strcmp(preg[i].chrom, r->fld[0]) && !strcmp(preg[i].sex, spec[s]) && preg[i].from <= pos1 && pos1 <= preg[i].to) { pl = preg[i].ploidy; found = 1; }
-                for (int i = 0; i < npreg && !found; ++i)
-                    if (preg[i].from < 0 && !strcmp(preg[i].sex, spec[s])) { pl = preg[i].ploidy; found = 1; }
-                for (int i = 0; i < npreg && !found; ++i)                       /* a sex without a default of its own takes the "*" sex's (ploidy.c:122-127) */
-                    if (preg[i].from < 0 && !strcmp(preg[i].sex, "*")) { pl = preg[i].ploidy; found = 1; }
-            }
-            r->ploidy[s] = (uint8_t)pl;
-        }
+        record_alleles(r); record_ploidy(r, P, M);
+        if (r->nals * (r->nals + 1) / 2 > R->ngmax) R->ngmax = r->nals * (r->nals + 1) / 2;
     }
     if (rrc < 0) DIE("%s\n", vio_error());
     vio_close(fin);
-    t_read = now_s() - t0;
-    if (cals && insert_missed) {                                 /* the targets behind the last record, then the sequences without any */
-        if (prev_chrom) flush_region(prev_chrom, prev_pos0, 1L << 40);
-        for (int x = 0; x < n_tgt; ++x) if (!tgt[tgt_sorted[x]].used) flush_region(tgt[tgt_sorted[x]].chrom, 0, 1L << 40);
-    }
-    if (S <= 0) DIE("no samples\n");
+}
+/* -i: the targets behind the last record, then the sequences without any */
+static void flush_last_targets(const recs_t *R)
+{
+    if (!cals || !insert_missed) return;
+    if (R->prev_chrom) flush_region(R->prev_chrom, R->prev_pos0, 1L << 40);
+    for (int x = 0; x < n_tgt; ++x) if (!tgt[tgt_sorted[x]].used) flush_region(tgt[tgt_sorted[x]].chrom, 0, 1L << 40);
+}
 
-    /* ---- -G: the group of every sample; ids in the order the groups first appear in the file (mcall.c:308-330) ---- */
-    int32_t *grp = NULL; int ngrp = 1;
-    if (grp_arg && !strcmp(grp_arg, "-")) {
-        grp = malloc((size_t)S * 4); ngrp = S;
-        for (int s = 0; s < S; ++s) grp[s] = s;
-    } else if (grp_arg) {
-        FILE *gf = fopen(grp_arg, "r");
-        if (!gf) DIE("cannot open %s\n", grp_arg);
-        grp = malloc((size_t)S * 4);
-        for (int s = 0; s < S; ++s) grp[s] = -1;
-        char (*gname)[256] = NULL; char ln[1024], w0[256], w1[256]; ngrp = 0;
+/* ---- -G: the group of every sample; ids in the order the groups first appear in the file (mcall.c:308-330) ---- */
+static void read_groups(opt_t *o, smap_t *M)
+{
+    const int S = M->S;
+    if (o->grp_arg && !strcmp(o->grp_arg, "-")) {
+        M->grp = malloc((size_t)S * 4); M->ngrp = S;
+        for (int s = 0; s < S; ++s) M->grp[s] = s;
+    } else if (o->grp_arg) {
+        FILE *gf = fopen(o->grp_arg, "r");
+        if (!gf) DIE("cannot open %s\n", o->grp_arg);
+        M->grp = malloc((size_t)S * 4);
+        for (int s = 0; s < S; ++s) M->grp[s] = -1;
+        char (*gname)[256] = NULL; char ln[1024], w0[256], w1[256]; int ngrp = 0;
         while (fgets(ln, sizeof ln, gf)) {
             if (sscanf(ln, "%255s %255s", w0, w1) != 2 || w0[0] == '#') continue;
             int s, g;
-            for (s = 0; s < S; ++s) if (!strcmp(names[col[s]], w0)) break;
+            for (s = 0; s < S; ++s) if (!strcmp(M->names[M->col[s]], w0)) break;
             if (s == S) continue;                                           /* not among the samples called */
             for (g = 0; g < ngrp; ++g) if (!strcmp(gname[g], w1)) break;
             if (g == ngrp) { gname = realloc(gname, (size_t)(ngrp + 1) * sizeof *gname); strcpy(gname[ngrp++], w1); }
-            grp[s] = g;
+            M->grp[s] = g;
         }
         fclose(gf); free(gname);
-        for (int s = 0; s < S; ++s) if (grp[s] < 0) DIE("sample %s is in no group of %s\n", names[col[s]], grp_arg);
+        M->ngrp = ngrp;
+        for (int s = 0; s < S; ++s) if (M->grp[s] < 0) DIE("sample %s is in no group of %s\n", M->names[M->col[s]], o->grp_arg);
     }
-    if (ngrp > 1 && !grp_tag) grp_tag = has_fmt_qs ? "QS" : has_fmt_ad ? "AD" : NULL;       /* mcall.c:272-281 */
-    if (ngrp > 1 && !grp_tag) DIE("-G needs FORMAT/QS or FORMAT/AD\n");
-    int namax = 1;
-    for (int k = 0; k < n; ++k) if (recs[k].nals > namax) namax = recs[k].nals;
+    if (M->ngrp > 1 && !o->grp_tag) o->grp_tag = has_fmt_qs ? "QS" : has_fmt_ad ? "AD" : NULL;       /* mcall.c:272-281 */
+    if (M->ngrp > 1 && !o->grp_tag) DIE("-G needs FORMAT/QS or FORMAT/AD\n");
+}
 
-    /* ---- what mcall() reads from the records: PL planes (missing / vector_end kept), QS, I16 ---- */
-    const double t1 = now_s();
-    int32_t *nals = malloc((size_t)n * 4), *unseen = malloc((size_t)n * 4);
-    int32_t *pl = dev_in ? NULL : malloc((size_t)n * ngmax * S * 4);
-    /* --device-input: no host planes; per record where the PL vector (and the -G tag's) lies in the byte buffer */
-    const int want_ad = ngrp > 1;
-    bcfgpu_bcf_vec *vec_pl = dev_in ? calloc((size_t)n + 1, sizeof *vec_pl) : NULL, *vec_ad = dev_in && want_ad ? calloc((size_t)n + 1, sizeof *vec_ad) : NULL;
-    float *qs = calloc((size_t)n * 5, 4), *i16 = calloc((size_t)n * 16, 4);
-    int32_t *ad = want_ad && !dev_in ? malloc((size_t)n * namax * S * 4) : NULL;
-    int32_t *pan = prior_an_tag[0] ? malloc((size_t)n * 4) : NULL, *pac = prior_an_tag[0] ? malloc((size_t)n * 4 * 4) : NULL;
-    const size_t l_pan = strlen(prior_an_tag), l_pac = strlen(prior_ac_tag);
+/* ---- what mcall() reads from the records ---- */
+/* FORMAT/PL and the -G tag among the record's keys; --device-input: where their vectors lie in the byte buffer */
+static void format_lookup(const opt_t *o, rec_t *r, int want_ad, bcfgpu_bcf_vec *vec_pl, bcfgpu_bcf_vec *vec_ad)
+{
+    r->pl_idx = r->ad_idx = -1;
+    int nk = r->nkeys; char *fmt = NULL, **keys = NULL;          /* the keys' names: the block's, or the FORMAT column's */
+    if (!o->dev_in) { fmt = strdup(r->fld[8]); keys = split(fmt, ':', &nk); }
+    for (int i = 0; i < nk; ++i) {
+        const char *id = keys ? keys[i] : r->keys[i].id;
+        if (!strcmp(id, "PL")) r->pl_idx = i;
+        if (want_ad && !strcmp(id, o->grp_tag)) r->ad_idx = i;
+    }
+    free(keys); free(fmt);
+    if (r->pl_idx < 0) DIE("no FORMAT/PL at %s:%s\n", r->fld[0], r->fld[1]);
+    if (want_ad && r->ad_idx < 0) DIE("FORMAT/%s is required with -G (%s:%s)\n", o->grp_tag, r->fld[0], r->fld[1]);     /* mcall.c:1476 */
+    if (!o->dev_in) return;
+    const vio_indiv_key *kp = &r->keys[r->pl_idx], *ka = want_ad ? &r->keys[r->ad_idx] : NULL;
+    if (kp->type < 1 || kp->type > 3) DIE("FORMAT/PL is not an integer vector at %s:%s\n", r->fld[0], r->fld[1]);
+    if (ka && (ka->type < 1 || ka->type > 3)) DIE("FORMAT/%s is not an integer vector at %s:%s\n", o->grp_tag, r->fld[0], r->fld[1]);
+    vec_pl->off = r->ioff + kp->off; vec_pl->type = kp->type; vec_pl->width = kp->width;
+    if (ka) { vec_ad->off = r->ioff + ka->off; vec_ad->type = ka->type; vec_ad->width = ka->width; }
+}
+/* a sample's value list of key `idx` into column s of a [width][S] plane; without the key the first value is missing */
+static void parse_int_list(char **vals, int nv, int idx, int32_t *plane, int width, int S, int s)
+{
+    if (idx < nv) {
+        int np; char **pv = split(vals[idx], ',', &np);
+        for (int j = 0; j < np && j < width; ++j) plane[(size_t)j * S + s] = !strcmp(pv[j], ".") ? BCFGPU_INT32_MISSING : atoi(pv[j]);
+        free(pv);
+    } else plane[s] = BCFGPU_INT32_MISSING;
+}
+/* INFO/QS, INFO/I16 and the -F tags of record k */
+static void parse_info(const opt_t *o, const rec_t *r, hplanes_t *H, int k)
+{
+    const size_t l_pan = strlen(o->prior_an_tag), l_pac = strlen(o->prior_ac_tag);
+    char *info = strdup(r->fld[7]); int ni; char **iv = split(info, ';', &ni);
+    for (int i = 0; i < ni; ++i) {
+        if (H->pan && !strncmp(iv[i], o->prior_an_tag, l_pan) && iv[i][l_pan] == '=') {        /* mcall.c:1499-1520 */
+            if (!strchr(iv[i], ',')) H->pan[k] = atoi(iv[i] + l_pan + 1);
+            continue;
+        }
+        if (H->pan && !strncmp(iv[i], o->prior_ac_tag, l_pac) && iv[i][l_pac] == '=') {
+            char *c = strdup(iv[i] + l_pac + 1); int nv; char **v = split(c, ',', &nv);
+            for (int j = 0; j < nv && j < 4; ++j) H->pac[(size_t)k * 4 + j] = !strcmp(v[j], ".") ? BCFGPU_INT32_MISSING : atoi(v[j]);
+            free(v); free(c);
+            continue;
+        }
+        const int is_qs = !strncmp(iv[i], "QS=", 3);
+        if (!is_qs && strncmp(iv[i], "I16=", 4)) continue;
+        float *dst = is_qs ? H->qs + (size_t)k * 5 : H->i16 + (size_t)k * 16;
+        int nv; char **v = split(strchr(iv[i], '=') + 1, ',', &nv);
+        for (int j = 0; j < nv && j < (is_qs ? 5 : 16); ++j) dst[j] = (float)atof(v[j]);
+        free(v);
+    }
+    free(iv); free(info);
+}
+static void build_planes(const opt_t *o, const smap_t *M, recs_t *R, hplanes_t *H)
+{
+    const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_in = o->dev_in;
+    memset(H, 0, sizeof *H);
+    H->nals = malloc((size_t)n * 4); H->unseen = malloc((size_t)n * 4);
+    H->pl = dev_in ? NULL : malloc((size_t)n * ngmax * S * 4);
+    H->want_ad = M->ngrp > 1;
+    H->vec_pl = dev_in ? calloc((size_t)n + 1, sizeof *H->vec_pl) : NULL; H->vec_ad = dev_in && H->want_ad ? calloc((size_t)n + 1, sizeof *H->vec_ad) : NULL;
+    H->qs = calloc((size_t)n * 5, 4); H->i16 = calloc((size_t)n * 16, 4);
+    H->ad = H->want_ad && !dev_in ? malloc((size_t)n * namax * S * 4) : NULL;
+    H->pan = o->prior_an_tag[0] ? malloc((size_t)n * 4) : NULL; H->pac = o->prior_an_tag[0] ? malloc((size_t)n * 4 * 4) : NULL;
     for (int k = 0; k < n; ++k) {
-        rec_t *r = &recs[k];
-        nals[k] = r->nals; unseen[k] = r->unseen;
-        if (pl) for (size_t i = 0; i < (size_t)ngmax * S; ++i) pl[(size_t)k * ngmax * S + i] = BCFGPU_INT32_VECTOR_END;
-        if (ad) for (size_t i = 0; i < (size_t)namax * S; ++i) ad[(size_t)k * namax * S + i] = BCFGPU_INT32_VECTOR_END;
-        if (pan) { pan[k] = BCFGPU_INT32_MISSING; for (int i = 0; i < 4; ++i) pac[(size_t)k * 4 + i] = BCFGPU_INT32_VECTOR_END; }
-        /* FORMAT/PL */
-        r->pl_idx = r->ad_idx = -1;
-        if (dev_in) {
-            for (int i = 0; i < r->nkeys; ++i) {
-                if (!strcmp(r->keys[i].id, "PL")) r->pl_idx = i;
-                if (want_ad && !strcmp(r->keys[i].id, grp_tag)) r->ad_idx = i;
-            }
-        } else {
-            int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
-            for (int i = 0; i < nk; ++i) {
-                if (!strcmp(keys[i], "PL")) r->pl_idx = i;
-                if (want_ad && !strcmp(keys[i], grp_tag)) r->ad_idx = i;
-            }
-            free(keys); free(fmt);
-        }
-        if (r->pl_idx < 0) DIE("no FORMAT/PL at %s:%s\n", r->fld[0], r->fld[1]);
-        if (want_ad && r->ad_idx < 0) DIE("FORMAT/%s is required with -G (%s:%s)\n", grp_tag, r->fld[0], r->fld[1]);     /* mcall.c:1476 */
-        if (dev_in) {
-            const vio_indiv_key *kp = &r->keys[r->pl_idx], *ka = want_ad ? &r->keys[r->ad_idx] : NULL;
-            if (kp->type < 1 || kp->type > 3) DIE("FORMAT/PL is not an integer vector at %s:%s\n", r->fld[0], r->fld[1]);
-            if (ka && (ka->type < 1 || ka->type > 3)) DIE("FORMAT/%s is not an integer vector at %s:%s\n", grp_tag, r->fld[0], r->fld[1]);
-            vec_pl[k].off = r->ioff + kp->off; vec_pl[k].type = kp->type; vec_pl[k].width = kp->width;
-            if (ka) { vec_ad[k].off = r->ioff + ka->off; vec_ad[k].type = ka->type; vec_ad[k].width = ka->width; }
-        }
+        rec_t *r = &R->rec[k];
+        int32_t *pl = H->pl ? H->pl + (size_t)k * ngmax * S : NULL, *ad = H->ad ? H->ad + (size_t)k * namax * S : NULL;
+        H->nals[k] = r->nals; H->unseen[k] = r->unseen;
+        if (pl) for (size_t i = 0; i < (size_t)ngmax * S; ++i) pl[i] = BCFGPU_INT32_VECTOR_END;
+        if (ad) for (size_t i = 0; i < (size_t)namax * S; ++i) ad[i] = BCFGPU_INT32_VECTOR_END;
+        if (H->pan) { H->pan[k] = BCFGPU_INT32_MISSING; for (int i = 0; i < 4; ++i) H->pac[(size_t)k * 4 + i] = BCFGPU_INT32_VECTOR_END; }
+        format_lookup(o, r, H->want_ad, dev_in ? &H->vec_pl[k] : NULL, H->vec_ad ? &H->vec_ad[k] : NULL);
         for (int s = 0; s < S && !dev_in; ++s) {
-            char *smp = strdup(r->fld[9 + col[s]]); int nv; char **vals = split(smp, ':', &nv);
-            if (r->pl_idx < nv) {
-                int np; char **pv = split(vals[r->pl_idx], ',', &np);
-                for (int j = 0; j < np && j < ngmax; ++j)
-                    pl[((size_t)k * ngmax + j) * S + s] = !strcmp(pv[j], ".") ? BCFGPU_INT32_MISSING : atoi(pv[j]);
-                free(pv);
-            } else pl[((size_t)k * ngmax) * S + s] = BCFGPU_INT32_MISSING;
-            if (ad && r->ad_idx < nv) {
-                int na; char **av = split(vals[r->ad_idx], ',', &na);
-                for (int j = 0; j < na && j < namax; ++j)
-                    ad[((size_t)k * namax + j) * S + s] = !strcmp(av[j], ".") ? BCFGPU_INT32_MISSING : atoi(av[j]);
-                free(av);
-            } else if (ad) ad[((size_t)k * namax) * S + s] = BCFGPU_INT32_MISSING;
+            char *smp = strdup(r->fld[9 + M->col[s]]); int nv; char **vals = split(smp, ':', &nv);
+            parse_int_list(vals, nv, r->pl_idx, pl, ngmax, S, s);
+            if (ad) parse_int_list(vals, nv, r->ad_idx, ad, namax, S, s);
             free(vals); free(smp);
         }
-        /* INFO/QS, INFO/I16 */
-        char *info = strdup(r->fld[7]); int ni; char **iv = split(info, ';', &ni);
-        for (int i = 0; i < ni; ++i) {
-            if (pan && !strncmp(iv[i], prior_an_tag, l_pan) && iv[i][l_pan] == '=') {        /* mcall.c:1499-1520 */
-                if (!strchr(iv[i], ',')) pan[k] = atoi(iv[i] + l_pan + 1);
-                continue;
-            }
-            if (pan && !strncmp(iv[i], prior_ac_tag, l_pac) && iv[i][l_pac] == '=') {
-                char *c = strdup(iv[i] + l_pac + 1); int nv; char **v = split(c, ',', &nv);
-                for (int j = 0; j < nv && j < 4; ++j) pac[(size_t)k * 4 + j] = !strcmp(v[j], ".") ? BCFGPU_INT32_MISSING : atoi(v[j]);
-                free(v); free(c);
-                continue;
-            }
-            float *dst = !strncmp(iv[i], "QS=", 3) ? qs + (size_t)k * 5 : !strncmp(iv[i], "I16=", 4) ? i16 + (size_t)k * 16 : NULL;
-            if (!dst) continue;
-            const int lim = dst == qs + (size_t)k * 5 ? 5 : 16;
-            int nv; char **v = split(strchr(iv[i], '=') + 1, ',', &nv);
-            for (int j = 0; j < nv && j < lim; ++j) dst[j] = (float)atof(v[j]);
-            free(v);
-        }
-        free(iv); free(info);
+        parse_info(o, r, H, k);
     }
+}
 
-    t_planes = now_s() - t1;
-
-    /* ---- the device ---- */
-    const double t2 = now_s();
+/* ---- the device ---- */
+/* everything goes up once; the records are called in runs of equal ploidy vectors (the ploidy is per call:
+ * vcfcall.c:807-825 re-initialises it when it changes) -- the planes are [record][...]: a run is a slice */
+static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, const hplanes_t *H, dev_t *D)
+{
+    const rec_t *recs = R->rec; const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_rec = o->dev_rec;
+    memset(D, 0, sizeof *D);
     bcfgpu_cfg cfg; memset(&cfg, 0, sizeof cfg);
     cfg.device = 0; cfg.n_smpl = S; cfg.max_sites = n; cfg.max_reads = 64;
-    cfg.min_baseQ = 13; cfg.capQ = 60; cfg.call_theta = prior; cfg.call_flag = (varonly ? BCFGPU_CALL_VARONLY : 0) | (keepalt ? BCFGPU_CALL_KEEPALT : 0); cfg.n_grp = ngrp; cfg.ploidy_max = 2;
-    cfg.output_tags = out_tags;
-    bcfgpu_ctx *ctx = NULL;
-    CHECK(bcfgpu_create(&cfg, &ctx));
-    /* everything goes up once; the records are called in runs of equal ploidy vectors (the ploidy is per call:
-     * vcfcall.c:807-825 re-initialises it when it changes) -- the planes are [record][...]: a run is a slice */
-    int32_t *d_nals = dev_upload(ctx, nals, (size_t)n * 4), *d_unseen = dev_upload(ctx, unseen, (size_t)n * 4);
-    int32_t *d_plin = NULL, *d_ad = NULL;
-    void *d_indiv = NULL;                                        /* --device-keys: kept until the pass-through keys' blocks are made */
-    if (dev_in) {                                                /* the bytes go up once; the planes are made where mcall() reads them */
+    cfg.min_baseQ = 13; cfg.capQ = 60; cfg.call_theta = o->prior; cfg.call_flag = (o->varonly ? BCFGPU_CALL_VARONLY : 0) | (o->keepalt ? BCFGPU_CALL_KEEPALT : 0); cfg.n_grp = M->ngrp; cfg.ploidy_max = 2;
+    cfg.output_tags = o->out_tags;
+    CHECK(bcfgpu_create(&cfg, &D->ctx)); bcfgpu_ctx *ctx = D->ctx;
+    D->d_nals = dev_upload(ctx, H->nals, (size_t)n * 4); D->d_unseen = dev_upload(ctx, H->unseen, (size_t)n * 4);
+    if (o->dev_in) {                                             /* the bytes go up once; the planes are made where mcall() reads them */
         void *dp = NULL;
-        d_indiv = dev_upload(ctx, ibuf, ibuf_l);
-        const int32_t *cmap = smpl_file ? (const int32_t *)col : NULL;     /* without -S / -s called sample s is input sample s */
-        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4 + 16, &dp)); d_plin = dp;
-        CHECK(bcfgpu_call_decode_bcf(ctx, n, S_in, d_indiv, ibuf_l, vec_pl, cmap, ngmax, d_plin));
-        if (want_ad) {
-            CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); d_ad = dp;
-            CHECK(bcfgpu_call_decode_bcf(ctx, n, S_in, d_indiv, ibuf_l, vec_ad, cmap, namax, d_ad));
+        D->d_indiv = dev_upload(ctx, R->ibuf, R->ibuf_l);
+        const int32_t *cmap = o->smpl_file ? (const int32_t *)M->col : NULL;     /* without -S / -s called sample s is input sample s */
+        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4 + 16, &dp)); D->d_plin = dp;
+        CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_pl, cmap, ngmax, D->d_plin));
+        if (H->want_ad) {
+            CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); D->d_ad = dp;
+            CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_ad, cmap, namax, D->d_ad));
         }
-        if (!dev_keys) { CHECK(bcfgpu_free(ctx, d_indiv)); d_indiv = NULL; }
+        if (!o->dev_keys) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
     } else {
-        d_plin = dev_upload(ctx, pl, (size_t)n * ngmax * S * 4);
-        if (ad) d_ad = dev_upload(ctx, ad, (size_t)n * namax * S * 4);
+        D->d_plin = dev_upload(ctx, H->pl, (size_t)n * ngmax * S * 4);
+        if (H->ad) D->d_ad = dev_upload(ctx, H->ad, (size_t)n * namax * S * 4);
     }
-    float *d_qs = dev_upload(ctx, qs, (size_t)n * 5 * 4), *d_i16 = dev_upload(ctx, i16, (size_t)n * 16 * 4);
-    int32_t *d_grp = grp ? dev_upload(ctx, grp, (size_t)S * 4) : NULL;
-    int32_t *d_pan = pan ? dev_upload(ctx, pan, (size_t)n * 4) : NULL, *d_pac = pan ? dev_upload(ctx, pac, (size_t)n * 16) : NULL;
-    void *d_site, *d_gt, *d_pl, *d_ploidy, *d_gq = NULL, *d_gp = NULL;
-    if (out_tags & BCFGPU_CALL_FMT_GQ) CHECK(bcfgpu_malloc(ctx, (size_t)n * S * 4, &d_gq));
-    if (out_tags & BCFGPU_CALL_FMT_GP) CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4, &d_gp));
-    CHECK(bcfgpu_malloc(ctx, (size_t)n * sizeof(bcfgpu_call_site), &d_site)); CHECK(bcfgpu_malloc(ctx, (size_t)n * 2 * S, &d_gt));
-    CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4, &d_pl)); CHECK(bcfgpu_malloc(ctx, (size_t)S + 16, &d_ploidy));
+    D->d_qs = dev_upload(ctx, H->qs, (size_t)n * 5 * 4); D->d_i16 = dev_upload(ctx, H->i16, (size_t)n * 16 * 4);
+    D->d_grp = M->grp ? dev_upload(ctx, M->grp, (size_t)S * 4) : NULL;
+    D->d_pan = H->pan ? dev_upload(ctx, H->pan, (size_t)n * 4) : NULL; D->d_pac = H->pan ? dev_upload(ctx, H->pac, (size_t)n * 16) : NULL;
+    if (o->out_tags & BCFGPU_CALL_FMT_GQ) CHECK(bcfgpu_malloc(ctx, (size_t)n * S * 4, &D->d_gq));
+    if (o->out_tags & BCFGPU_CALL_FMT_GP) CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4, &D->d_gp));
+    CHECK(bcfgpu_malloc(ctx, (size_t)n * sizeof(bcfgpu_call_site), &D->d_site)); CHECK(bcfgpu_malloc(ctx, (size_t)n * 2 * S, &D->d_gt));
+    CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4, &D->d_pl)); CHECK(bcfgpu_malloc(ctx, (size_t)S + 16, &D->d_ploidy));
     for (int i = 0; i < n; ) {
         int j = i + 1, all2 = 1;
         while (j < n && !memcmp(recs[j].ploidy, recs[i].ploidy, (size_t)S)) ++j;
         for (int s = 0; s < S; ++s) all2 &= recs[i].ploidy[s] == 2;
         bcfgpu_call_in in; memset(&in, 0, sizeof in);
         in.n_sites = j - i; in.n_gt_max = ngmax; in.n_al_max = 0;
-        in.nals = d_nals + i; in.unseen = d_unseen + i; in.pl = d_plin + (size_t)i * ngmax * S; in.qs = d_qs + (size_t)i * 5;
-        in.i16 = d_i16 + (size_t)i * 16;
-        if (d_ad) { in.ad = d_ad + (size_t)i * namax * S; in.n_al_max = namax; in.grp = d_grp; }
-        if (d_pan) { in.prior_an = d_pan + i; in.prior_ac = d_pac + (size_t)i * 4; }
-        if (!all2) { CHECK(bcfgpu_memcpy_h2d(ctx, d_ploidy, recs[i].ploidy, (size_t)S)); in.ploidy = d_ploidy; }
+        in.nals = D->d_nals + i; in.unseen = D->d_unseen + i; in.pl = D->d_plin + (size_t)i * ngmax * S; in.qs = D->d_qs + (size_t)i * 5;
+        in.i16 = D->d_i16 + (size_t)i * 16;
+        if (D->d_ad) { in.ad = D->d_ad + (size_t)i * namax * S; in.n_al_max = namax; in.grp = D->d_grp; }
+        if (D->d_pan) { in.prior_an = D->d_pan + i; in.prior_ac = D->d_pac + (size_t)i * 4; }
+        if (!all2) { CHECK(bcfgpu_memcpy_h2d(ctx, D->d_ploidy, recs[i].ploidy, (size_t)S)); in.ploidy = D->d_ploidy; }
         bcfgpu_call_out out; memset(&out, 0, sizeof out);
-        out.site = (bcfgpu_call_site*)d_site + i; out.gt = (int8_t*)d_gt + (size_t)i * 2 * S; out.pl = (int32_t*)d_pl + (size_t)i * ngmax * S;
-        if (d_gq) out.gq = (int32_t*)d_gq + (size_t)i * S;
-        if (d_gp) out.gp = (float*)d_gp + (size_t)i * ngmax * S;
+        out.site = (bcfgpu_call_site*)D->d_site + i; out.gt = (int8_t*)D->d_gt + (size_t)i * 2 * S; out.pl = (int32_t*)D->d_pl + (size_t)i * ngmax * S;
+        if (D->d_gq) out.gq = (int32_t*)D->d_gq + (size_t)i * S;
+        if (D->d_gp) out.gp = (float*)D->d_gp + (size_t)i * ngmax * S;
         CHECK(bcfgpu_mcall(ctx, &in, &out));
-        CHECK(bcfgpu_sync(ctx));                               /* (d_ploidy is reused by the next run) */
+        CHECK(bcfgpu_sync(ctx));                                      /* (d_ploidy is reused by the next run) */
         i = j;
     }
-    bcfgpu_call_site *cs = malloc((size_t)n * sizeof *cs);
+    D->cs = malloc((size_t)n * sizeof *D->cs);
     /* --device-records: the site records alone come down here (and GP); GT, PL and GQ follow as bytes once the writer's header is known */
-    int8_t *gt = dev_rec ? NULL : malloc((size_t)n * 2 * S); int32_t *opl = dev_rec ? NULL : malloc((size_t)n * ngmax * S * 4);
-    CHECK(bcfgpu_memcpy_d2h(ctx, cs, d_site, (size_t)n * sizeof *cs));
-    if (gt) CHECK(bcfgpu_memcpy_d2h(ctx, gt, d_gt, (size_t)n * 2 * S));
-    if (opl) CHECK(bcfgpu_memcpy_d2h(ctx, opl, d_pl, (size_t)n * ngmax * S * 4));
-    int32_t *gq = d_gq && !dev_rec ? malloc((size_t)n * S * 4) : NULL; float *gp = d_gp ? malloc((size_t)n * ngmax * S * 4) : NULL;
-    if (gq) CHECK(bcfgpu_memcpy_d2h(ctx, gq, d_gq, (size_t)n * S * 4));
-    if (gp) CHECK(bcfgpu_memcpy_d2h(ctx, gp, d_gp, (size_t)n * ngmax * S * 4));
+    D->gt = dev_rec ? NULL : malloc((size_t)n * 2 * S); D->opl = dev_rec ? NULL : malloc((size_t)n * ngmax * S * 4);
+    CHECK(bcfgpu_memcpy_d2h(ctx, D->cs, D->d_site, (size_t)n * sizeof *D->cs));
+    if (D->gt) CHECK(bcfgpu_memcpy_d2h(ctx, D->gt, D->d_gt, (size_t)n * 2 * S));
+    if (D->opl) CHECK(bcfgpu_memcpy_d2h(ctx, D->opl, D->d_pl, (size_t)n * ngmax * S * 4));
+    D->gq = D->d_gq && !dev_rec ? malloc((size_t)n * S * 4) : NULL; D->gp = D->d_gp ? malloc((size_t)n * ngmax * S * 4) : NULL;
+    if (D->gq) CHECK(bcfgpu_memcpy_d2h(ctx, D->gq, D->d_gq, (size_t)n * S * 4));
+    if (D->gp) CHECK(bcfgpu_memcpy_d2h(ctx, D->gp, D->d_gp, (size_t)n * ngmax * S * 4));
     CHECK(bcfgpu_sync(ctx));
-    t_dev = now_s() - t2;
-    const double t3 = now_s();
+}
 
-    /* ---- the output header: the input's, for the samples kept, without the calling-only tags, plus what mcall_init
-     * declares (vcfcall.c:670,703-704; mcall.c:382-394) ---- */
-    if (smpl_file && vio_hdr_subset(hdr, S, col)) DIE("%s\n", vio_error());
+/* ---- the output header: the input's, for the samples kept, without the calling-only tags, plus what mcall_init
+ * declares (vcfcall.c:670,703-704; mcall.c:382-394) ---- */
+static void output_header(const opt_t *o, const smap_t *M, vio_hdr *hdr)
+{
+    if (o->smpl_file && vio_hdr_subset(hdr, M->S, M->col)) DIE("%s\n", vio_error());
     vio_hdr_remove(hdr, "INFO", "QS");
     vio_hdr_remove(hdr, "INFO", "I16");
-    if (gv_n) {                                                  /* gvcf_update_header, on the reader's header (vcfcall.c:661-666) */
+    if (o->gv_n) {                                               /* gvcf_update_header, on the reader's header (vcfcall.c:661-666) */
         vio_hdr_append(hdr, "##INFO=<ID=END,Number=1,Type=Integer,Description=\"End position of the variant described in this record\">");
         vio_hdr_append(hdr, "##INFO=<ID=MinDP,Number=1,Type=Integer,Description=\"Minimum per-sample depth in this gVCF block\">");
     }
     vio_hdr_append(hdr, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">");
-    if (out_tags & BCFGPU_CALL_FMT_GQ) vio_hdr_append(hdr, "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Phred-scaled Genotype Quality\">");
-    if (out_tags & BCFGPU_CALL_FMT_GP) vio_hdr_append(hdr, "##FORMAT=<ID=GP,Number=G,Type=Float,Description=\"Genotype posterior probabilities in the range 0 to 1\">");
+    if (o->out_tags & BCFGPU_CALL_FMT_GQ) vio_hdr_append(hdr, "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Phred-scaled Genotype Quality\">");
+    if (o->out_tags & BCFGPU_CALL_FMT_GP) vio_hdr_append(hdr, "##FORMAT=<ID=GP,Number=G,Type=Float,Description=\"Genotype posterior probabilities in the range 0 to 1\">");
     vio_hdr_append(hdr, "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Allele count in genotypes for each ALT allele, in the same order as listed\">");
     vio_hdr_append(hdr, "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"Total number of alleles in called genotypes\">");
     vio_hdr_append(hdr, "##INFO=<ID=DP4,Number=4,Type=Integer,Description=\"Number of high-quality ref-forward , ref-reverse, alt-forward and alt-reverse bases\">");
     vio_hdr_append(hdr, "##INFO=<ID=MQ,Number=1,Type=Integer,Description=\"Average mapping quality\">");
-    /* ---- --device-records: GT, PL and GQ of the records that will be written, as BCF2 key blocks made in HBM; the key ids are the
-     * output header's.  One call over all records: the size first, then the bytes; one offset per record and key ---- */
-    unsigned char *kblk = NULL; uint64_t *koff = NULL; int n_enc = 0; double t_enc = 0.;
-    unsigned char *pblk = NULL; uint64_t *poff = NULL; long n_pjob = 0, n_phost = 0;      /* --device-keys: the pass-through keys' blocks, one offset a job */
-    if (dev_rec) {
-        const double te = now_s();
-        uint8_t *emit = malloc((size_t)n + 1);
-        for (int k = 0; k < n; ++k) { emit[k] = !(cs[k].ret < 0 || (varonly && cs[k].ret == 0)); n_enc += emit[k]; }      /* the record loop's rule */
-        int32_t kid[BCFGPU_CALL_BCF_NKEYS];
-        kid[BCFGPU_CALL_BCF_GT] = vio_hdr_fmt_id(hdr, "GT"); kid[BCFGPU_CALL_BCF_PL] = vio_hdr_fmt_id(hdr, "PL");
-        kid[BCFGPU_CALL_BCF_GQ] = d_gq ? vio_hdr_fmt_id(hdr, "GQ") : 0;
-        if (kid[BCFGPU_CALL_BCF_PL] < 0) DIE("FORMAT tag PL is not defined in the header\n");
-        void *d_emit = dev_upload(ctx, emit, (size_t)n), *d_koff = NULL, *d_kblk = NULL;
-        const size_t n_off = (size_t)n * BCFGPU_CALL_BCF_NKEYS + 1;
-        CHECK(bcfgpu_malloc(ctx, n_off * 8, &d_koff));
-        bcfgpu_call_out planes; memset(&planes, 0, sizeof planes);
-        planes.site = d_site; planes.gt = d_gt; planes.pl = d_pl; planes.gq = d_gq;
-        uint64_t need = 0;
-        int rc = bcfgpu_call_encode_bcf(ctx, n, ngmax, &planes, kid, d_emit, NULL, 0, d_koff, &need);
-        if (rc && rc != BCFGPU_E_RANGE) DIE("bcfgpu_call_encode_bcf: %s (%d)\n", bcfgpu_last_error(), rc);
-        koff = malloc(n_off * 8); kblk = malloc(need ? need : 1);
-        if (need) {
-            CHECK(bcfgpu_malloc(ctx, need, &d_kblk));
-            CHECK(bcfgpu_call_encode_bcf(ctx, n, ngmax, &planes, kid, d_emit, d_kblk, need, d_koff, &need));
-            CHECK(bcfgpu_memcpy_d2h(ctx, kblk, d_kblk, need));
+}
+
+/* ---- --device-records: GT, PL and GQ of the records that will be written, as BCF2 key blocks made in HBM; the key ids are the
+ * output header's.  One call over all records: the size first, then the bytes; one offset per record and key ---- */
+typedef struct { bcfgpu_ctx *ctx; int n, ngmax; bcfgpu_call_out planes; int32_t kid[BCFGPU_CALL_BCF_NKEYS]; const void *d_emit; } enc_arg;
+static int enc_call(void *arg, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *need)
+{
+    const enc_arg *a = arg;
+    return bcfgpu_call_encode_bcf(a->ctx, a->n, a->ngmax, &a->planes, a->kid, a->d_emit, d_buf, cap, d_off, need);
+}
+static void encode_call_blocks(const opt_t *o, const recs_t *R, const dev_t *D, const vio_hdr *hdr, blocks_t *B)
+{
+    const int n = R->n;
+    B->emit = malloc((size_t)n + 1);
+    for (int k = 0; k < n; ++k) { B->emit[k] = !(D->cs[k].ret < 0 || (o->varonly && D->cs[k].ret == 0)); B->n_enc += B->emit[k]; }      /* the record loop's rule */
+    enc_arg a; memset(&a, 0, sizeof a);
+    a.ctx = D->ctx; a.n = n; a.ngmax = R->ngmax;
+    a.kid[BCFGPU_CALL_BCF_GT] = vio_hdr_fmt_id(hdr, "GT"); a.kid[BCFGPU_CALL_BCF_PL] = vio_hdr_fmt_id(hdr, "PL");
+    a.kid[BCFGPU_CALL_BCF_GQ] = D->d_gq ? vio_hdr_fmt_id(hdr, "GQ") : 0;
+    if (a.kid[BCFGPU_CALL_BCF_PL] < 0) DIE("FORMAT tag PL is not defined in the header\n");
+    a.d_emit = B->d_emit = dev_upload(D->ctx, B->emit, (size_t)n);
+    a.planes.site = D->d_site; a.planes.gt = D->d_gt; a.planes.pl = D->d_pl; a.planes.gq = D->d_gq;
+    encode_two_pass(D->ctx, enc_call, &a, "bcfgpu_call_encode_bcf", (size_t)n * BCFGPU_CALL_BCF_NKEYS + 1, &B->kblk, &B->koff);
+}
+
+/* ---- --device-keys: a job for every integer pass-through key of every record that is written; the blocks are made from the
+ * input's bytes where --device-input left them, with the sample map it passed and the site records' als_map ---- */
+typedef struct { bcfgpu_ctx *ctx; int32_t n_job; const bcfgpu_bcf_key *job; int S_in, n; const void *d_indiv; size_t l_indiv; const int32_t *cmap; const void *d_site, *d_emit; } remap_arg;
+static int remap_call(void *arg, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *need)
+{
+    const remap_arg *a = arg;
+    return bcfgpu_call_remap_bcf(a->ctx, a->n_job, a->job, a->S_in, a->d_indiv, a->l_indiv, a->cmap, a->d_site, a->n, a->d_emit, d_buf, cap, d_off, need);
+}
+static void encode_key_blocks(const opt_t *o, const smap_t *M, recs_t *R, dev_t *D, const vio_hdr *hdr, blocks_t *B)
+{
+    size_t cap_job = 0; bcfgpu_bcf_key *job = NULL;
+    for (int k = 0; k < R->n; ++k) {
+        rec_t *r = &R->rec[k];
+        if (!B->emit[k]) continue;
+        r->kjob = malloc((size_t)(r->nkeys ? r->nkeys : 1) * sizeof *r->kjob);
+        for (int i = 0; i < r->nkeys; ++i) {
+            const vio_indiv_key *q = &r->keys[i];
+            r->kjob[i] = -1;
+            if (i == r->pl_idx || !strcmp(q->id, "GT") || vio_hdr_fmt_type(hdr, q->dict) != VIO_TYPE_INT) continue;
+            if (q->type < 0 || q->type > 3 || q->width < 0 || q->width > BCFGPU_BCF_KEY_MAX_WIDTH) continue;
+            const int id = vio_hdr_fmt_id(hdr, q->id);
+            if (id < 0) continue;
+            if ((size_t)B->n_pjob == cap_job) { cap_job = cap_job ? 2 * cap_job : 4096; job = realloc(job, cap_job * sizeof *job); if (!job) DIE("out of memory\n"); }
+            bcfgpu_bcf_key *j = &job[B->n_pjob];
+            j->off = r->ioff + q->off; j->site = k; j->key_id = id; j->type = q->type; j->width = q->width; j->nals = r->nals;
+            j->flags = is_numberR(fmtR, n_fmtR, q->id, strlen(q->id));
+            r->kjob[i] = (int)B->n_pjob++;
         }
-        CHECK(bcfgpu_memcpy_d2h(ctx, koff, d_koff, n_off * 8));
+    }
+    if (B->n_pjob > INT32_MAX - 1) DIE("too many pass-through keys for one call\n");
+    if (B->n_pjob) {
+        remap_arg a = { D->ctx, (int32_t)B->n_pjob, job, M->S_in, R->n, D->d_indiv, R->ibuf_l, o->smpl_file ? (const int32_t *)M->col : NULL, D->d_site, B->d_emit };
+        encode_two_pass(D->ctx, remap_call, &a, "bcfgpu_call_remap_bcf", (size_t)B->n_pjob + 1, &B->pblk, &B->poff);
+    } else B->poff = calloc(1, 8);
+    free(job);
+    CHECK(bcfgpu_free(D->ctx, D->d_indiv)); D->d_indiv = NULL;
+}
+
+/* ---- -g: gVCF blocks over the records that are written (vcfcall.c:1145-1149; gvcf_write, gvcf.c:88-226).  What
+ * gvcf_write looks at goes to the device as arrays: may the record join (mcall() returned 1: the reference allele alone),
+ * FORMAT/DP of every sample, position, sequence, INFO/END; the block table and the blocks' DP come back. ---- */
+static void gvcf_blocks(const opt_t *o, const smap_t *M, const recs_t *R, const dev_t *D, gvcf_t *G)
+{
+    bcfgpu_ctx *ctx = D->ctx; const int n = R->n, S = M->S;
+    int gv_nw = 0;
+    G->w = malloc((size_t)(n + 1) * 4);
+    int32_t *pos = malloc((size_t)(n + 1) * 4), *rid = malloc((size_t)(n + 1) * 4), *endp = malloc((size_t)(n + 1) * 4);
+    uint8_t *ro = malloc((size_t)n + 1); int32_t *dp = malloc(((size_t)n * S + 1) * 4);
+    char **chroms = NULL; int nchrom = 0;
+    for (int k = 0; k < n; ++k) {
+        const rec_t *r = &R->rec[k];
+        if (D->cs[k].ret < 0) { G->w[k] = -1; continue; }
+        const int w = G->w[k] = gv_nw++;
+        pos[w] = atoi(r->fld[1]) - 1; endp[w] = pos[w];
+        int ci; for (ci = 0; ci < nchrom; ++ci) if (!strcmp(chroms[ci], r->fld[0])) break;
+        if (ci == nchrom) { chroms = realloc(chroms, (size_t)(nchrom + 1) * sizeof *chroms); chroms[nchrom++] = r->fld[0]; }
+        rid[w] = ci;
+        ro[w] = D->cs[k].ret == 1;
+        const char *e = strstr(r->fld[7], "END=");
+        if (e && (e == r->fld[7] || e[-1] == ';')) endp[w] = atoi(e + 4) - 1;
+        int nk, dpi = -1; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
+        for (int i = 0; i < nk; ++i) if (!strcmp(keys[i], "DP")) dpi = i;
+        free(keys); free(fmt);
+        for (int s2 = 0; s2 < S; ++s2) {
+            int32_t v = INT32_MIN;                           /* missing: the record stays as it is */
+            if (dpi >= 0) {
+                char *smp = strdup(r->fld[9 + M->col[s2]]); int nv; char **vals = split(smp, ':', &nv);
+                if (dpi < nv && strcmp(vals[dpi], ".")) v = atoi(vals[dpi]);
+                free(vals); free(smp);
+            }
+            dp[(size_t)w * S + s2] = v;
+        }
+    }
+    free(chroms);
+    if (gv_nw) {
+        void *d_pos = dev_upload(ctx, pos, (size_t)gv_nw * 4), *d_rid = dev_upload(ctx, rid, (size_t)gv_nw * 4), *d_end = dev_upload(ctx, endp, (size_t)gv_nw * 4);
+        void *d_ro = dev_upload(ctx, ro, (size_t)gv_nw), *d_dp = dev_upload(ctx, dp, (size_t)gv_nw * S * 4);
+        void *d_blk, *d_min, *d_block, *d_gdp;
+        CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * 4, &d_blk)); CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * 4, &d_min));
+        CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * sizeof(bcfgpu_gvcf_block), &d_block)); CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * S * 4, &d_gdp));
+        bcfgpu_gvcf_in gi; memset(&gi, 0, sizeof gi);
+        gi.n_sites = gv_nw; gi.n_range = o->gv_n; gi.dp_range = o->gv_range; gi.pos = d_pos; gi.rid = d_rid; gi.end = d_end; gi.ref_only = d_ro; gi.dp = d_dp;
+        bcfgpu_gvcf_out go; memset(&go, 0, sizeof go);
+        go.blk = d_blk; go.min_dp = d_min; go.block = d_block; go.dp = d_gdp;
+        int32_t nb = 0;
+        CHECK(bcfgpu_gvcf_blocks(ctx, &gi, &go, &nb));
+        G->blk = malloc((size_t)gv_nw * 4); G->min = malloc((size_t)gv_nw * 4);
+        G->block = malloc((size_t)(nb + 1) * sizeof *G->block); G->dp = malloc(((size_t)nb * S + 1) * 4);
+        CHECK(bcfgpu_memcpy_d2h(ctx, G->blk, d_blk, (size_t)gv_nw * 4)); CHECK(bcfgpu_memcpy_d2h(ctx, G->min, d_min, (size_t)gv_nw * 4));
+        if (nb) { CHECK(bcfgpu_memcpy_d2h(ctx, G->block, d_block, (size_t)nb * sizeof *G->block)); CHECK(bcfgpu_memcpy_d2h(ctx, G->dp, d_gdp, (size_t)nb * S * 4)); }
         CHECK(bcfgpu_sync(ctx));
-        /* ---- --device-keys: a job for every integer pass-through key of every record that is written; the blocks are made from the
-         * input's bytes where --device-input left them, with the sample map it passed and the site records' als_map ---- */
-        if (dev_keys) {
-            size_t cap_job = 0; bcfgpu_bcf_key *job = NULL;
-            for (int k = 0; k < n; ++k) {
-                rec_t *r = &recs[k];
-                if (!emit[k]) continue;
-                r->kjob = malloc((size_t)(r->nkeys ? r->nkeys : 1) * sizeof *r->kjob);
-                for (int i = 0; i < r->nkeys; ++i) {
-                    const vio_indiv_key *q = &r->keys[i];
-                    r->kjob[i] = -1;
-                    if (i == r->pl_idx || !strcmp(q->id, "GT") || vio_hdr_fmt_type(hdr, q->dict) != VIO_TYPE_INT) continue;
-                    if (q->type < 0 || q->type > 3 || q->width < 0 || q->width > BCFGPU_BCF_KEY_MAX_WIDTH) continue;
-                    const int id = vio_hdr_fmt_id(hdr, q->id);
-                    if (id < 0) continue;
-                    if ((size_t)n_pjob == cap_job) { cap_job = cap_job ? 2 * cap_job : 4096; job = realloc(job, cap_job * sizeof *job); if (!job) DIE("out of memory\n"); }
-                    bcfgpu_bcf_key *j = &job[n_pjob];
-                    j->off = r->ioff + q->off; j->site = k; j->key_id = id; j->type = q->type; j->width = q->width; j->nals = r->nals;
-                    j->flags = is_numberR(fmtR, n_fmtR, q->id, strlen(q->id));
-                    r->kjob[i] = (int)n_pjob++;
-                }
-            }
-            if (n_pjob > INT32_MAX - 1) DIE("too many pass-through keys for one call\n");
-            poff = calloc((size_t)n_pjob + 1, 8);
-            if (n_pjob) {
-                const int32_t *cmap = smpl_file ? (const int32_t *)col : NULL;
-                void *d_poff = NULL, *d_pblk = NULL;
-                CHECK(bcfgpu_malloc(ctx, ((size_t)n_pjob + 1) * 8, &d_poff));
-                uint64_t pneed = 0;
-                rc = bcfgpu_call_remap_bcf(ctx, (int32_t)n_pjob, job, S_in, d_indiv, ibuf_l, cmap, d_site, n, d_emit, NULL, 0, d_poff, &pneed);
-                if (rc && rc != BCFGPU_E_RANGE) DIE("bcfgpu_call_remap_bcf: %s (%d)\n", bcfgpu_last_error(), rc);
-                pblk = malloc(pneed ? pneed : 1);
-                if (pneed) {
-                    CHECK(bcfgpu_malloc(ctx, pneed, &d_pblk));
-                    CHECK(bcfgpu_call_remap_bcf(ctx, (int32_t)n_pjob, job, S_in, d_indiv, ibuf_l, cmap, d_site, n, d_emit, d_pblk, pneed, d_poff, &pneed));
-                    CHECK(bcfgpu_memcpy_d2h(ctx, pblk, d_pblk, pneed));
-                }
-                CHECK(bcfgpu_memcpy_d2h(ctx, poff, d_poff, ((size_t)n_pjob + 1) * 8));
-                CHECK(bcfgpu_sync(ctx));
-                if (d_pblk) CHECK(bcfgpu_free(ctx, d_pblk));
-                CHECK(bcfgpu_free(ctx, d_poff));
-            }
-            free(job);
-            CHECK(bcfgpu_free(ctx, d_indiv)); d_indiv = NULL;
-        }
-        free(emit);
-        t_enc = now_s() - te;                                    /* a device stage: counted there, not under writing */
     }
-    vio_file *fout = vio_open_write(out_path, out_mode);
-    if (!fout || vio_write_hdr(fout, hdr)) DIE("%s\n", vio_error());
-    LN = open_memstream(&ln_buf, &ln_len);
-    if (!LN) DIE("open_memstream failed\n");
-    /* ---- -g: gVCF blocks over the records that are written (vcfcall.c:1145-1149; gvcf_write, gvcf.c:88-226).  What
-     * gvcf_write looks at goes to the device as arrays: may the record join (mcall() returned 1: the reference allele alone),
-     * FORMAT/DP of every sample, position, sequence, INFO/END; the block table and the blocks' DP come back. ---- */
-    int32_t *gv_w = NULL, *gv_blk = NULL, *gv_min = NULL, *gv_dp = NULL; bcfgpu_gvcf_block *gv_block = NULL; int gv_nw = 0;
-    if (gv_n) {
-        gv_w = malloc((size_t)(n + 1) * 4);                      /* record k is written record gv_w[k], or -1 */
-        int32_t *pos = malloc((size_t)(n + 1) * 4), *rid = malloc((size_t)(n + 1) * 4), *endp = malloc((size_t)(n + 1) * 4);
-        uint8_t *ro = malloc((size_t)n + 1);
-        int32_t *dp = malloc(((size_t)n * S + 1) * 4);
-        char **chroms = NULL; int nchrom = 0;
-        for (int k = 0; k < n; ++k) {
-            const rec_t *r = &recs[k];
-            if (cs[k].ret < 0) { gv_w[k] = -1; continue; }
-            const int w = gv_nw++;
-            gv_w[k] = w;
-            pos[w] = atoi(r->fld[1]) - 1; endp[w] = pos[w];
-            int ci; for (ci = 0; ci < nchrom; ++ci) if (!strcmp(chroms[ci], r->fld[0])) break;
-            if (ci == nchrom) { chroms = realloc(chroms, (size_t)(nchrom + 1) * sizeof *chroms); chroms[nchrom++] = r->fld[0]; }
-            rid[w] = ci;
-            ro[w] = cs[k].ret == 1;
-            const char *e = strstr(r->fld[7], "END=");
-            if (e && (e == r->fld[7] || e[-1] == ';')) endp[w] = atoi(e + 4) - 1;
-            int nk, dpi = -1; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
-            for (int i = 0; i < nk; ++i) if (!strcmp(keys[i], "DP")) dpi = i;
-            free(keys); free(fmt);
-            for (int s2 = 0; s2 < S; ++s2) {
-                int32_t v = INT32_MIN;                           /* missing: the record stays as it is */
-                if (dpi >= 0) {
-                    char *smp = strdup(r->fld[9 + col[s2]]); int nv; char **vals = split(smp, ':', &nv);
-                    if (dpi < nv && strcmp(vals[dpi], ".")) v = atoi(vals[dpi]);
-                    free(vals); free(smp);
-                }
-                dp[(size_t)w * S + s2] = v;
-            }
-        }
-        free(chroms);
-        if (gv_nw) {
-            void *d_pos = dev_upload(ctx, pos, (size_t)gv_nw * 4), *d_rid = dev_upload(ctx, rid, (size_t)gv_nw * 4), *d_end = dev_upload(ctx, endp, (size_t)gv_nw * 4);
-            void *d_ro = dev_upload(ctx, ro, (size_t)gv_nw), *d_dp = dev_upload(ctx, dp, (size_t)gv_nw * S * 4);
-            void *d_blk, *d_min, *d_block, *d_gdp;
-            CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * 4, &d_blk)); CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * 4, &d_min));
-            CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * sizeof(bcfgpu_gvcf_block), &d_block)); CHECK(bcfgpu_malloc(ctx, (size_t)gv_nw * S * 4, &d_gdp));
-            bcfgpu_gvcf_in gi; memset(&gi, 0, sizeof gi);
-            gi.n_sites = gv_nw; gi.n_range = gv_n; gi.dp_range = gv_range; gi.pos = d_pos; gi.rid = d_rid; gi.end = d_end; gi.ref_only = d_ro; gi.dp = d_dp;
-            bcfgpu_gvcf_out go; memset(&go, 0, sizeof go);
-            go.blk = d_blk; go.min_dp = d_min; go.block = d_block; go.dp = d_gdp;
-            int32_t nb = 0;
-            CHECK(bcfgpu_gvcf_blocks(ctx, &gi, &go, &nb));
-            gv_blk = malloc((size_t)gv_nw * 4); gv_min = malloc((size_t)gv_nw * 4);
-            gv_block = malloc((size_t)(nb + 1) * sizeof *gv_block); gv_dp = malloc(((size_t)nb * S + 1) * 4);
-            CHECK(bcfgpu_memcpy_d2h(ctx, gv_blk, d_blk, (size_t)gv_nw * 4)); CHECK(bcfgpu_memcpy_d2h(ctx, gv_min, d_min, (size_t)gv_nw * 4));
-            if (nb) { CHECK(bcfgpu_memcpy_d2h(ctx, gv_block, d_block, (size_t)nb * sizeof *gv_block)); CHECK(bcfgpu_memcpy_d2h(ctx, gv_dp, d_gdp, (size_t)nb * S * 4)); }
-            CHECK(bcfgpu_sync(ctx));
-        }
-        free(pos); free(rid); free(endp); free(ro); free(dp);
+    free(pos); free(rid); free(endp); free(ro); free(dp);
+}
+
+/* ---- the record loop (vcfcall.c:1137-1147, mcall.c:1627-1681) ---- */
+typedef struct {
+    const opt_t *o; const smap_t *M; const recs_t *R; const dev_t *D; blocks_t *B; const gvcf_t *G; vio_file *fout; vio_hdr *hdr;
+    char *smp_text; size_t smp_cap;
+    char *hblk, *iblk; size_t hblk_cap, iblk_cap;                /* --device-records: the host keys' blocks, the record's per-sample part */
+} writer_t;
+/* what a record's FORMAT column says of its keys: who makes which */
+typedef struct { char **keys; int nk, called, host_keys; const int *kjob; } fmt_t;
+/* -i: a target that met no record (tgt_flush_region, vcfcall.c:408-424) */
+static void write_missed_target(const writer_t *W, const tgt_t *t)
+{
+    fprintf(LN, "%s\t%d\t.\t%s\t", t->chrom, t->pos, t->als[0]);
+    if (t->nals < 2) fputc('.', LN);
+    for (int i = 1; i < t->nals; ++i) fprintf(LN, "%s%s", i > 1 ? "," : "", t->als[i]);
+    fputs("\t.\t.\t.\tGT", LN);
+    for (int s2 = 0; s2 < W->M->S; ++s2) fputs("\t.", LN);
+    end_record(W->fout, W->hdr);
+}
+/* ALT: the kept alleles in their new order */
+static void print_alt(const rec_t *r, const bcfgpu_call_site *c)
+{
+    const char *al[5] = { 0, 0, 0, 0, 0 };
+    for (int i = 0; i < r->nals; ++i) if (c->als_map[i] >= 0) al[c->als_map[i]] = r->als[i];
+    if (c->nals_new < 2) fputc('.', LN);
+    for (int i = 1; i < c->nals_new; ++i) fprintf(LN, "%s%s", i > 1 ? "," : "", al[i]);
+}
+static void print_gt(const int8_t *gt, size_t k, int S, int s)
+{
+    const int g0 = gt[(k * 2 + 0) * S + s], g1 = gt[(k * 2 + 1) * S + s];
+    if (g0 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g0);
+    if (g1 != BCFGPU_GT_VECTOR_END) { fputc('/', LN); if (g1 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g1); }
+}
+/* record k closes block b: the block's one line (gvcf.c:134-166) */
+static void write_block_line(const writer_t *W, int k, int b)
+{
+    const bcfgpu_gvcf_block *B = &W->G->block[b]; const int S = W->M->S;
+    int kf = k; while (W->G->w[kf] != B->first_site) --kf;      /* the block's first record: alleles and genotypes are its */
+    const rec_t *rf = &W->R->rec[kf];
+    fprintf(LN, "%s\t%d\t.\t%s\t", rf->fld[0], B->start_pos + 1, rf->fld[3]);
+    print_alt(rf, &W->D->cs[kf]);
+    fputs("\t.\t.\t", LN);
+    if (B->start_pos + 1 < B->end1) fprintf(LN, "END=%d;", B->end1);
+    fprintf(LN, "MinDP=%d\tGT:DP", B->min_dp);
+    for (int s2 = 0; s2 < S; ++s2) {
+        fputc('\t', LN);
+        print_gt(W->D->gt, (size_t)kf, S, s2);
+        const int32_t v = W->G->dp[(size_t)b * S + s2];
+        if (v == INT32_MIN) fputs(":.", LN); else fprintf(LN, ":%d", v);
     }
-    /* ---- the record loop (vcfcall.c:1137-1147, mcall.c:1627-1681) ---- */
-    const int n_out = cals ? n_events : n;
-    char *smp_text = NULL; size_t smp_cap = 0;
-    char *hblk = NULL, *iblk = NULL; size_t hblk_cap = 0, iblk_cap = 0;       /* --device-records: the host keys' blocks, the record's per-sample part */
+    end_record(W->fout, W->hdr);
+}
+/* INFO: I16 and QS go, AC / AN / DP4 / MQ come */
+static void print_info(const rec_t *r, const bcfgpu_call_site *c, int gv_min_dp)
+{
+    const int nn = c->nals_new;
+    char *info = strdup(r->fld[7]); int ni, first = 1; char **iv = split(info, ';', &ni);
+    for (int i = 0; i < ni; ++i) {
+        if (!strncmp(iv[i], "I16=", 4) || !strncmp(iv[i], "QS=", 3) || !strcmp(iv[i], ".")) continue;
+        const char *eq = strchr(iv[i], '=');
+        if (eq && nn != r->nals && is_numberR(infoR, n_infoR, iv[i], (size_t)(eq - iv[i]))) {
+            fprintf(LN, "%s%.*s=", first ? "" : ";", (int)(eq - iv[i]), iv[i]);
+            print_numberR(eq + 1, c->als_map, r->nals, nn);
+        } else fprintf(LN, "%s%s", first ? "" : ";", iv[i]);
+        first = 0;
+    }
+    free(iv); free(info);
+    if (nn > 1) { fprintf(LN, "%sAC=", first ? "" : ";"); first = 0; for (int i = 1; i < nn; ++i) fprintf(LN, "%s%d", i > 1 ? "," : "", c->ac[i]); }
+    fprintf(LN, "%sAN=%d", first ? "" : ";", c->an);
+    if (c->has_i16) {
+        fprintf(LN, ";DP4=%d,%d,%d,%d", c->dp4[0], c->dp4[1], c->dp4[2], c->dp4[3]);
+        if (c->mq == BCFGPU_INT32_MISSING) fputs(";MQ=.", LN); else fprintf(LN, ";MQ=%d", c->mq);
+    }
+    if (gv_min_dp == INT32_MIN) fputs(";MinDP=.", LN); else if (gv_min_dp) fprintf(LN, ";MinDP=%d", gv_min_dp);
+}
+/* sample s of record k: GT (unless it is a block already), the input's keys the host makes, GP, GQ */
+static void print_sample_text(const writer_t *W, int k, const fmt_t *F, const char *column, int s)
+{
+    const rec_t *r = &W->R->rec[k]; const bcfgpu_call_site *c = &W->D->cs[k]; const dev_t *D = W->D;
+    const int S = W->M->S, ngmax = W->R->ngmax, dev_rec = W->o->dev_rec, nn = c->nals_new, ngn = nn * (nn + 1) / 2;
+    int nf = 0;                                          /* fields of this sample so far: ':' in front of all but the first */
+    if (!dev_rec || s) fputc('\t', LN);
+    if (!dev_rec) { print_gt(D->gt, (size_t)k, S, s); ++nf; }
+    char *smp = strdup(column); int nv; char **vals = split(smp, ':', &nv);
+    for (int i = 0; i < F->nk; ++i) {
+        if (F->kjob && F->kjob[i] >= 0) continue;
+        if (i == r->pl_idx) {
+            if (c->pl_dropped || dev_rec) continue;
+            if (nf++) fputc(':', LN);
+            int printed = 0;
+            for (int j = 0; j < ngn; ++j) {
+                const int32_t v = D->opl[((size_t)k * ngmax + j) * S + s];
+                if (v == BCFGPU_INT32_VECTOR_END) break;
+                if (printed++) fputc(',', LN);
+                if (v == BCFGPU_INT32_MISSING) fputc('.', LN); else fprintf(LN, "%d", v);
+            }
+            if (!printed) fputc('.', LN);
+        } else if (i < nv && nn != r->nals && is_numberR(fmtR, n_fmtR, F->keys[i], strlen(F->keys[i]))) {
+            if (nf++) fputc(':', LN);
+            print_numberR(vals[i], c->als_map, r->nals, nn);
+        } else fprintf(LN, "%s%s", nf++ ? ":" : "", i < nv ? vals[i] : ".");
+    }
+    if (F->called && D->gp) {
+        if (nf++) fputc(':', LN);
+        int printed = 0;
+        for (int j = 0; j < ngn; ++j) {
+            uint32_t bits; memcpy(&bits, &D->gp[((size_t)k * ngmax + j) * S + s], 4);
+            if (bits == 0x7F800002u) break;
+            if (printed++) fputc(',', LN);
+            if (bits == 0x7F800001u) fputc('.', LN); else fprintf(LN, "%g", (double)D->gp[((size_t)k * ngmax + j) * S + s]);
+        }
+        if (!printed) fputc('.', LN);
+    }
+    if (F->called && D->gq) {
+        const int32_t v = D->gq[(size_t)k * S + s];
+        if (v == BCFGPU_INT32_MISSING) fputs(":.", LN); else fprintf(LN, ":%d", v);
+    }
+    free(vals); free(smp);
+}
+typedef struct { char *dst; size_t len; } cursor_t;
+static void put(cursor_t *c, const void *src, uint64_t b0, uint64_t b1) { memcpy(c->dst + c->len, (const char *)src + b0, (size_t)(b1 - b0)); c->len += (size_t)(b1 - b0); }
+/* --device-records: the record's per-sample part: the device's blocks and the host's (made here from the sample text behind the
+ * head, at head_end of the stream), in the FORMAT column's order */
+static void splice_record(writer_t *W, int k, const fmt_t *F, long head_end)
+{
+    const rec_t *r = &W->R->rec[k]; const blocks_t *B = W->B; const int *kjob = F->kjob, nk = F->nk, with_gp = F->called && W->D->gp;
+    end_head();
+    int nhost = 0; size_t kend[64];
+    if (F->host_keys > 0) {
+        char *hf = malloc(strlen(r->fld[8]) + 8), *o = hf;              /* the host's keys as a FORMAT column of their own */
+        for (int i = 0; i < nk; ++i) if (i != r->pl_idx && !(kjob && kjob[i] >= 0)) o += sprintf(o, "%s%s", o > hf ? ":" : "", F->keys[i]);
+        if (with_gp) o += sprintf(o, "%sGP", o > hf ? ":" : "");
+        if ((nhost = vio_encode_keys(W->hdr, hf, ln_buf + head_end, W->M->S, &W->hblk, &W->hblk_cap, kend)) != F->host_keys) DIE("%s\n", nhost < 0 ? vio_error() : "FORMAT keys lost on the way");
+        free(hf);
+    }
+    const uint64_t *ko = B->koff + (size_t)k * BCFGPU_CALL_BCF_NKEYS, *poff = B->poff;
+    size_t need = (size_t)(ko[BCFGPU_CALL_BCF_NKEYS] - ko[0]) + (nhost ? kend[nhost - 1] : 0);
+    for (int i = 0; kjob && i < nk; ++i) if (kjob[i] >= 0) need += (size_t)(poff[kjob[i] + 1] - poff[kjob[i]]);
+    if (need > W->iblk_cap) { W->iblk_cap = need * 2 + 256; W->iblk = realloc(W->iblk, W->iblk_cap); if (!W->iblk) DIE("out of memory\n"); }
+    cursor_t cur = { W->iblk, 0 }; int hk = 0;
+    put(&cur, B->kblk, ko[BCFGPU_CALL_BCF_GT], ko[BCFGPU_CALL_BCF_GT + 1]);
+    for (int i = 0; i < nk + with_gp; ++i) {                    /* (GP, the host's, comes behind the input's keys) */
+        if (i == r->pl_idx) put(&cur, B->kblk, ko[BCFGPU_CALL_BCF_PL], ko[BCFGPU_CALL_BCF_PL + 1]);
+        else if (i < nk && kjob && kjob[i] >= 0) put(&cur, B->pblk, poff[kjob[i]], poff[kjob[i] + 1]);
+        else { put(&cur, W->hblk, hk ? kend[hk - 1] : 0, kend[hk]); ++hk; }
+    }
+    put(&cur, B->kblk, ko[BCFGPU_CALL_BCF_GQ], ko[BCFGPU_CALL_BCF_GQ + 1]);
+    if (vio_write_record_indiv(W->fout, W->hdr, ln_buf, W->iblk, cur.len)) DIE("%s\n", vio_error());
+    rewind(LN);
+}
+/* record k as mcall.c:1627-1681 leaves it; gv_min_dp: the MinDP of a reference record outside the -g ranges, or 0 */
+static void write_record(writer_t *W, int k, int gv_min_dp)
+{
+    const opt_t *o = W->o; const recs_t *R = W->R; const dev_t *D = W->D;
+    const rec_t *r = &R->rec[k]; const bcfgpu_call_site *c = &D->cs[k];
+    const int nn = c->nals_new, S = W->M->S, dev_rec = o->dev_rec;
+    fprintf(LN, "%s\t%s\t%s\t%s\t", r->fld[0], r->fld[1], r->fld[2], r->fld[3]);
+    print_alt(r, c);
+    if (c->qual_missing) fputs("\t.", LN); else fprintf(LN, "\t%g", (double)c->qual);
+    fprintf(LN, "\t%s\t", r->fld[6]);
+    print_info(r, c, gv_min_dp);
+    /* FORMAT: GT first, PL trimmed or dropped, the rest as it came */
+    fmt_t F; char *fmt = strdup(r->fld[8]); F.keys = split(fmt, ':', &F.nk);
+    F.called = nn > 1 && c->ret > 0;                           /* mcall_call_genotypes ran: GP and GQ exist (mcall.c:1618-1623) */
+    /* --device-records: GT, PL and GQ are blocks already; the sample text holds the other keys alone (host_keys of them) */
+    F.kjob = o->dev_keys && r->kjob && F.nk == r->nkeys ? r->kjob : NULL;     /* the keys whose blocks the device made */
+    F.host_keys = dev_rec ? F.nk - 1 + (F.called && D->gp) : 0;
+    for (int i = 0; F.kjob && i < F.nk; ++i) F.host_keys -= F.kjob[i] >= 0;
+    const int want_text = !dev_rec || F.host_keys > 0;
+    if (dev_rec) W->B->n_phost += F.host_keys;
+    char **smp_fld = r->fld + 9;                               /* the input's sample columns */
+    if (o->dev_in && want_text) {                            /* ... which become text here, for a record that is written */
+        int ns;
+        if (vio_indiv_text(W->hdr, R->ibuf + r->ioff, r->ilen, r->n_fmt, W->M->S_in, &W->smp_text, &W->smp_cap)) DIE("%s\n", vio_error());
+        smp_fld = split(W->smp_text + 1, '\t', &ns);
+        if (ns != W->M->S_in) DIE("malformed VCF\n");
+    }
+    fputs("\tGT", LN);
+    for (int i = 0; i < F.nk; ++i) if (i != r->pl_idx || !c->pl_dropped) fprintf(LN, ":%s", F.keys[i]);
+    if (F.called && D->gp) fputs(":GP", LN);
+    if (F.called && (D->gq || (dev_rec && D->d_gq))) fputs(":GQ", LN);
+    const long head_end = dev_rec ? end_head() : 0;            /* the head ends here; the other keys' sample text follows it in the stream */
+    for (int s = 0; s < S && want_text; ++s) print_sample_text(W, k, &F, smp_fld[W->M->col[s]], s);
+    if (dev_rec) splice_record(W, k, &F, head_end); else end_record(W->fout, W->hdr);
+    free(F.keys); free(fmt);
+    if (o->dev_in && want_text) free(smp_fld);
+}
+static void write_records(writer_t *W)
+{
+    const opt_t *o = W->o; const gvcf_t *G = W->G; const bcfgpu_call_site *cs = W->D->cs;
+    const int n_out = cals ? n_events : W->R->n;
     for (int ev = 0; ev < n_out; ++ev) {
-        if (cals && events[ev].is_missed) {                      /* -i: a target that met no record (tgt_flush_region, vcfcall.c:408-424) */
-            const tgt_t *t = &tgt[events[ev].tgt];
-            fprintf(LN, "%s\t%d\t.\t%s\t", t->chrom, t->pos, t->als[0]);
-            if (t->nals < 2) fputc('.', LN);
-            for (int i = 1; i < t->nals; ++i) fprintf(LN, "%s%s", i > 1 ? "," : "", t->als[i]);
-            fputs("\t.\t.\t.\tGT", LN);
-            for (int s2 = 0; s2 < S; ++s2) fputs("\t.", LN);
-            fputc(0, LN); fflush(LN);
-            if (vio_write_line(fout, hdr, ln_buf)) DIE("%s\n", vio_error());
-            rewind(LN);
-            continue;
-        }
+        if (cals && events[ev].is_missed) { write_missed_target(W, &tgt[events[ev].tgt]); continue; }
         const int k = cals ? events[ev].tgt : ev;
-        const rec_t *r = &recs[k];
-        const bcfgpu_call_site *c = &cs[k];
-        if (c->ret == -2 || (varonly && c->ret == 0) || c->ret < 0) continue;
-        const int nn = c->nals_new, ngn = nn * (nn + 1) / 2;
+        if (cs[k].ret == -2 || (o->varonly && cs[k].ret == 0) || cs[k].ret < 0) continue;
         int gv_min_dp = 0;
-        if (gv_n) {
-            const int w = gv_w[k], b = gv_blk[w];
-            if (b >= 0) {                                        /* inside a block: one line when the block ends (gvcf.c:134-166) */
-                const bcfgpu_gvcf_block *B = &gv_block[b];
-                if (B->last_site != w) continue;
-                int kf = k; while (gv_w[kf] != B->first_site) --kf;  /* the block's first record: alleles and genotypes are its */
-                const rec_t *rf = &recs[kf]; const bcfgpu_call_site *cf = &cs[kf];
-                fprintf(LN, "%s\t%d\t.\t%s\t", rf->fld[0], B->start_pos + 1, rf->fld[3]);
-                {
-                    const char *al[5] = { 0, 0, 0, 0, 0 };
-                    for (int i = 0; i < rf->nals; ++i) if (cf->als_map[i] >= 0) al[cf->als_map[i]] = rf->als[i];
-                    if (cf->nals_new < 2) fputc('.', LN);
-                    for (int i = 1; i < cf->nals_new; ++i) fprintf(LN, "%s%s", i > 1 ? "," : "", al[i]);
-                }
-                fputs("\t.\t.\t", LN);
-                if (B->start_pos + 1 < B->end1) fprintf(LN, "END=%d;", B->end1);
-                fprintf(LN, "MinDP=%d\tGT:DP", B->min_dp);
-                for (int s2 = 0; s2 < S; ++s2) {
-                    const int g0 = gt[((size_t)kf * 2 + 0) * S + s2], g1 = gt[((size_t)kf * 2 + 1) * S + s2];
-                    fputc('\t', LN);
-                    if (g0 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g0);
-                    if (g1 != BCFGPU_GT_VECTOR_END) { fputc('/', LN); if (g1 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g1); }
-                    const int32_t v = gv_dp[(size_t)b * S + s2];
-                    if (v == INT32_MIN) fputs(":.", LN); else fprintf(LN, ":%d", v);
-                }
-                fputc(0, LN); fflush(LN);
-                if (vio_write_line(fout, hdr, ln_buf)) DIE("%s\n", vio_error());
-                rewind(LN);
+        if (o->gv_n) {
+            const int w = G->w[k], b = G->blk[w];
+            if (b >= 0) {                                        /* inside a block: one line when the block ends */
+                if (G->block[b].last_site == w) write_block_line(W, k, b);
                 continue;
             }
-            if (c->ret == 1) gv_min_dp = gv_min[w];                /* a reference record outside the ranges keeps MinDP (gvcf.c:221-222) */
+            if (cs[k].ret == 1) gv_min_dp = G->min[w];             /* a reference record outside the ranges keeps MinDP (gvcf.c:221-222) */
         }
-        fprintf(LN, "%s\t%s\t%s\t%s\t", r->fld[0], r->fld[1], r->fld[2], r->fld[3]);
-        {   /* ALT: the kept alleles in their new order */
-            const char *al[5] = { 0, 0, 0, 0, 0 };
-            for (int i = 0; i < r->nals; ++i) if (c->als_map[i] >= 0) al[c->als_map[i]] = r->als[i];
-            if (nn < 2) fputc('.', LN);
-            for (int i = 1; i < nn; ++i) fprintf(LN, "%s%s", i > 1 ? "," : "", al[i]);
-        }
-        if (c->qual_missing) fputs("\t.", LN); else fprintf(LN, "\t%g", (double)c->qual);
-        fprintf(LN, "\t%s\t", r->fld[6]);
-        {   /* INFO: I16 and QS go, AC / AN / DP4 / MQ come */
-            char *info = strdup(r->fld[7]); int ni, first = 1; char **iv = split(info, ';', &ni);
-            for (int i = 0; i < ni; ++i) {
-                if (!strncmp(iv[i], "I16=", 4) || !strncmp(iv[i], "QS=", 3) || !strcmp(iv[i], ".")) continue;
-                const char *eq = strchr(iv[i], '=');
-                if (eq && nn != r->nals && is_numberR(infoR, n_infoR, iv[i], (size_t)(eq - iv[i]))) {
-                    fprintf(LN, "%s%.*s=", first ? "" : ";", (int)(eq - iv[i]), iv[i]);
-                    print_numberR(eq + 1, c->als_map, r->nals, nn);
-                } else fprintf(LN, "%s%s", first ? "" : ";", iv[i]);
-                first = 0;
-            }
-            free(iv); free(info);
-            if (nn > 1) { fprintf(LN, "%sAC=", first ? "" : ";"); first = 0; for (int i = 1; i < nn; ++i) fprintf(LN, "%s%d", i > 1 ? "," : "", c->ac[i]); }
-            fprintf(LN, "%sAN=%d", first ? "" : ";", c->an);
-            if (c->has_i16) {
-                fprintf(LN, ";DP4=%d,%d,%d,%d", c->dp4[0], c->dp4[1], c->dp4[2], c->dp4[3]);
-                if (c->mq == BCFGPU_INT32_MISSING) fputs(";MQ=.", LN); else fprintf(LN, ";MQ=%d", c->mq);
-            }
-            if (gv_min_dp == INT32_MIN) fputs(";MinDP=.", LN); else if (gv_min_dp) fprintf(LN, ";MinDP=%d", gv_min_dp);
-        }
-        /* FORMAT: GT first, PL trimmed or dropped, the rest as it came */
-        int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
-        const int called = nn > 1 && c->ret > 0;               /* mcall_call_genotypes ran: GP and GQ exist (mcall.c:1618-1623) */
-        /* --device-records: GT, PL and GQ are blocks already; the sample text holds the other keys alone (host_keys of them) */
-        const int *kjob = dev_keys && r->kjob && nk == r->nkeys ? r->kjob : NULL;     /* the keys whose blocks the device made */
-        int host_keys = dev_rec ? nk - 1 + (called && gp) : 0;
-        for (int i = 0; kjob && i < nk; ++i) host_keys -= kjob[i] >= 0;
-        const int want_text = !dev_rec || host_keys > 0;
-        if (dev_rec) n_phost += host_keys;
-        char **smp_fld = r->fld + 9;                               /* the input's sample columns */
-        if (dev_in && want_text) {                               /* ... which become text here, for a record that is written */
-            int ns;
-            if (vio_indiv_text(hdr, ibuf + r->ioff, r->ilen, r->n_fmt, S_in, &smp_text, &smp_cap)) DIE("%s\n", vio_error());
-            smp_fld = split(smp_text + 1, '\t', &ns);
-            if (ns != S_in) DIE("malformed VCF\n");
-        }
-        fputs("\tGT", LN);
-        for (int i = 0; i < nk; ++i) if (i != r->pl_idx || !c->pl_dropped) fprintf(LN, ":%s", keys[i]);
-        if (called && gp) fputs(":GP", LN);
-        if (called && (gq || (dev_rec && d_gq))) fputs(":GQ", LN);
-        long head_end = 0;
-        if (dev_rec) { fputc(0, LN); head_end = ftell(LN); }    /* the head ends here; the other keys' sample text follows it in the stream */
-        for (int s = 0; s < S && want_text; ++s) {
-            int nf = 0;                                          /* fields of this sample so far: ':' in front of all but the first */
-            if (!dev_rec || s) fputc('\t', LN);
-            if (!dev_rec) {
-                const int g0 = gt[((size_t)k * 2 + 0) * S + s], g1 = gt[((size_t)k * 2 + 1) * S + s];
-                if (g0 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g0);
-                if (g1 != BCFGPU_GT_VECTOR_END) { fputc('/', LN); if (g1 == BCFGPU_GT_MISSING) fputc('.', LN); else fprintf(LN, "%d", g1); }
-                ++nf;
-            }
-            char *smp = strdup(smp_fld[col[s]]); int nv; char **vals = split(smp, ':', &nv);
-            for (int i = 0; i < nk; ++i) {
-                if (kjob && kjob[i] >= 0) continue;
-                if (i == r->pl_idx) {
-                    if (c->pl_dropped || dev_rec) continue;
-                    if (nf++) fputc(':', LN);
-                    int printed = 0;
-                    for (int j = 0; j < ngn; ++j) {
-                        const int32_t v = opl[((size_t)k * ngmax + j) * S + s];
-                        if (v == BCFGPU_INT32_VECTOR_END) break;
-                        if (printed++) fputc(',', LN);
-                        if (v == BCFGPU_INT32_MISSING) fputc('.', LN); else fprintf(LN, "%d", v);
-                    }
-                    if (!printed) fputc('.', LN);
-                } else if (i < nv && nn != r->nals && is_numberR(fmtR, n_fmtR, keys[i], strlen(keys[i]))) {
-                    if (nf++) fputc(':', LN);
-                    print_numberR(vals[i], c->als_map, r->nals, nn);
-                } else fprintf(LN, "%s%s", nf++ ? ":" : "", i < nv ? vals[i] : ".");
-            }
-            if (called && gp) {
-                if (nf++) fputc(':', LN);
-                int printed = 0;
-                for (int j = 0; j < ngn; ++j) {
-                    uint32_t bits; memcpy(&bits, &gp[((size_t)k * ngmax + j) * S + s], 4);
-                    if (bits == 0x7F800002u) break;
-                    if (printed++) fputc(',', LN);
-                    if (bits == 0x7F800001u) fputc('.', LN); else fprintf(LN, "%g", (double)gp[((size_t)k * ngmax + j) * S + s]);
-                }
-                if (!printed) fputc('.', LN);
-            }
-            if (called && gq) {
-                const int32_t v = gq[(size_t)k * S + s];
-                if (v == BCFGPU_INT32_MISSING) fputs(":.", LN); else fprintf(LN, ":%d", v);
-            }
-            free(vals); free(smp);
-        }
-        if (dev_rec) {
-            /* the record's per-sample part: the device's blocks and the host's, in the FORMAT column's order */
-            fputc(0, LN); fflush(LN);
-            int nhost = 0; size_t kend[64];
-            if (host_keys > 0) {
-                char *hf = malloc(strlen(r->fld[8]) + 8), *o = hf;              /* the host's keys as a FORMAT column of their own */
-                for (int i = 0; i < nk; ++i) if (i != r->pl_idx && !(kjob && kjob[i] >= 0)) o += sprintf(o, "%s%s", o > hf ? ":" : "", keys[i]);
-                if (called && gp) o += sprintf(o, "%sGP", o > hf ? ":" : "");
-                if ((nhost = vio_encode_keys(hdr, hf, ln_buf + head_end, S, &hblk, &hblk_cap, kend)) != host_keys) DIE("%s\n", nhost < 0 ? vio_error() : "FORMAT keys lost on the way");
-                free(hf);
-            }
-            const uint64_t *ko = koff + (size_t)k * BCFGPU_CALL_BCF_NKEYS;
-            size_t need = (size_t)(ko[BCFGPU_CALL_BCF_NKEYS] - ko[0]) + (nhost ? kend[nhost - 1] : 0);
-            for (int i = 0; kjob && i < nk; ++i) if (kjob[i] >= 0) need += (size_t)(poff[kjob[i] + 1] - poff[kjob[i]]);
-            if (need > iblk_cap) { iblk_cap = need * 2 + 256; iblk = realloc(iblk, iblk_cap); if (!iblk) DIE("out of memory\n"); }
-            size_t il = 0; int hk = 0;
-            #define PUT_DEV(i) do { memcpy(iblk + il, kblk + ko[i], (size_t)(ko[(i) + 1] - ko[i])); il += (size_t)(ko[(i) + 1] - ko[i]); } while (0)
-            #define PUT_HOST() do { const size_t b0 = hk ? kend[hk - 1] : 0; memcpy(iblk + il, hblk + b0, kend[hk] - b0); il += kend[hk] - b0; ++hk; } while (0)
-            #define PUT_KEY(j) do { memcpy(iblk + il, pblk + poff[j], (size_t)(poff[(j) + 1] - poff[j])); il += (size_t)(poff[(j) + 1] - poff[j]); } while (0)
-            PUT_DEV(BCFGPU_CALL_BCF_GT);
-            for (int i = 0; i < nk; ++i) { if (i == r->pl_idx) PUT_DEV(BCFGPU_CALL_BCF_PL); else if (kjob && kjob[i] >= 0) PUT_KEY(kjob[i]); else PUT_HOST(); }
-            if (called && gp) PUT_HOST();
-            PUT_DEV(BCFGPU_CALL_BCF_GQ);
-            #undef PUT_DEV
-            #undef PUT_HOST
-            #undef PUT_KEY
-            if (vio_write_record_indiv(fout, hdr, ln_buf, iblk, il)) DIE("%s\n", vio_error());
-            rewind(LN);
-            free(keys); free(fmt);
-            if (dev_in && want_text) free(smp_fld);
-            continue;
-        }
-        free(keys); free(fmt);
-        if (dev_in) free(smp_fld);
-        fputc(0, LN); fflush(LN);                              /* the record, NUL-terminated, then the stream starts over */
-        if (vio_write_line(fout, hdr, ln_buf)) DIE("%s\n", vio_error());
-        rewind(LN);
+        write_record(W, k, gv_min_dp);
     }
+}
+
+int main(int argc, char **argv)
+{
+    opt_t o; ploidy_t P; smap_t M; recs_t R; hplanes_t H; dev_t D; blocks_t B; gvcf_t G; vio_hdr *hdr;
+    if (parse_options(argc, argv, &o)) return 2;
+    load_ploidy(&o, &P);
+    vio_file *fin = open_input(&o, &hdr);
+    const double t0 = now_s();
+    for (int i = 0; i < vio_hdr_nlines(hdr); ++i) header_line(vio_hdr_line(hdr, i));
+    map_samples(&o, &P, hdr, &M);
+    read_records(&o, &P, &M, fin, hdr, &R);
+    const double t_read = now_s() - t0;
+    flush_last_targets(&R);
+    if (M.S <= 0) DIE("no samples\n");
+    read_groups(&o, &M);
+    R.namax = 1;
+    for (int k = 0; k < R.n; ++k) if (R.rec[k].nals > R.namax) R.namax = R.rec[k].nals;
+    const double t1 = now_s();
+    build_planes(&o, &M, &R, &H);
+    const double t_planes = now_s() - t1, t2 = now_s();
+    call_on_device(&o, &M, &R, &H, &D);
+    double t_dev = now_s() - t2, t_enc = 0.;
+    const double t3 = now_s();
+    output_header(&o, &M, hdr);
+    memset(&B, 0, sizeof B); memset(&G, 0, sizeof G);
+    if (o.dev_rec) {
+        const double te = now_s();
+        encode_call_blocks(&o, &R, &D, hdr, &B);
+        if (o.dev_keys) encode_key_blocks(&o, &M, &R, &D, hdr, &B);
+        free(B.emit);
+        t_enc = now_s() - te;                                    /* a device stage: counted there, not under writing */
+    }
+    vio_file *fout = vio_open_write(o.out_path, o.out_mode);
+    if (!fout || vio_write_hdr(fout, hdr)) DIE("%s\n", vio_error());
+    open_record_stream();
+    if (o.gv_n) gvcf_blocks(&o, &M, &R, &D, &G);
+    writer_t W; memset(&W, 0, sizeof W);
+    W.o = &o; W.M = &M; W.R = &R; W.D = &D; W.B = &B; W.G = &G; W.fout = fout; W.hdr = hdr;
+    write_records(&W);
     if (vio_close(fout)) DIE("%s\n", vio_error());
-    t_write = now_s() - t3 - t_enc; t_dev += t_enc;
-    if (want_timing) fprintf(stderr, "[bcfgpu_call] seconds: reading records %.3f, building the planes on the host %.3f, uploads and device stages %.3f, writing records %.3f\n", t_read, t_planes, t_dev, t_write);
-    if (want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", dev_in ? n : 0);
-    if (want_timing) fprintf(stderr, "[bcfgpu_call] device records: %d records' FORMAT blocks encoded on the device\n", n_enc);
-    if (want_timing && keys_given) fprintf(stderr, "[bcfgpu_call] device keys: %ld pass-through key blocks made on the device, %ld on the host\n", n_pjob, n_phost);
-    bcfgpu_destroy(ctx);
+    const double t_write = now_s() - t3 - t_enc; t_dev += t_enc;
+    if (o.want_timing) fprintf(stderr, "[bcfgpu_call] seconds: reading records %.3f, building the planes on the host %.3f, uploads and device stages %.3f, writing records %.3f\n", t_read, t_planes, t_dev, t_write);
+    if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", o.dev_in ? R.n : 0);
+    if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device records: %d records' FORMAT blocks encoded on the device\n", B.n_enc);
+    if (o.want_timing && o.keys_given) fprintf(stderr, "[bcfgpu_call] device keys: %ld pass-through key blocks made on the device, %ld on the host\n", B.n_pjob, B.n_phost);
+    bcfgpu_destroy(D.ctx);
     return 0;
 }

@@ -18,6 +18,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "bcfgpu.h"
+#include "drv.h"
 
 #define READ_LEN 100
 
@@ -29,16 +30,6 @@ static uint32_t rnd32(void)
     return (uint32_t)((rng_state * 2685821657736338717ULL) >> 32);
 }
 static uint32_t rnd_below(uint32_t n) { return (uint32_t)(((uint64_t)rnd32() * n) >> 32); }
-
-#define CHECK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "%s: %s (%d)\n", #call, bcfgpu_last_error(), rc_); exit(1); } } while (0)
-
-static void *dev_alloc(bcfgpu_ctx *ctx, size_t bytes)
-{
-    void *p = NULL;
-    CHECK(bcfgpu_malloc(ctx, bytes ? bytes : 16, &p));
-    CHECK(bcfgpu_memset(ctx, p, 0, bytes ? bytes : 16));
-    return p;
-}
 
 int main(int argc, char **argv)
 {

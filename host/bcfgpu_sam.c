@@ -63,18 +63,9 @@
 extern long syscall(long number, ...);       /* (unistd.h keeps it back under -std=c99 -D_POSIX_C_SOURCE) */
 #include "bcfgpu.h"
 #include "vcfio.h"
+#include "drv.h"
 
-#define CHECK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "%s: %s (%d)\n", #call, bcfgpu_last_error(), rc_); exit(1); } } while (0)
-#define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(1); } while (0)
-
-static FILE *LN; static char *ln_buf; static size_t ln_len;      /* the record being written: a memory stream, framed by vcfio */
 static vio_file *fout; static vio_hdr *hdr;
-static void end_record(void)
-{
-    fputc(0, LN); fflush(LN);
-    if (vio_write_line(fout, hdr, ln_buf)) { fprintf(stderr, "%s\n", vio_error()); exit(1); }
-    rewind(LN);
-}
 
 typedef struct {
     int n, cap;                                   /* reads */
@@ -838,7 +829,7 @@ static void print_record(const char *contig, int pos1, const char *alleles, cons
     if (fmt_flag & BCFGPU_FMT_SCR) fputs(":SCR", LN);
     if (fmt_flag & BCFGPU_FMT_QS) fputs(":QS", LN);
     if (indiv) {
-        fputc(0, LN); fflush(LN);
+        end_head();
         if (dt_on ? vio_write_record_text(fout, hdr, ln_buf, indiv, l_indiv) : vio_write_record_indiv(fout, hdr, ln_buf, indiv, l_indiv)) { fprintf(stderr, "%s\n", vio_error()); exit(1); }
         rewind(LN);
         if (dt_on) ++n_dev_text; else ++n_dev_records;
@@ -870,7 +861,7 @@ static void print_record(const char *contig, int pos1, const char *alleles, cons
     if (fmt_flag & BCFGPU_FMT_SCR) { int32_t *a = COL(1); for (int s = 0; s < S; ++s) a[s] = pp->scr[k * Ss + s]; }
     if (fmt_flag & BCFGPU_FMT_QS) { int32_t *a = COL(na); for (int s = 0; s < S; ++s) for (int j = 0; j < na; ++j) a[(size_t)s * na + j] = pp->qs[(k * 5 + j) * Ss + s]; }
     #undef COL
-    fputc(0, LN); fflush(LN);
+    end_head();
     if (vio_write_record_int(fout, hdr, ln_buf, nk, width, (const int32_t *const *)col)) { fprintf(stderr, "%s\n", vio_error()); exit(1); }
     rewind(LN);
 }
@@ -924,27 +915,18 @@ static void run_mpileup(bcfgpu_ctx *ctx, const bcfgpu_tile *tile, int n, bcfgpu_
 
 /* The per-sample blocks of a tile's records from the planes in HBM: the size pass tells how many bytes, the second call writes them.
  * emit: HOST [n], which sites have a record.  rec / off: HOST, malloc'ed: the blocks back to back, and where each starts. */
-static int encode_blocks(bcfgpu_ctx *ctx, int n, const bcfgpu_mplp_out *mo, const uint8_t *d_emit, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *nb)
+typedef struct { bcfgpu_ctx *ctx; int n; const bcfgpu_mplp_out *mo; const uint8_t *d_emit; } enc_arg;
+static int encode_blocks(void *arg, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *nb)
 {
-    return dt_on ? bcfgpu_mplp_encode_vcf(ctx, n, mo, d_emit, d_buf, cap, d_off, nb)             /* VCF text for -O v|z */
-                 : bcfgpu_mplp_encode_bcf(ctx, n, mo, dr_key, d_emit, d_buf, cap, d_off, nb);    /* BCF2 for -O u|b */
+    const enc_arg *a = arg;
+    return dt_on ? bcfgpu_mplp_encode_vcf(a->ctx, a->n, a->mo, a->d_emit, d_buf, cap, d_off, nb)             /* VCF text for -O v|z */
+                 : bcfgpu_mplp_encode_bcf(a->ctx, a->n, a->mo, dr_key, a->d_emit, d_buf, cap, d_off, nb);    /* BCF2 for -O u|b */
 }
 static void encode_records(bcfgpu_ctx *ctx, int n, const bcfgpu_mplp_out *mo, const uint8_t *emit, uint8_t **rec, uint64_t **off)
 {
-    void *d_emit, *d_off, *d_buf = NULL; uint64_t nb = 0;
-    CHECK(bcfgpu_malloc(ctx, (size_t)n + 1, &d_emit)); CHECK(bcfgpu_malloc(ctx, ((size_t)n + 1) * 8, &d_off));
-    CHECK(bcfgpu_memcpy_h2d(ctx, d_emit, emit, (size_t)n));
-    const int rc = encode_blocks(ctx, n, mo, d_emit, NULL, 0, d_off, &nb);
-    if (rc && rc != BCFGPU_E_RANGE) { fprintf(stderr, "%s: %s (%d)\n", dt_on ? "bcfgpu_mplp_encode_vcf" : "bcfgpu_mplp_encode_bcf", bcfgpu_last_error(), rc); exit(1); }
-    if (nb) {
-        CHECK(bcfgpu_malloc(ctx, nb, &d_buf));
-        CHECK(encode_blocks(ctx, n, mo, d_emit, d_buf, nb, d_off, &nb));
-    }
-    *rec = malloc(nb ? nb : 1); *off = malloc(((size_t)n + 1) * 8);
-    if (nb) CHECK(bcfgpu_memcpy_d2h(ctx, *rec, d_buf, nb));
-    CHECK(bcfgpu_memcpy_d2h(ctx, *off, d_off, ((size_t)n + 1) * 8));
-    CHECK(bcfgpu_sync(ctx));
-    bcfgpu_free(ctx, d_emit); bcfgpu_free(ctx, d_off); if (d_buf) bcfgpu_free(ctx, d_buf);
+    enc_arg a = { ctx, n, mo, dev_upload(ctx, emit, (size_t)n) };
+    encode_two_pass(ctx, encode_blocks, &a, dt_on ? "bcfgpu_mplp_encode_vcf" : "bcfgpu_mplp_encode_bcf", (size_t)n + 1, rec, off);
+    bcfgpu_free(ctx, (void *)a.d_emit);
 }
 
 /* ---- options (file scope: the tile loop and its helpers read them) ---- */
@@ -985,7 +967,7 @@ static void block_line(const char *contig, int start_pos, int end1, int min_dp, 
     if (start_pos + 1 < end1) fprintf(LN, "END=%d;", end1);                   /* gvcf.c:150-151 */
     fprintf(LN, "MinDP=%d;QS=%g,%g\tPL:DP", min_dp, (double)qs0, (double)qs1);
     for (int s = 0; s < S; ++s) fprintf(LN, "\t%d,%d,%d:%d", pl[s], pl[(size_t)S + s], pl[2 * (size_t)S + s], dp[s]);
-    end_record();
+    end_record(fout, hdr);
 }
 static void pending_flush(void)
 {
@@ -1016,9 +998,7 @@ static unsigned long long tot_entries, tot_pairs;
 /* --timing: where the wall time of a run goes (seconds): reading and parsing the files, building a tile's pool, the device
  * stages of a tile (every call up to the records' planes on the host), writing the records; with --prefetch the wait inside
  * bcfgpu_pool_adopt (what of the next tile's copy the current tile's stages did not cover) */
-#include <time.h>
 static int want_timing; static double t_read, t_pool, t_dev, t_emit, t_adopt;
-static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 /* ---- a tile's records, written beside the device stages of the next tile: process_tile() hands everything the record loop reads over
  * as a job (host copies only: sites, planes, the indel columns' results, the gVCF blocks) and goes on; one worker thread takes the
  * jobs in order.  The pending gVCF block (PB) and the output are the worker's while it runs: whoever else needs them waits for it
@@ -1820,8 +1800,7 @@ int main(int argc, char **argv)
     if (!list_only) {
         fout = vio_open_write(out_path, out_mode);
         if (!fout || vio_write_hdr(fout, hdr)) DIE("%s\n", vio_error());
-        LN = open_memstream(&ln_buf, &ln_len);
-        if (!LN) DIE("open_memstream failed\n");
+        open_record_stream();
         /* --device-records: BCF output only (text is formatted from the planes on the host) */
         dr_on = device_records && (out_mode == 'u' || out_mode == 'b');
         /* --device-text: text output only (BCF has --device-records) */

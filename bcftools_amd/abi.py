@@ -186,6 +186,21 @@ class BcfKey(C.Structure):
 BCF_KEY = [("off", "<u8"), ("site", "<i4"), ("key_id", "<i4"), ("type", "<i4"), ("width", "<i4"), ("nals", "<i4"), ("flags", "<i4")]
 
 
+# bcfgpu_call_encode_vcf: the kinds of a field (BCFGPU_VCF_FIELD_*), the fields a site may have, the bound on one sample's text
+VCF_FIELD_GT, VCF_FIELD_PL, VCF_FIELD_GQ, VCF_FIELD_KEY = 0, 1, 2, 3
+VCF_MAX_FIELDS = 16
+VCF_SAMPLE_CAP = 15360
+
+
+class VcfField(C.Structure):
+    """bcfgpu_vcf_field: one field of one record's sample column, for bcfgpu_call_encode_vcf (32 bytes, the layout of BcfKey)."""
+    _fields_ = [("off", C.c_uint64), ("site", C.c_int32), ("kind", C.c_int32), ("type", C.c_int32), ("width", C.c_int32),
+                ("nals", C.c_int32), ("flags", C.c_int32)]
+
+
+VCF_FIELD = [("off", "<u8"), ("site", "<i4"), ("kind", "<i4"), ("type", "<i4"), ("width", "<i4"), ("nals", "<i4"), ("flags", "<i4")]
+
+
 class Timing(C.Structure):
     _fields_ = [("glfgen_ms", C.c_float), ("combine_ms", C.c_float),
                 ("mcall_ms", C.c_float), ("total_ms", C.c_float)]
@@ -262,6 +277,8 @@ PROTOTYPES = {
                                          C.c_int32, C.c_void_p]),
     "bcfgpu_call_remap_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BcfKey), C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bcfgpu_call_encode_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.c_int32, C.POINTER(VcfField), C.c_int32, C.c_void_p,
+                                         C.c_uint64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_comm_init_all": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
     "bcfgpu_comm_destroy": (None, [C.c_void_p]),
     "bcfgpu_gather_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

@@ -1,7 +1,8 @@
 // bcfcodec.h -- what the device codecs of the records' per-sample bytes have in common (bcfenc.hip, vcfenc.hip, bcfcallenc.hip,
-// bcfkeys.hip, bcfdec.hip): the line-wise copy between global memory and the LDS stage, the BCF2 block header and typed-value
-// rules (bcf_enc_vint / bcf_dec_int of htslib vcf.c; here host/vcfio.c enc_int1 / enc_size / enc_vint / dec_int), the
-// workgroup maximum of the size kernels, and the FORMAT keys of an mpileup record.  Device and host-inline code only.
+// bcfkeys.hip, bcfdec.hip, vcfcallenc.hip): the line-wise copy between global memory and the LDS stage, the BCF2 block header and
+// typed-value rules (bcf_enc_vint / bcf_dec_int of htslib vcf.c; here host/vcfio.c enc_int1 / enc_size / enc_vint / dec_int), the
+// workgroup maximum of the size kernels, decimal text, the reading of a pass-through key from the input's bytes, and the FORMAT
+// keys of an mpileup record.  Device and host-inline code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -118,6 +119,79 @@ __device__ __forceinline__ void wg_max(int32_t (&m)[N], int32_t (&red)[COD_THREA
         for (int i = 0; i < N; ++i)
             for (int w = 1; w < COD_THREADS / 64; ++w) m[i] = red[w][i] > m[i] ? red[w][i] : m[i];
     }
+}
+
+// ---- decimal text (vcfenc.hip, vcfcallenc.hip) ----
+// decimal digits of v, by comparisons
+__device__ __forceinline__ int n_digits(uint32_t v)
+{
+    return 1 + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u)
+             + (v >= 100000000u) + (v >= 1000000000u);
+}
+// v in decimal at p (LDS), written from its known end backwards; returns the byte after it
+__device__ __forceinline__ unsigned char *put_value(unsigned char *p, uint32_t v)
+{
+    const int nd = n_digits(v);
+    for (int i = nd - 1; i > 0; --i) { const uint32_t q = v / 10u; p[i] = (unsigned char)('0' + (v - q * 10u)); v = q; }
+    p[0] = (unsigned char)('0' + v);
+    return p + nd;
+}
+// the signed form: a '-' in front of a negative value's digits
+__device__ __forceinline__ int signed_len(int32_t v) { return v < 0 ? 1 + n_digits(0u - (uint32_t)v) : n_digits((uint32_t)v); }
+__device__ __forceinline__ unsigned char *put_signed(unsigned char *p, int32_t v)
+{
+    if (v < 0) { *p++ = '-'; return put_value(p, 0u - (uint32_t)v); }
+    return put_value(p, (uint32_t)v);
+}
+
+// ---- a pass-through key of a call record, read from the input record's bytes (bcfkeys.hip as BCF2, vcfcallenc.hip as text) ----
+// what is the same for every sample of a job
+struct KeyJob {
+    const unsigned char *run;           // value [input sample 0][0]
+    int es, width;                      // bytes a value and values a sample in the input (width 0: no values, every sample is '.')
+    bool aligned;                       // the run's values lie at their natural alignment
+    int nals, nn;                       // alleles of the input record, of the output record
+    bool remap;                         // Number=R and alleles dropped: a sample with nals values follows the alleles
+    int inv[BCFGPU_MAX_ALLELES];        // output value t is input value inv[t], -1: `missing`
+};
+
+// J: a bcfgpu_bcf_key or a bcfgpu_vcf_field of kind KEY (off, type, width, nals, flags)
+template <class Job>
+__device__ __forceinline__ KeyJob kenc_job(const unsigned char *indiv, const Job &J, const bcfgpu_call_site &c)
+{
+    KeyJob K;
+    K.run = indiv + J.off;
+    K.es = J.type == 3 ? 4 : J.type == 0 ? 1 : J.type;
+    K.width = J.type ? J.width : 0;
+    K.aligned = ((uintptr_t)K.run & (uintptr_t)(K.es - 1)) == 0;
+    K.nals = J.nals;
+    K.nn = c.nals_new < 1 ? 1 : c.nals_new > BCFGPU_MAX_ALLELES ? BCFGPU_MAX_ALLELES : c.nals_new;
+    K.remap = (J.flags & 1) && K.nn != K.nals;
+    #pragma unroll
+    for (int t = 0; t < BCFGPU_MAX_ALLELES; ++t) {
+        K.inv[t] = -1;
+        #pragma unroll
+        for (int i = 0; i < BCFGPU_MAX_ALLELES; ++i) if (i < K.nals && c.als_map[i] == t) K.inv[t] = i;   // (the last one stays, as out[map[i]] = v[i] in turn leaves it)
+    }
+    if (K.nn == 1) K.inv[0] = 0;
+    return K;
+}
+
+// the values of the sample at p before its first `end of vector`
+__device__ __forceinline__ int kenc_len(const KeyJob &K, const unsigned char *p)
+{
+    int len = 0;
+    for (; len < K.width; ++len) if (get_int(p + len * K.es, K.es, K.aligned) == BCFGPU_INT32_VECTOR_END) break;
+    return len;
+}
+
+// the input value that goes to place j of a remapped vector, -1: `missing`
+__device__ __forceinline__ int kenc_src(const KeyJob &K, int j)
+{
+    int src = -1;
+    #pragma unroll
+    for (int t = 0; t < BCFGPU_MAX_ALLELES; ++t) if (t == j) src = K.inv[t];
+    return src;
 }
 
 // ---- the FORMAT keys of an mpileup record (bcfenc.hip as BCF2, vcfenc.hip as text) ----

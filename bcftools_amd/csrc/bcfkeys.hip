@@ -35,44 +35,6 @@ constexpr int KENC_NRED = 3;                                    // width, max, -
 
 static_assert(BCFGPU_BCF_KEY_MAX_WIDTH * 4 <= COD_SLICE, "a sample of the widest key fits a slice: a slice is at least 15 samples");
 
-// what is the same for every sample of a job
-struct KeyJob {
-    const unsigned char *run;           // value [input sample 0][0]
-    int es, width;                      // bytes a value and values a sample in the input (width 0: no values, every sample is '.')
-    bool aligned;                       // the run's values lie at their natural alignment
-    int nals, nn;                       // alleles of the input record, of the output record
-    bool remap;                         // Number=R and alleles dropped: a sample with nals values follows the alleles
-    int inv[BCFGPU_MAX_ALLELES];        // output value t is input value inv[t], -1: `missing`
-};
-
-__device__ __forceinline__ KeyJob kenc_job(const unsigned char *indiv, const bcfgpu_bcf_key &J, const bcfgpu_call_site &c)
-{
-    KeyJob K;
-    K.run = indiv + J.off;
-    K.es = J.type == 3 ? 4 : J.type == 0 ? 1 : J.type;
-    K.width = J.type ? J.width : 0;
-    K.aligned = ((uintptr_t)K.run & (uintptr_t)(K.es - 1)) == 0;
-    K.nals = J.nals;
-    K.nn = c.nals_new < 1 ? 1 : c.nals_new > BCFGPU_MAX_ALLELES ? BCFGPU_MAX_ALLELES : c.nals_new;
-    K.remap = (J.flags & 1) && K.nn != K.nals;
-    #pragma unroll
-    for (int t = 0; t < BCFGPU_MAX_ALLELES; ++t) {
-        K.inv[t] = -1;
-        #pragma unroll
-        for (int i = 0; i < BCFGPU_MAX_ALLELES; ++i) if (i < K.nals && c.als_map[i] == t) K.inv[t] = i;   // (the last one stays, as out[map[i]] = v[i] in turn leaves it)
-    }
-    if (K.nn == 1) K.inv[0] = 0;
-    return K;
-}
-
-// the values of the sample at p before its first `end of vector`
-__device__ __forceinline__ int kenc_len(const KeyJob &K, const unsigned char *p)
-{
-    int len = 0;
-    for (; len < K.width; ++len) if (get_int(p + len * K.es, K.es, K.aligned) == BCFGPU_INT32_VECTOR_END) break;
-    return len;
-}
-
 // one called sample (its input values at p; not read when the key has none): the output vector's length, its values into m[1], m[2]
 __device__ __forceinline__ void kenc_measure(const KeyJob &K, const unsigned char *p, int32_t *m)
 {
@@ -148,12 +110,7 @@ __device__ __forceinline__ void kenc_put_sample(const KeyJob &K, const unsigned 
     for (int j = 0; j < w; ++j) {
         int32_t x = BCFGPU_INT32_VECTOR_END;
         if (j < olen) {
-            int src = j;                                                    // the input value that goes here, -1: `missing`
-            if (remap) {
-                src = -1;
-                #pragma unroll
-                for (int t = 0; t < BCFGPU_MAX_ALLELES; ++t) if (t == j) src = K.inv[t];
-            }
+            const int src = remap ? kenc_src(K, j) : j;                     // the input value that goes here, -1: `missing`
             x = src < 0 || len == 0 ? BCFGPU_INT32_MISSING : get_int(p + src * K.es, K.es, K.aligned);
         }
         put_int<BYTEWISE>(q + j * es, narrow(x, es), es);

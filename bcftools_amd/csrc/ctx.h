@@ -81,7 +81,7 @@ enum WsSlot : int {
     // bcfgpu_gvcf_blocks, bcfgpu_compact_calls[_async]: scratch for one call
     WS_GVCF_SCAN = 32, WS_GVCF_SCAN_TMP = 33,
     WS_COMPACT_SIZE = 35, WS_COMPACT_SCAN_TMP = 36, WS_COMPACT_COUNTS = 37,
-    // the device codecs of the records' per-sample bytes (bcfcodec.h): scratch for one call.  The four encoders' size passes
+    // the device codecs of the records' per-sample bytes (bcfcodec.h): scratch for one call.  The encoders' size passes
     // (enc_offsets) share the scan's temporary storage: each entry synchronises the context's stream before it returns
     WS_COMPACT_ENC_SCAN_TMP = 167,
     // bcfgpu_mplp_encode_bcf (bcfenc.hip): the keys' integer types per site
@@ -93,13 +93,15 @@ enum WsSlot : int {
     // bcfgpu_call_remap_bcf (bcfkeys.hip): the uploaded copies of the key jobs and of the sample map, one packed word a job (the
     // block's integer type and width)
     WS_COMPACT_BCFKEY_JOBS = 172, WS_COMPACT_BCFKEY_COL = 173, WS_COMPACT_BCFKEY_WORD = 174,
+    // bcfgpu_call_encode_vcf (vcfcallenc.hip): the uploaded copies of the fields, of each site's first field and of the sample map
+    WS_COMPACT_CALLVCF_FIELDS = 175, WS_COMPACT_CALLVCF_FIRST = 176, WS_COMPACT_CALLVCF_COL = 177,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_COMPACT_BCFKEY_WORD + 1      // one past the highest slot
+    WS_COUNT = WS_COMPACT_CALLVCF_COL + 1      // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names

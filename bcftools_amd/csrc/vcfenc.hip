@@ -34,13 +34,6 @@ static_assert(VCF_SAMPLE_MAX == 293, "the worst-case sample of eleven keys");
 static_assert(VCF_SAMPLE_MAX <= VCF_STAGE, "one sample always fits the stage: every round takes at least one");
 static_assert(VCF_STAGE % COD_LINE == 0, "the stage is whole lines");
 
-// decimal digits of v, by comparisons
-__device__ __forceinline__ int n_digits(uint32_t v)
-{
-    return 1 + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u)
-             + (v >= 100000000u) + (v >= 1000000000u);
-}
-
 // bytes of sample s's text at site k: the tab, a ':' between keys, per key a ',' between values and the values' digits.
 // keys: bit kind = the key is written (PL, bit 0, always is)
 __device__ __forceinline__ int sample_len(const MplpPlanes &P, uint32_t keys, int na, size_t k, int s, size_t S)
@@ -54,15 +47,6 @@ __device__ __forceinline__ int sample_len(const MplpPlanes &P, uint32_t keys, in
         for (int j = 0; j < w; ++j) len += n_digits((uint32_t)key_value(P, kind, k, j, s, S));
     }
     return len;
-}
-
-// v in decimal at p (LDS), written from its known end backwards; returns the byte after it
-__device__ __forceinline__ unsigned char *put_value(unsigned char *p, uint32_t v)
-{
-    const int nd = n_digits(v);
-    for (int i = nd - 1; i > 0; --i) { const uint32_t q = v / 10u; p[i] = (unsigned char)('0' + (v - q * 10u)); v = q; }
-    p[0] = (unsigned char)('0' + v);
-    return p + nd;
 }
 
 // size[k] = bytes of site k's block (0: no record), size[n_sites] = 0

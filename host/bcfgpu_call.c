@@ -2,7 +2,7 @@
  *  include/bcfgpu.h: the record loop of main_vcfcall (vcfcall.c:1089-1148) with mcall() on the device.
  *
  *      bcfgpu_call [-v] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]]
- *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-records] [--device-keys] [--timing] [-O v|z|u|b] <in.vcf>
+ *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] <in.vcf>
  *          -S: the samples to keep, in that order: NAME [PLOIDY|SEX] per line, or a PED file (vcfcall.c:202-344)
  *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c)
  *          -G: sample groups with their own allele frequencies, '-' = every sample alone, or NAME GROUP lines
@@ -28,9 +28,19 @@
  *              them.  The host splices them in their keys' places; Float and String keys and GP stay on the host
  *              (vio_encode_keys), and a record without any of those forms no sample text at all.  In any other run the option does
  *              nothing.  The same output either way.
+ *          --device-text: with -O v|z and --device-input in effect, the sample columns of the written records are not formed on the
+ *              host either: the input records' bytes stay in HBM after the decode and bcfgpu_call_encode_vcf formats every such
+ *              record's columns there -- GT, the input's keys in their order with the trimmed PL in PL's place (nothing when PL is
+ *              dropped), the -S sample choice, the Number=R values following als_map, GQ -- one size call and one write call over
+ *              all of them.  The host prints the head up to the FORMAT column and hands both to vio_write_record_text.  A record
+ *              stays on the host (the route without options) when an input key other than PL is not stored as integers of at most
+ *              255 values, a key is named GT, the record carries GP, or it has more than 16 fields or passes the bound of
+ *              include/bcfgpu.h; when no written record does, the GT, PL and GQ planes are not downloaded.  In any other run the
+ *              option does nothing.  The same output either way.
  *          --timing: lines on stderr: the seconds (reading records, building the planes on the host, uploads and device stages,
  *              writing records), how many records' planes were decoded on the device, and how many records' FORMAT blocks were
- *              encoded there; with --device-keys given, also how many pass-through key blocks were made on the device and on the host
+ *              encoded there; with --device-keys given, also how many pass-through key blocks were made on the device and on the host;
+ *              with --device-text given, also how many records' sample columns were formatted on the device and on the host
  *
  *  Host: VCF text in, what mcall() reads from a record (alleles, FORMAT/PL, INFO/QS, INFO/I16) packed into the planes of
  *  bcfgpu_call_in, one bcfgpu_mcall over all records, then what mcall.c:1627-1681 does to the record: alleles trimmed with
@@ -388,7 +398,7 @@ static int unwanted_site(const char *line, int acgt_only, int skip_kind)
 
 /* ---- the state of a run, stage by stage ---- */
 typedef struct {                                                /* the command line */
-    int varonly, out_tags, keepalt, dev_in, dev_rec, dev_keys, keys_given, want_timing;
+    int varonly, out_tags, keepalt, dev_in, dev_rec, dev_keys, keys_given, dev_text, text_given, want_timing;
     int acgt_only, skip_kind;                                   /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
     const char *tgt_file, *smpl_file, *smpl_list, *ploidy_file, *ploidy_alias, *grp_arg, *grp_tag, *out_path, *in_path;
     double prior; char out_mode, prior_an_tag[64], prior_ac_tag[64];
@@ -407,7 +417,7 @@ typedef struct { int32_t *nals, *unseen, *pl, *ad, *pan, *pac; float *qs, *i16; 
 typedef struct {                                                /* the planes in HBM, and what came down of the results */
     bcfgpu_ctx *ctx;
     int32_t *d_nals, *d_unseen, *d_plin, *d_ad, *d_grp, *d_pan, *d_pac; float *d_qs, *d_i16;
-    void *d_indiv;                                              /* --device-keys: kept until the pass-through keys' blocks are made */
+    void *d_indiv;                                              /* --device-keys, --device-text: kept until the pass-through keys are made */
     void *d_site, *d_gt, *d_pl, *d_ploidy, *d_gq, *d_gp;
     bcfgpu_call_site *cs; int8_t *gt; int32_t *opl, *gq; float *gp;
 } dev_t;
@@ -415,6 +425,7 @@ typedef struct {                                                /* --device-reco
     uint8_t *emit; void *d_emit;                                /* which records are written */
     unsigned char *kblk; uint64_t *koff; int n_enc;
     unsigned char *pblk; uint64_t *poff; long n_pjob, n_phost;  /* --device-keys: the pass-through keys' blocks, one offset a job */
+    unsigned char *tblk; uint64_t *toff; long n_tdev, n_thost;  /* --device-text: the sample columns as text, one offset a record (equal: the host's) */
 } blocks_t;
 typedef struct { int32_t *w, *blk, *min, *dp; bcfgpu_gvcf_block *block; } gvcf_t;   /* -g: record k is written record w[k], or -1 */
 static void gvcf_option(opt_t *o, const char *arg, const char *echo) { if ((o->gv_n = parse_gvcf_limits(arg, o->gv_range)) < 0) DIE("Could not parse: --gvcf %s\n", echo); }
@@ -448,6 +459,7 @@ static int parse_options(int argc, char **argv, opt_t *o)
         else if (!strcmp(argv[1], "--device-input")) { o->dev_in = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-records")) { o->dev_rec = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-keys")) { o->dev_keys = o->keys_given = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-text")) { o->dev_text = o->text_given = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--timing")) { o->want_timing = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "-C") && argc > 3) { if (strcmp(argv[2], "alleles")) DIE("-C: only `alleles` is supported\n"); cals = 1; argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-T") && argc > 3) { o->tgt_file = argv[2]; argv += 2; argc -= 2; }
@@ -494,7 +506,7 @@ static int parse_options(int argc, char **argv, opt_t *o)
     }
     if (o->gv_n && o->varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (o->gv_n && cals) DIE("-g with -C alleles is not supported\n");
-    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-records] [--device-keys] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
     o->in_path = argv[1]; return 0;
 }
 static void load_ploidy(opt_t *o, ploidy_t *P)
@@ -548,6 +560,7 @@ static vio_file *open_input(opt_t *o, vio_hdr **hdr)
     o->dev_in = o->dev_in && vio_is_bcf(fin) && !cals && !o->gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
     o->dev_rec = o->dev_rec && (o->out_mode == 'u' || o->out_mode == 'b') && !o->gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
     o->dev_keys = o->dev_keys && o->dev_in && o->dev_rec;      /* the input's bytes in HBM and key blocks to splice: both ends on the device */
+    o->dev_text = o->dev_text && o->dev_in && (o->out_mode == 'v' || o->out_mode == 'z');     /* the input's bytes in HBM, text records to write */
     return fin;
 }
 /* the samples of the header, or those of -S / -s in that order (vcfcall.c:202-344) */
@@ -804,7 +817,7 @@ static void build_planes(const opt_t *o, const smap_t *M, recs_t *R, hplanes_t *
  * vcfcall.c:807-825 re-initialises it when it changes) -- the planes are [record][...]: a run is a slice */
 static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, const hplanes_t *H, dev_t *D)
 {
-    const rec_t *recs = R->rec; const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_rec = o->dev_rec;
+    const rec_t *recs = R->rec; const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_rec = o->dev_rec || o->dev_text;
     memset(D, 0, sizeof *D);
     bcfgpu_cfg cfg; memset(&cfg, 0, sizeof cfg);
     cfg.device = 0; cfg.n_smpl = S; cfg.max_sites = n; cfg.max_reads = 64;
@@ -822,7 +835,7 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
             CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); D->d_ad = dp;
             CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_ad, cmap, namax, D->d_ad));
         }
-        if (!o->dev_keys) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
+        if (!o->dev_keys && !o->dev_text) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
     } else {
         D->d_plin = dev_upload(ctx, H->pl, (size_t)n * ngmax * S * 4);
         if (H->ad) D->d_ad = dev_upload(ctx, H->ad, (size_t)n * namax * S * 4);
@@ -854,12 +867,13 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
         i = j;
     }
     D->cs = malloc((size_t)n * sizeof *D->cs);
-    /* --device-records: the site records alone come down here (and GP); GT, PL and GQ follow as bytes once the writer's header is known */
+    /* --device-records: the site records alone come down here (and GP); GT, PL and GQ follow as bytes once the writer's header is known.
+     * --device-text: the site records alone; the planes follow only when a written record is left to the host (download_planes) */
     D->gt = dev_rec ? NULL : malloc((size_t)n * 2 * S); D->opl = dev_rec ? NULL : malloc((size_t)n * ngmax * S * 4);
     CHECK(bcfgpu_memcpy_d2h(ctx, D->cs, D->d_site, (size_t)n * sizeof *D->cs));
     if (D->gt) CHECK(bcfgpu_memcpy_d2h(ctx, D->gt, D->d_gt, (size_t)n * 2 * S));
     if (D->opl) CHECK(bcfgpu_memcpy_d2h(ctx, D->opl, D->d_pl, (size_t)n * ngmax * S * 4));
-    D->gq = D->d_gq && !dev_rec ? malloc((size_t)n * S * 4) : NULL; D->gp = D->d_gp ? malloc((size_t)n * ngmax * S * 4) : NULL;
+    D->gq = D->d_gq && !dev_rec ? malloc((size_t)n * S * 4) : NULL; D->gp = D->d_gp && !o->dev_text ? malloc((size_t)n * ngmax * S * 4) : NULL;
     if (D->gq) CHECK(bcfgpu_memcpy_d2h(ctx, D->gq, D->d_gq, (size_t)n * S * 4));
     if (D->gp) CHECK(bcfgpu_memcpy_d2h(ctx, D->gp, D->d_gp, (size_t)n * ngmax * S * 4));
     CHECK(bcfgpu_sync(ctx));
@@ -944,6 +958,83 @@ static void encode_key_blocks(const opt_t *o, const smap_t *M, recs_t *R, dev_t 
     } else B->poff = calloc(1, 8);
     free(job);
     CHECK(bcfgpu_free(D->ctx, D->d_indiv)); D->d_indiv = NULL;
+}
+
+/* ---- --device-text: the sample columns of the records that are written, as VCF text made in HBM from the call planes and the
+ * input's bytes where --device-input left them.  A field list per record in the order of its FORMAT column; a record the device
+ * cannot format (see the head of this file) has no field and d_emit = 0: the host's route writes it, from planes that come down only
+ * then ---- */
+typedef struct { bcfgpu_ctx *ctx; int n, ngmax; bcfgpu_call_out planes; int32_t n_field; const bcfgpu_vcf_field *field; int S_in; const void *d_indiv; size_t l_indiv;
+                 const int32_t *cmap; const void *d_emit; } text_arg;
+static int text_call(void *arg, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *need)
+{
+    const text_arg *a = arg;
+    return bcfgpu_call_encode_vcf(a->ctx, a->n, a->ngmax, &a->planes, a->n_field, a->field, a->S_in, a->d_indiv, a->l_indiv, a->cmap, a->d_emit, d_buf, cap, d_off, need);
+}
+/* values x (longest text of a value + 1): a pass-through key's share of the bound on one sample's text (include/bcfgpu.h) */
+static size_t key_text_bound(const bcfgpu_vcf_field *f)
+{
+    size_t values = f->type && f->width > 1 ? (size_t)f->width : 1;
+    if ((f->flags & 1) && values < BCFGPU_MAX_ALLELES) values = BCFGPU_MAX_ALLELES;
+    return values * (f->type == 3 ? 12u : f->type == 2 ? 7u : 5u);
+}
+static void download_planes(const smap_t *M, const recs_t *R, dev_t *D)
+{
+    const size_t n = (size_t)R->n, S = (size_t)M->S, ngmax = (size_t)R->ngmax;
+    D->gt = malloc(n * 2 * S + 1); D->opl = malloc(n * ngmax * S * 4 + 1);
+    CHECK(bcfgpu_memcpy_d2h(D->ctx, D->gt, D->d_gt, n * 2 * S)); CHECK(bcfgpu_memcpy_d2h(D->ctx, D->opl, D->d_pl, n * ngmax * S * 4));
+    if (D->d_gq) { D->gq = malloc(n * S * 4 + 1); CHECK(bcfgpu_memcpy_d2h(D->ctx, D->gq, D->d_gq, n * S * 4)); }
+    if (D->d_gp) { D->gp = malloc(n * ngmax * S * 4 + 1); CHECK(bcfgpu_memcpy_d2h(D->ctx, D->gp, D->d_gp, n * ngmax * S * 4)); }
+    CHECK(bcfgpu_sync(D->ctx));
+}
+static void encode_text_columns(const opt_t *o, const smap_t *M, const recs_t *R, dev_t *D, blocks_t *B)
+{
+    const int n = R->n;
+    uint8_t *emit = malloc((size_t)n + 1);
+    size_t cap_f = 0, n_f = 0; bcfgpu_vcf_field *fld = NULL; long n_host = 0;
+    for (int k = 0; k < n; ++k) {
+        const rec_t *r = &R->rec[k]; const bcfgpu_call_site *c = &D->cs[k];
+        emit[k] = 0;
+        if (c->ret < 0 || (o->varonly && c->ret == 0)) continue;                /* the record loop's rule: not written */
+        const int called = c->nals_new > 1 && c->ret > 0;
+        const int n_here = 1 + r->nkeys - (c->pl_dropped ? 1 : 0) + (called && D->d_gq ? 1 : 0);
+        int ok = r->nkeys == r->n_fmt && !(called && D->d_gp) && n_here <= BCFGPU_VCF_MAX_FIELDS;
+        for (int i = 0; ok && i < r->nkeys; ++i) {
+            const vio_indiv_key *q = &r->keys[i];
+            if (!strcmp(q->id, "GT")) ok = 0;
+            else if (i != r->pl_idx && (q->type < 0 || q->type > 3 || q->width < 0 || q->width > BCFGPU_BCF_KEY_MAX_WIDTH)) ok = 0;
+        }
+        if (ok) {
+            if (n_f + BCFGPU_VCF_MAX_FIELDS > cap_f) { cap_f = cap_f ? 2 * cap_f : 4096; fld = realloc(fld, cap_f * sizeof *fld); if (!fld) DIE("out of memory\n"); }
+            const size_t f0 = n_f; size_t bound = 1 + 4;
+            bcfgpu_vcf_field *f = &fld[n_f++];
+            memset(f, 0, sizeof *f); f->site = k; f->kind = BCFGPU_VCF_FIELD_GT;
+            for (int i = 0; i < r->nkeys; ++i) {
+                const vio_indiv_key *q = &r->keys[i];
+                if (i == r->pl_idx && c->pl_dropped) continue;
+                f = &fld[n_f++];
+                memset(f, 0, sizeof *f); f->site = k;
+                if (i == r->pl_idx) { f->kind = BCFGPU_VCF_FIELD_PL; bound += (size_t)R->ngmax * 12; continue; }
+                f->kind = BCFGPU_VCF_FIELD_KEY; f->off = r->ioff + q->off; f->type = q->type; f->width = q->width; f->nals = r->nals;
+                f->flags = is_numberR(fmtR, n_fmtR, q->id, strlen(q->id));
+                bound += key_text_bound(f);
+            }
+            if (called && D->d_gq) { f = &fld[n_f++]; memset(f, 0, sizeof *f); f->site = k; f->kind = BCFGPU_VCF_FIELD_GQ; bound += 12; }
+            if (bound > BCFGPU_VCF_SAMPLE_CAP) { ok = 0; n_f = f0; }
+        }
+        emit[k] = (uint8_t)ok;
+        if (ok) ++B->n_tdev; else ++n_host;
+    }
+    if (n_f > INT32_MAX - 1) DIE("too many fields for one call\n");
+    text_arg a; memset(&a, 0, sizeof a);
+    a.ctx = D->ctx; a.n = n; a.ngmax = R->ngmax; a.n_field = (int32_t)n_f; a.field = fld; a.S_in = M->S_in; a.d_indiv = D->d_indiv; a.l_indiv = R->ibuf_l;
+    a.cmap = o->smpl_file ? (const int32_t *)M->col : NULL;
+    void *d_emit = dev_upload(D->ctx, emit, (size_t)n); a.d_emit = d_emit;
+    a.planes.site = D->d_site; a.planes.gt = D->d_gt; a.planes.pl = D->d_pl; a.planes.gq = D->d_gq;
+    encode_two_pass(D->ctx, text_call, &a, "bcfgpu_call_encode_vcf", (size_t)n + 1, &B->tblk, &B->toff);
+    CHECK(bcfgpu_free(D->ctx, d_emit)); CHECK(bcfgpu_free(D->ctx, D->d_indiv)); D->d_indiv = NULL;
+    free(fld); free(emit);
+    if (n_host) download_planes(M, R, D);                       /* (GP with them: a record that carries it is the host's) */
 }
 
 /* ---- -g: gVCF blocks over the records that are written (vcfcall.c:1145-1149; gvcf_write, gvcf.c:88-226).  What
@@ -1170,8 +1261,10 @@ static void write_record(writer_t *W, int k, int gv_min_dp)
     F.kjob = o->dev_keys && r->kjob && F.nk == r->nkeys ? r->kjob : NULL;     /* the keys whose blocks the device made */
     F.host_keys = dev_rec ? F.nk - 1 + (F.called && D->gp) : 0;
     for (int i = 0; F.kjob && i < F.nk; ++i) F.host_keys -= F.kjob[i] >= 0;
-    const int want_text = !dev_rec || F.host_keys > 0;
+    const int text_ready = o->dev_text && W->B->toff[k + 1] > W->B->toff[k];     /* --device-text: the sample columns came from the device */
+    const int want_text = !text_ready && (!dev_rec || F.host_keys > 0);
     if (dev_rec) W->B->n_phost += F.host_keys;
+    if (o->text_given && !text_ready) ++W->B->n_thost;
     char **smp_fld = r->fld + 9;                               /* the input's sample columns */
     if (o->dev_in && want_text) {                            /* ... which become text here, for a record that is written */
         int ns;
@@ -1181,11 +1274,14 @@ static void write_record(writer_t *W, int k, int gv_min_dp)
     }
     fputs("\tGT", LN);
     for (int i = 0; i < F.nk; ++i) if (i != r->pl_idx || !c->pl_dropped) fprintf(LN, ":%s", F.keys[i]);
-    if (F.called && D->gp) fputs(":GP", LN);
-    if (F.called && (D->gq || (dev_rec && D->d_gq))) fputs(":GQ", LN);
-    const long head_end = dev_rec ? end_head() : 0;            /* the head ends here; the other keys' sample text follows it in the stream */
+    if (F.called && D->d_gp) fputs(":GP", LN);
+    if (F.called && D->d_gq) fputs(":GQ", LN);
+    const long head_end = dev_rec || text_ready ? end_head() : 0;      /* the head ends here; the other keys' sample text follows it in the stream */
     for (int s = 0; s < S && want_text; ++s) print_sample_text(W, k, &F, smp_fld[W->M->col[s]], s);
-    if (dev_rec) splice_record(W, k, &F, head_end); else end_record(W->fout, W->hdr);
+    if (text_ready) {                                         /* head and ready columns to the writer */
+        if (vio_write_record_text(W->fout, W->hdr, ln_buf, W->B->tblk + W->B->toff[k], (size_t)(W->B->toff[k + 1] - W->B->toff[k]))) DIE("%s\n", vio_error());
+        rewind(LN);
+    } else if (dev_rec) splice_record(W, k, &F, head_end); else end_record(W->fout, W->hdr);
     free(F.keys); free(fmt);
     if (o->dev_in && want_text) free(smp_fld);
 }
@@ -1241,6 +1337,11 @@ int main(int argc, char **argv)
         free(B.emit);
         t_enc = now_s() - te;                                    /* a device stage: counted there, not under writing */
     }
+    if (o.dev_text) {
+        const double te = now_s();
+        encode_text_columns(&o, &M, &R, &D, &B);
+        t_enc = now_s() - te;
+    }
     vio_file *fout = vio_open_write(o.out_path, o.out_mode);
     if (!fout || vio_write_hdr(fout, hdr)) DIE("%s\n", vio_error());
     open_record_stream();
@@ -1254,6 +1355,7 @@ int main(int argc, char **argv)
     if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", o.dev_in ? R.n : 0);
     if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device records: %d records' FORMAT blocks encoded on the device\n", B.n_enc);
     if (o.want_timing && o.keys_given) fprintf(stderr, "[bcfgpu_call] device keys: %ld pass-through key blocks made on the device, %ld on the host\n", B.n_pjob, B.n_phost);
+    if (o.want_timing && o.text_given) fprintf(stderr, "[bcfgpu_call] device text: %ld records' sample columns formatted on the device, %ld on the host\n", B.n_tdev, B.n_thost);
     bcfgpu_destroy(D.ctx);
     return 0;
 }

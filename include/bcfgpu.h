@@ -34,6 +34,8 @@
  *                                           per-sample block behind them: FORMAT/PL and AD / QS of BCF records as the planes of bcfgpu_call_in
  *    bcfgpu_call_remap_bcf               <- mcall_trim_and_update_numberR (mcall.c:1196-1265), bcf_subset's sample choice and the writer's
  *                                           typed-value encoder, for the integer FORMAT keys a call record passes through (AD, DP, SP, ...)
+ *    bcfgpu_call_encode_vcf              <- the same three and the text vcf_format writes for them: the sample columns of a call record, the
+ *                                           caller's GT / PL / GQ and the pass-through keys interleaved in FORMAT order
  *
  *  Memory model: all bulk arrays are *device* pointers (HBM).  Hosts that do
  *  not link HIP use bcfgpu_malloc/free/memcpy_*.  Kernels are enqueued on the
@@ -804,6 +806,61 @@ int  bcfgpu_call_remap_bcf(bcfgpu_ctx *ctx, int32_t n_keys, const bcfgpu_bcf_key
                            const void *d_indiv, uint64_t n_indiv_bytes, const int32_t *col,
                            const bcfgpu_call_site *d_site, int32_t n_sites, const uint8_t *d_emit,
                            void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
+
+/* The call records' sample columns as VCF text (vcfcallenc.hip): for every emitted site exactly the bytes the text route appends after the
+ * FORMAT column (host/bcfgpu_call.c print_sample_text and print_gt over the planes that came down, host/vcfio.c vio_indiv_text and
+ * print_numberR over the input's bytes; vcf_format of htslib vcf.c behind mcall.c:1158-1265, :1583, :1618-1623).  Per called sample, in
+ * sample order: a tab, then the site's fields joined by ':'.  No newline: the writer adds it (host/vcfio.c vio_write_record_text).  A
+ * field is one of the caller's planes or a run of the input's bytes; the caller of this entry lists them per site in the order of the
+ * record's FORMAT column, so that the pass-through keys lie between GT, PL and GQ where the text route has them.  With
+ * nn = site[k].nals_new (1 .. 5) and ngn = min(nn(nn+1)/2, n_gt_max), a field's text:
+ *     GT    the first entry as a digit, '.' for BCFGPU_GT_MISSING; when the second entry is not BCFGPU_GT_VECTOR_END a '/' and the second
+ *           entry by the same rule (print_gt).  Allele indices are 0 .. 9; any other entry is '.' too
+ *     PL    planes 0 .. ngn-1 up to the first BCFGPU_INT32_VECTOR_END, joined by ',', BCFGPU_INT32_MISSING as '.', negative values with
+ *           their sign; '.' when nothing was printed.  Whether PL is listed (site[k].pl_dropped) is the caller's decision
+ *     GQ    one value, '.' for MISSING.  The caller lists it only where nn > 1 && site[k].ret > 0
+ *     KEY   the vector and remap of bcfgpu_call_remap_bcf above, word for word: the sample's `width` values widened, cut at the first
+ *           `end of vector`, an empty one being '.'; when flags & 1 and nn != nals and the vector has nals values: [v[0]] when nn == 1,
+ *           else nn values '.' with out[map[i]] = v[i] for every i < nals with map[i] >= 0; every other vector as it is.  Joined by ',',
+ *           MISSING as '.', negative values with '-'.  No type or width is chosen: it is text.  Called sample s reads input sample
+ *           col ? col[s] : s
+ *   planes    DEVICE pointers: site is required when n_fields > 0; gt, pl, gq are required when a field of that kind is listed; gp is
+ *             not read
+ *   fields    HOST [n_fields], ordered by site (non-decreasing), a site's fields contiguous and in the order of its sample column; at
+ *             most BCFGPU_VCF_MAX_FIELDS a site.  A site without a field has zero length
+ *   d_indiv, n_indiv_bytes, n_smpl_in, col   as for bcfgpu_call_remap_bcf
+ *   d_emit    DEVICE [n_sites], 0 = the site has no record: zero length; NULL = every site has one
+ *   d_buf     DEVICE, cap_bytes: the sites' texts back to back in site order, each starting at whatever byte the one before ended
+ *   d_off     DEVICE [n_sites + 1], 8-byte aligned, 64-bit: d_off[k] = the start of site k's text, d_off[n_sites] = the size of all.  Set
+ *             whether or not the texts fit
+ *   n_bytes   HOST, out: the size of all
+ * The bound on one sample's text, which a caller applies before it lists a site:
+ *     1 + sum over the site's fields of values x (longest text of a value + 1) <= BCFGPU_VCF_SAMPLE_CAP
+ * with GT counting as 4 bytes in all, PL as n_gt_max values of 11 bytes, GQ as one value of 11 bytes, and a KEY as max(width, 1) values --
+ * at least BCFGPU_MAX_ALLELES with flags & 1 -- of 4 bytes for int8 and for type 0, 6 for int16, 11 for int32.  No sample's text is
+ * longer than its site's bound, and a sample that fits is what lets every round of the write kernel take at least one.
+ * When the texts do not fit cap_bytes nothing is written to d_buf, *n_bytes is the size needed and the call returns BCFGPU_E_RANGE
+ * (cap_bytes = 0 asks for the size).  BCFGPU_E_ARG, checked on the host before anything runs: every case bcfgpu_call_remap_bcf rejects
+ * (NULL pointers, a KEY's type outside 0-3 or width outside 0 .. BCFGPU_BCF_KEY_MAX_WIDTH, a site outside [0, n_sites), nals outside
+ * 1 .. 5 with flags & 1, a col entry outside [0, n_smpl_in), more called samples than input samples without a map), a kind outside the
+ * enum, sites that decrease, more than BCFGPU_VCF_MAX_FIELDS fields at a site, GT, PL or GQ listed with its plane NULL, n_gt_max outside
+ * 1 .. 15, a site whose bound passes BCFGPU_VCF_SAMPLE_CAP; BCFGPU_E_RANGE when a KEY's off + n_smpl_in * width * size passes
+ * n_indiv_bytes; nothing is written in either case.  n_sites == 0 and n_fields == 0 are valid.  Runs on the context's stream and
+ * synchronises it. */
+enum { BCFGPU_VCF_FIELD_GT, BCFGPU_VCF_FIELD_PL, BCFGPU_VCF_FIELD_GQ, BCFGPU_VCF_FIELD_KEY };
+#define BCFGPU_VCF_MAX_FIELDS 16          /* fields of one site */
+#define BCFGPU_VCF_SAMPLE_CAP 15360       /* bound on one sample's text, = the LDS stage */
+typedef struct {            /* one field of one record's sample column; 32 bytes, the layout of bcfgpu_bcf_key */
+    uint64_t off;           /* KEY: byte offset in the indiv buffer of value [input sample 0][0] */
+    int32_t  site;          /* index into planes->site / d_emit */
+    int32_t  kind;          /* BCFGPU_VCF_FIELD_* */
+    int32_t  type, width;   /* KEY: as bcfgpu_bcf_key (type 0-3, width 0 .. BCFGPU_BCF_KEY_MAX_WIDTH) */
+    int32_t  nals, flags;   /* KEY: as bcfgpu_bcf_key (bit 0: Number=R) */
+} bcfgpu_vcf_field;
+int  bcfgpu_call_encode_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_gt_max, const bcfgpu_call_out *planes,
+                            int32_t n_fields, const bcfgpu_vcf_field *fields,
+                            int32_t n_smpl_in, const void *d_indiv, uint64_t n_indiv_bytes, const int32_t *col,
+                            const uint8_t *d_emit, void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
 
 /* One communicator over the contexts of a node, rank i = ctxs[i] (RCCL ncclCommInitAll; every context on its own device;
  * librccl is loaded at this call, a single context needs none). */

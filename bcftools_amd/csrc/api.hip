@@ -31,6 +31,7 @@ struct bcfgpu_ctx {
     hipStream_t own_stream = nullptr, stream = nullptr;
     // constant tables in HBM
     double *d_fk = nullptr, *d_beta = nullptr, *d_lhet = nullptr, *d_pl2p = nullptr, *d_mw = nullptr;
+    double *d_pfx = nullptr;        // glfgen's prefix table (kernels.h GLF_PFX_*), built on the device from d_fk and d_beta
     float *d_q2p = nullptr;         // 10^(-q/10) as float (htslib g_qual2prob), for the realignment kernel
     double call_theta_log = 0;
     // workspaces sized by cfg.max_sites / cfg.max_reads
@@ -124,6 +125,7 @@ int bcfgpu_create(const bcfgpu_cfg *cfg, bcfgpu_ctx **out)
     int rc = 0;
     if ((rc = dev_alloc(c, (void**)&c->d_fk, fk.size() * 8)) || (rc = dev_alloc(c, (void**)&c->d_beta, beta.size() * 8 + 64)) ||
         (rc = dev_alloc(c, (void**)&c->d_lhet, lhet.size() * 8)) || (rc = dev_alloc(c, (void**)&c->d_pl2p, sizeof pl2p)) ||
+        (rc = dev_alloc(c, (void**)&c->d_pfx, GLF_PFX_DOUBLES * 8)) ||
         (rc = dev_alloc(c, (void**)&c->d_mw, sizeof mw)) || (rc = dev_alloc(c, (void**)&c->d_q2p, 256 * sizeof(float))) || (rc = dev_alloc(c, (void**)&c->d_err, 8 * sizeof(int)))) {
         bcfgpu_destroy(c); return rc;
     }
@@ -135,6 +137,11 @@ int bcfgpu_create(const bcfgpu_cfg *cfg, bcfgpu_ctx **out)
     hipMemcpy(c->d_mw, mw, sizeof mw, hipMemcpyHostToDevice);
     { float q2p[256]; for (int i = 0; i < 256; ++i) q2p[i] = (float)std::pow(10., -i / 10.); hipMemcpy(c->d_q2p, q2p, sizeof q2p, hipMemcpyHostToDevice); }
     hipMemset(c->d_err, 0, 8 * sizeof(int));
+    // the errmod walk's sums after a cell's highest quality, from the tables just uploaded: on the stream of those copies, and
+    // waited for with them below (the error word is that of the uploads above as well: none of them is checked on its own)
+    launch_glfgen_prefix(c->d_fk, c->d_beta, c->d_pfx, nullptr);
+    e = hipGetLastError();
+    if (e != hipSuccess) { bcfgpu_destroy(c); return set_err(BCFGPU_E_HIP, "table upload or prefix table launch", e); }
 
     // the prior: theta <- log(theta * sum_{i<n} 1/i), n = ploidy_max * nsamples (mcall.c:396-416, vcfcall.c:654-655)
     c->call_theta_log = 0;
@@ -470,7 +477,7 @@ static int enqueue_mpileup(bcfgpu_ctx *c, const bcfgpu_tile *tile, const bcfgpu_
     }
     g.n_reads = (uint32_t)tile->n_reads;
     g.ref16 = tile->ref16; g.off = tile->plp_off; g.rd = tile->rd; g.epos = tile->epos; g.aux = tile->aux;
-    g.fk = c->d_fk; g.beta = c->d_beta; g.lhet = c->d_lhet;
+    g.fk = c->d_fk; g.beta = c->d_beta; g.lhet = c->d_lhet; g.pfx = c->d_pfx;
     g.crp = c->d_crp;
     // the callret planes are addressed with ncells of *this* tile
     g.hist = c->d_hist; g.err = c->d_err; g.site_sums = c->d_site_sums;

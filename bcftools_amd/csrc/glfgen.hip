@@ -175,7 +175,7 @@ __device__ __forceinline__ uint32_t count_runs(uint32_t *s_slot, uint64_t qm, in
 // and wait for the older one only).
 // `brow`: byte offset of beta[0][0][n] (stored q, k, n: tables.cpp; the q = 0 row is all zeros).
 template <class Src>
-__device__ __forceinline__ double walk_runs(uint32_t *s_slot, uint64_t qm, const double *s_fk, const char *bbase, int tid,
+__device__ __forceinline__ double walk_runs(uint32_t *s_slot, uint64_t qm, const double *s_fk, const char *bbase, const double *pfx, int tid,
                                             uint32_t brow, Src src, int nsrc, uint32_t &rev_out, uint32_t &qs_out)
 {
     double bs = 0;
@@ -218,8 +218,23 @@ __device__ __forceinline__ double walk_runs(uint32_t *s_slot, uint64_t qm, const
     bool first = true;
     while (__any(qm != 0)) {                                              // a round: the next NRANK qualities of every lane
         qs += first ? count_runs<true>(s_slot, qm, tid, src, nsrc) : count_runs<false>(s_slot, qm, tid, src, nsrc);
-        first = false; r = 0;
+        r = 0;
         d_nx = slot_of(0);
+        // The first round starts from a sum of +0 with no read walked, so what the walk reaches after the lane's highest
+        // quality depends on that quality, n and its two strand counts alone: pfx[q][n][reverse][forward] holds it, formed in
+        // the walk's own order and arithmetic (glfgen_prefix_kernel), and the lane goes on from rank 1.  Selects only, no
+        // branch: the load is issued for every lane and in every round (entry 0 for a lane outside the table, without a read
+        // or in a later round), ahead of the first two steps' loads, and its value joins the sum behind them -- it is one more
+        // load in flight, counted like the walk's own, and not waited for on its own.
+        const uint32_t d0 = d_nx, r1 = d0 & 0xffu, f1 = (d0 >> 8) & 0xffu;
+        const bool tb = first && brow < (uint32_t)GLF_PFX_N << 3 && (d0 & 0xe0e0u) == 0u && (d0 & 0xffffu) != 0u;
+        const uint32_t ti = tb ? (d0 & 0x3f0000u) | brow << 7 | r1 << 5 | f1 : 0u;     // q << 16 | n << 10 | r << 5 | f
+        const double t0 = pfx[ti];
+        wpack = tb ? r1 | f1 << 16 : wpack;
+        koff = tb ? brow + ((r1 + f1) << 11) : koff;
+        r = tb ? 1u : 0u;
+        d_nx = slot_of(r);
+        first = false;
         // Two steps in flight, each in its own registers: a trip adds the older one and puts the step after next in its place, so
         // no step's operands are copied and the wait before an addition is for that step's loads alone.  (Once a step finds
         // no lane with a read, every later one adds +0: the two left over at the end are added in any order.)
@@ -229,6 +244,7 @@ __device__ __forceinline__ double walk_runs(uint32_t *s_slot, uint64_t qm, const
         WALK_LOAD(bx, fx, off, wi);
         bool ay = step(off, wi);
         WALK_LOAD(by, fy, off, wi);
+        bs = tb ? t0 : bs;
         while (ax) {
             WALK_ADD(bx, fx);
             ax = step(off, wi);
@@ -566,7 +582,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
             const uint32_t v[NPART] = { A.t_bq - A.d_bq, A.t_bq2 - A.d_bq2, A.d_bq, A.d_bq2, A.t_mq - A.d_mq, A.t_mq2 - A.d_mq2, A.d_mq, A.d_mq2,
                                         A.t_md - A.d_md, A.t_md2 - A.d_md2, A.d_md, A.d_md2, C.ori, C.mq0, C.m59, C.ref59, C.rev59 };
             if (LDS_HIST) {
-                uint32_t *pt = s_part + (sg - site0) * (NPART * pcol) + (tid & (pcol - 1));
+                int col = tid & (pcol - 1);                      // (formed here, every segment: not a value kept alive through the rounds)
+                asm volatile("" : "+v"(col));
+                uint32_t *pt = s_part + (sg - site0) * (NPART * pcol) + col;
                 #pragma unroll
                 for (int j = 0; j < NPART; ++j) atomicAdd(&pt[j * pcol], v[j]);
             } else {
@@ -590,7 +608,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         if (LDS_HIST) {
             // the columns of every partial sum: four lanes per value
             const int nslot = min(P.hist_slots, P.n_sites - site0), q4 = pcol >> 2;
-            for (int i = tid; i < nslot * NPART * 4; i += WG) {
+            int i0 = tid;                                        // (formed here, every round, like the clearing loop's above)
+            asm volatile("" : "+v"(i0));
+            for (int i = i0; i < nslot * NPART * 4; i += WG) {
                 const uint32_t *pt = s_part + (i >> 2) * pcol + (i & 3) * q4;
                 unsigned long long x = 0;
                 for (int k = 0; k < q4; ++k) x += pt[k];
@@ -713,7 +733,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         {
             const uint16_t *kpp = kp + n_other;               // primary-base keys and zeros (rejected reads)
             const PrimSrc psrc{kpp};
-            const double bs = walk_runs(s_cnt, qmask, s_fk, bbase, tid, brow, psrc, dead_cell ? 0 : cnt_raw - (int)n_other, prim_rev, qs_prim);
+            const double bs = walk_runs(s_cnt, qmask, s_fk, bbase, P.pfx, tid, brow, psrc, dead_cell ? 0 : cnt_raw - (int)n_other, prim_rev, qs_prim);
             #pragma unroll
             for (int b = 0; b < 5; ++b) if (b == primary) bsum[b] = bs;
         }
@@ -752,7 +772,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                 uint64_t qm = 0;
                 for (int i = 0; i < no; ++i) { const int key = src(i); if (key >= 0) qm |= 1ull << (key >> 1); }
                 uint32_t r_, q_;
-                bs = walk_runs(s_cnt, qm, s_fk, bbase, tid, brow, src, no, r_, q_);
+                bs = walk_runs(s_cnt, qm, s_fk, bbase, P.pfx, tid, brow, src, no, r_, q_);
                 }
                 if (cb > 0) {
                     #pragma unroll
@@ -866,6 +886,30 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
             if (v) atomicAdd(&P.site_sums[(size_t)site0 * SITE_NSUM + i], v);
         }
     }
+}
+
+// The prefix table of walk_runs() (kernels.h), stored [q][n][r][f]: one lane per (q, n, r); the lanes of a wavefront differ in
+// n (the thread index is decoded with n fastest), so that its loads of beta[q][k][n] are one row.  The
+// lane forms the sum of its r reverse-strand reads, then stores it as f = 0 and after every forward-strand read it adds -- the
+// walk's order, a multiply and an add per read (-ffp-contract=off), so an entry has the bits the walk reaches read by read.
+// beta is read at k = r + f - 1 <= 2 * GLF_PFX_S - 3; entries with r + f > n are never looked up.
+static_assert(2 * GLF_PFX_S - 3 < 256 && GLF_PFX_N <= 256 && GLF_PFX_S <= 256, "the prefix table stays inside fk[256] and beta[64][256][256]");
+__global__ __launch_bounds__(WG) void glfgen_prefix_kernel(const double *fk, const double *beta, double *pfx)
+{
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= 64u * GLF_PFX_S * GLF_PFX_N) return;
+    const uint32_t n = i % GLF_PFX_N, r = i / GLF_PFX_N % GLF_PFX_S, q = i / (GLF_PFX_N * GLF_PFX_S);
+    const double *b = beta + ((size_t)q << 16 | n);                 // beta[q][k][n] = b[k << 8]
+    double *t = pfx + (((size_t)q * GLF_PFX_N + n) * GLF_PFX_S + r) * GLF_PFX_S;
+    double bs = 0;
+    for (uint32_t u = 0; u < r; ++u) bs += fk[u] * b[u << 8];
+    t[0] = bs;
+    for (uint32_t u = 0; u + 1 < (uint32_t)GLF_PFX_S; ++u) { bs += fk[u] * b[(r + u) << 8]; t[u + 1] = bs; }
+}
+
+void launch_glfgen_prefix(const double *fk, const double *beta, double *pfx, hipStream_t s)
+{
+    hipLaunchKernelGGL(glfgen_prefix_kernel, dim3(64 * GLF_PFX_S * GLF_PFX_N / WG), dim3(WG), 0, s, fk, beta, pfx);
 }
 
 size_t glfgen_lds_bytes(int cap, int hist_slots)

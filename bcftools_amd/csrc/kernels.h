@@ -18,6 +18,11 @@ enum : int { SITE_NSUM = 14 };
 // the most keys of one staging round of glfgen_kernel's tile launch (csrc/api.hip sizes the LDS window under it; the packed
 // 16-bit histogram counters of csrc/glfgen.hip rely on it)
 enum : int { GLF_MAX_WINDOW = 16384 };
+// the prefix table of glfgen_kernel's errmod walk (csrc/glfgen.hip, walk_runs): the double sum a cell of n reads has after the
+// r reverse- and f forward-strand reads of its highest quality q, as [q][n][r][f] with q < 64 (the key's six bits),
+// n < GLF_PFX_N, r and f < GLF_PFX_S -- 32 MiB, the size of beta.  Built once per context from its fk and beta.
+enum : int { GLF_PFX_N = 64, GLF_PFX_S = 32 };
+enum : size_t { GLF_PFX_DOUBLES = (size_t)64 * GLF_PFX_N * GLF_PFX_S * GLF_PFX_S };
 
 // per (site,sample) result of the glfgen kernel = bcf_callret1_t (bam2bcf.h:90-108), SoA planes over
 // ncells = n_sites*n_smpl.  Everything but p is an exact integer.
@@ -67,6 +72,7 @@ struct GlfgenParams {
     const uint8_t  *epos;
     const uint32_t *aux;
     const double *fk, *beta, *lhet;
+    const double *pfx;              // [64][GLF_PFX_N][GLF_PFX_S][GLF_PFX_S] the walk's sums after a cell's highest quality (launch_glfgen_prefix)
     const CallretPlanes *crp;       // the output planes' addresses, in device memory: read where the stores are (glfgen.hip)
     int *hist;                      // [n_sites][H_SIZE], zeroed before launch
     unsigned long long *site_sums;  // [n_sites][SITE_NSUM] site totals of anno[4..15], ori_depth, mq0 (exact integers), zeroed before launch
@@ -255,6 +261,7 @@ void launch_gap_entries(const GapIn &in, const GapSite *sites, int n_ent, GapEnt
 
 size_t glfgen_lds_bytes(int cap, int hist_slots);
 void launch_glfgen(const GlfgenParams &p, hipStream_t s);
+void launch_glfgen_prefix(const double *fk, const double *beta, double *pfx, hipStream_t s);   // pfx: GLF_PFX_DOUBLES doubles
 void launch_combine(const CombineParams &p, hipStream_t s);
 void launch_mcall(const McallParams &p, hipStream_t s);
 

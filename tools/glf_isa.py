@@ -24,7 +24,7 @@ Phase B's loops follow, each found by what it holds, not by its label (static co
   rank code   "the quality of every rank joins its counts": the blocks that read and write one slot dword (ds_read_b32 and
               ds_write_b32) with the v_ffbh_u32 blocks around them -- a loop, or the unrolled copies, then counted per copy
   walk        the innermost loops with four global_load_dwordx2 and double-precision arithmetic, with the s_waitcnt that
-              opens the trip"""
+              opens the trip; and the walk's start, from the prefix-table load to the loop (walk_start below)"""
 import re
 import sys
 
@@ -179,6 +179,7 @@ def phase_b(bl, parent, phase_a):
         elif glob >= 4 and any(re.match(r"v_(fma|add|mul)_f64", i) for i in ins):
             wait = next((i for i in mem[0]["ins"] if i.startswith("s_waitcnt")), "none in the header block")
             line("walk_runs trip", h, mem, "  opens with: " + wait)
+            walk_start(bl, mem[0])
     # the rank code: slot dwords read and written back
     upd = [k for k, b in enumerate(bl) if cnt(b["ins"], "ds_read_b32") and cnt(b["ins"], "ds_write_b32") and id(b) not in skip]
     groups = []
@@ -208,6 +209,23 @@ def phase_b(bl, parent, phase_a):
         v, d = per[len(per) // 2]
         print("  %-34s from %-9s depth %d, %2d copies: v_*=%3d ds=%2d a rank (the median copy)" % (
             "rank code, unrolled", bl[first(g[0])]["lab"], depth(h) + 1 if h else 1, len(g), v, d))
+
+
+def walk_start(bl, header):
+    """The walk's start: from the prefix-table load (the last global_load_dwordx2 with a 64-bit vector address in front of the
+    walk's loop; the walk's own loads address beta from a scalar base) to the loop's header -- the loads issued behind it and
+    every s_waitcnt vmcnt on the way (vmcnt(0) right behind the load: the table entry is waited for on its own)."""
+    k = next(i for i, b in enumerate(bl) if b is header)
+    seq = [i for b in bl[:k] for i in b["ins"]]
+    at = next((j for j in range(len(seq) - 1, -1, -1) if re.match(r"global_load_dwordx2\s+v\[\d+:\d+\], v\[\d+:\d+\], off", seq[j])), None)
+    if at is None or len(seq) - at > 400:
+        print("    walk start: no prefix-table load in front of the loop")
+        return
+    tail = seq[at + 1:]
+    waits = ["%s after %d more loads" % (i.split(None, 1)[1], cnt(tail[:j], "global_load")) for j, i in enumerate(tail)
+             if i.startswith("s_waitcnt") and "vmcnt" in i]
+    print("    walk start: table load to loop header %d instructions, v_*=%d, loads behind it=%d; vmcnt waits: %s" % (
+        len(tail), cnt(tail, "v_"), cnt(tail, "global_load"), "; ".join(waits) or "none"))
 
 
 if __name__ == "__main__":

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void compact_size_kernel(const bcfgpu_call_sit
     if (m && (threadIdx.x & 63) == 0) atomicAdd(&counts[1], (unsigned long long)__popcll(m));
 }
 
-// one workgroup per site: header, then the GT planes, then the kept PL planes.  counts: [0] bytes of all records, [1] records
+// one workgroup per site: header, then the GT planes, then the kept PL planes, the gaps behind both zeroed.  counts: [0] bytes of all records, [1] records
 // (compact_size_kernel), [2] set when the records do not fit cap_bytes (nothing is written then)
 __global__ __launch_bounds__(256) void compact_copy_kernel(const bcfgpu_call_site *cs, const bcfgpu_site *ms, const int8_t *gt, const int32_t *pl,
                                                            int n_gt_planes, int n_smpl, int n_sites, int site0, int variants_only,
@@ -65,11 +65,18 @@ __global__ __launch_bounds__(256) void compact_copy_kernel(const bcfgpu_call_sit
         if (ms) h.mplp = ms[k];
         *reinterpret_cast<bcfgpu_call_rec*>(dst) = h;
     }
+    // every byte of the record is written, the two gaps included: what d_buf held before never shows
+    const int n_g = 2 * n_smpl, pl0 = (int)sizeof(bcfgpu_call_rec) + ((n_g + 3) & ~3);
     int8_t *g = reinterpret_cast<int8_t*>(dst + sizeof(bcfgpu_call_rec));
-    for (int i = tid; i < 2 * n_smpl; i += 256) g[i] = gt[(size_t)k * 2 * n_smpl + i];
+    // a site the caller skipped (write_skipped, mcall.hip) has no genotype: its GT planes were never written and are not read
+    if (nn == 0) for (int i = tid; i < n_g; i += 256) g[i] = (int8_t)BCFGPU_GT_MISSING;
+    else for (int i = tid; i < n_g; i += 256) g[i] = gt[(size_t)k * n_g + i];
+    if (tid < (-n_g & 3)) g[n_g + tid] = 0;                                        // 0-3 bytes up to the PL planes
     // the PL planes start 4-byte aligned: sizeof(bcfgpu_call_rec) is a multiple of 16 and 2*n_smpl is padded up to 4
-    int32_t *p = reinterpret_cast<int32_t*>(dst + sizeof(bcfgpu_call_rec) + ((2 * n_smpl + 3) & ~3));
+    int32_t *p = reinterpret_cast<int32_t*>(dst + pl0);
     for (int i = tid; i < ng * n_smpl; i += 256) p[i] = pl[(size_t)k * n_gt_planes * n_smpl + i];
+    const uint32_t end = (uint32_t)pl0 + 4u * ng * n_smpl;
+    if ((uint32_t)tid < bytes - end) dst[end + tid] = 0;                            // 0-15 bytes up to the next record
 }
 
 // d[0 .. n) becomes its exclusive sum, queued on st; the scan's temporary storage is workspace `slot`.  0, BCFGPU_E_HIP or

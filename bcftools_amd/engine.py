@@ -255,9 +255,10 @@ class Context:
             self.release(bufs + [b for _, b in outs])
         return nb.value, blk, min_dp, block, bdp
 
-    def mcall_device(self, cin):
+    def mcall_device(self, cin, fill=0):
         """Run the caller on a host CallInput and leave its result planes in HBM: (abi.CallOut of device pointers, {plane name:
-        DevBuf}, the host CallResult downloaded from them).  The buffers are the caller's to release (Context.release)."""
+        DevBuf}, the host CallResult downloaded from them).  The buffers are the caller's to release (Context.release).
+        fill: the byte the result planes hold before the call (what the call does not write keeps it)."""
         assert cin.n_smpl == self.cfg.n_smpl
         keep = []
         d = abi.CallIn()
@@ -270,7 +271,7 @@ class Context:
                 setattr(d, k, b.ptr)
         o, ob, res = self.alloc_call_out(cin.n_sites, cin.n_gt_max)
         for b in ob.values():
-            check(self.L.bcfgpu_memset(self.h, b.ptr, 0, b.nbytes))
+            check(self.L.bcfgpu_memset(self.h, b.ptr, fill, b.nbytes))
         try:
             check(self.L.bcfgpu_mcall(self.h, C.byref(d), C.byref(o)))
             self.sync()

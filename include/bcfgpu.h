@@ -640,7 +640,10 @@ int  bcfgpu_gap_prep_stats(const bcfgpu_ctx *ctx, bcfgpu_gap_stats *out);
  * each, with no exchange on the data path.  What goes to the writer on rank 0 is the records that will be written: they are
  * compacted on the device -- per record a fixed header with the call record and the mpileup-stage site record, then the
  * site's GT planes [2][n_smpl] i8 (padded to 4 bytes) and its trimmed PL planes [n_gt][n_smpl] i32, the whole padded to
- * 16 bytes, records back to back in site order -- and gathered in rank order, which is genomic order. */
+ * 16 bytes, records back to back in site order -- and gathered in rank order, which is genomic order.
+ * Every byte of a record is a function of the inputs: `pad`, the bytes that pad the GT planes to 4 and those that pad the
+ * record to 16 are zero, whatever d_buf held.  A record with call.nals_new == 0 (ret == 0: the caller skipped the site and
+ * wrote no genotype there) has BCFGPU_GT_MISSING in all 2*n_smpl GT bytes; the site's GT planes are not read. */
 typedef struct {
     int32_t site;                 /* site0 + index of the site in the shard's tile */
     int32_t n_gt;                 /* PL planes that follow: nals_new*(nals_new+1)/2, or 0 when FORMAT/PL is dropped */

@@ -97,13 +97,10 @@ def test_two_ranks_on_the_device_engine_match_one_context(tmp_path, gpu_ctx_fact
     got = np.load(out)
     assert n_rec > 5 and got.tobytes() == want.tobytes()
     # the records are self-describing: walk them
-    o, sites = 0, []
-    hdr = np.dtype([("site", "<i4"), ("n_gt", "<i4"), ("bytes", "<u4"), ("pad", "<i4")])
-    while o < len(got):
-        h = got[o:o + 16].view(hdr)[0]
-        sites.append(int(h["site"]))
-        o += int(h["bytes"])
-    assert o == len(got) and sites == sorted(sites) and len(sites) == n_rec
+    from tests.helpers import callrec
+    recs = callrec.walk(got, N_SMPL)                      # (asserts that the walk ends exactly at len(got))
+    sites = [int(h["site"]) for h, _, _ in recs]
+    assert sum(int(h["bytes"]) for h, _, _ in recs) == len(got) and sites == sorted(sites) and len(sites) == n_rec
 
 
 def test_bench_rehearsal_two_ranks_match_one_process():

@@ -43,14 +43,18 @@ def gap_prep_gpu(ctx, b, **kw):
 
 
 class DevicePool:
-    """A synthetic batch's reads as a pool in HBM: bcfgpu_pileup over the batch's whole reference (done once), after which
-    bcfgpu_gap_prep_tile runs on the candidate columns with nothing crossing PCIe but the per-column results."""
+    """A batch's reads as a pool in HBM: bcfgpu_pileup over the batch's whole reference (done once), after which
+    bcfgpu_gap_prep_tile runs on the candidate columns with nothing crossing PCIe but the per-column results.
+    `pool`: a ready pool (reads dict, r_mapq, r_smpl, order) -- reads grouped by sample and position-sorted inside a sample, any
+    lengths, shared between columns; order = None says that the batch lists every column's entries in pool order already.
+    Without it the pool is synth.indel_pool(b): equal-length reads, one per entry."""
 
-    def __init__(self, ctx, b):
+    def __init__(self, ctx, b, pool=None):
         from bcftools_amd import synth
         from bcftools_amd.lib import check
         self.ctx, self.b = ctx, b
-        self.reads, mapq, smpl, self.order = synth.indel_pool(b)
+        self.reads, mapq, smpl, self.order = synth.indel_pool(b) if pool is None else pool
+        self.has_zq = bool(np.asarray(self.reads["r_has_zq"]).any())
         self.rd = abi.Reads()
         self.rd.n_reads = self.reads["n_reads"]
         for k in READ_KEYS:
@@ -83,7 +87,9 @@ class DevicePool:
         oo.maxins, oo.indelreg, oo.max_support, oo.max_frac = (out["maxins"].ctypes.data, out["indelreg"].ctypes.data,
                                                                out["max_support"].ctypes.data, out["max_frac"].ctypes.data)
         t = abi.Tile()
-        check(ctx.L.bcfgpu_gap_prep_tile(ctx.h, ns, self.cols.ctypes.data, None, C.byref(par), C.byref(oo), CAP, C.byref(t)))
+        # (the pileup keeps no "ZQ" bytes: a pool that has some hands them over here)
+        check(ctx.L.bcfgpu_gap_prep_tile(ctx.h, ns, self.cols.ctypes.data, C.byref(self.rd) if self.has_zq else None, C.byref(par), C.byref(oo), CAP,
+                                         C.byref(t)))
         st = abi.GapStats()
         check(ctx.L.bcfgpu_gap_prep_stats(ctx.h, C.byref(st)))
         return out, st, t
@@ -156,7 +162,10 @@ def assert_tile_matches_host_batch(ctx, b, pool, got_t, tile, got):
     check(ctx.L.bcfgpu_memcpy_d2h(ctx.h, off.ctypes.data, tile.plp_off, off.nbytes))
     np.testing.assert_array_equal(np.diff(off.astype(np.int64)), want_cnt, err_msg="tile.plp_off")
     cell = np.repeat(np.arange(ns * S), full)
-    dev2batch = pool.order[np.argsort(cell[pool.order], kind="stable")]  # the batch's entries, column-major, each cell in pool order
+    if pool.order is None:
+        dev2batch = np.arange(len(cell))                                 # the batch lists its entries in pool order
+    else:
+        dev2batch = pool.order[np.argsort(cell[pool.order], kind="stable")]  # the batch's entries, column-major, each cell in pool order
     keep = np.repeat(np.repeat(ok, S), full)
     if got_t["aux"].size:
         np.testing.assert_array_equal(got_t["aux"][:tile.n_reads], got["aux"][dev2batch][keep], err_msg="p->aux")

@@ -174,6 +174,16 @@ class BcfVec(C.Structure):
 
 BCF_VEC = [("off", "<u8"), ("type", "<i4"), ("width", "<i4")]       # the same as a numpy record
 
+
+
+class VcfVec(C.Structure):
+    """bcfgpu_vcf_vec: where a VCF record's sample columns lie in the text buffer, and the key's place in its FORMAT column."""
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("idx", C.c_int32)]
+
+
+VCF_VEC = [("off", "<u8"), ("len", "<u4"), ("idx", "<i4")]
+VCFDEC_START_BYTES = 4 << 20        # BCFGPU_VCFDEC_START_BYTES: the bound on the workspace of bcfgpu_call_decode_vcf's column offsets
+
 BCF_KEY_MAX_WIDTH = 255
 
 
@@ -274,6 +284,8 @@ PROTOTYPES = {
     "bcfgpu_call_encode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
                                          C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_call_decode_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(BcfVec), C.POINTER(C.c_int32),
+                                         C.c_int32, C.c_void_p]),
+    "bcfgpu_call_decode_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(VcfVec), C.POINTER(C.c_int32),
                                          C.c_int32, C.c_void_p]),
     "bcfgpu_call_remap_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BcfKey), C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -1,8 +1,8 @@
 // bcfcodec.h -- what the device codecs of the records' per-sample bytes have in common (bcfenc.hip, vcfenc.hip, bcfcallenc.hip,
-// bcfkeys.hip, bcfdec.hip, vcfcallenc.hip): the line-wise copy between global memory and the LDS stage, the BCF2 block header and
-// typed-value rules (bcf_enc_vint / bcf_dec_int of htslib vcf.c; here host/vcfio.c enc_int1 / enc_size / enc_vint / dec_int), the
-// workgroup maximum of the size kernels, decimal text, the reading of a pass-through key from the input's bytes, and the FORMAT
-// keys of an mpileup record.  Device and host-inline code only.
+// bcfkeys.hip, bcfdec.hip, vcfcallenc.hip, vcfdec.hip): the line-wise copy between global memory and the LDS stage, the BCF2 block
+// header and typed-value rules (bcf_enc_vint / bcf_dec_int of htslib vcf.c; here host/vcfio.c enc_int1 / enc_size / enc_vint /
+// dec_int), the workgroup maximum of the size kernels, decimal text written and read, the reading of a pass-through key from the
+// input's bytes, and the FORMAT keys of an mpileup record.  Device and host-inline code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -142,6 +142,64 @@ __device__ __forceinline__ unsigned char *put_signed(unsigned char *p, int32_t v
 {
     if (v < 0) { *p++ = '-'; return put_value(p, 0u - (uint32_t)v); }
     return put_value(p, (uint32_t)v);
+}
+
+// ---- reading text (vcfdec.hip) ----
+// bit i of the result: byte i of the 16-byte line w is c (the exact zero-byte test on w ^ cccc, then the four high bits of a word
+// gathered by one multiplication whose partial products meet on no bit)
+__device__ __forceinline__ uint32_t line_match(uint4 w, unsigned char c)
+{
+    const uint32_t cc = 0x01010101u * c, x[4] = { w.x ^ cc, w.y ^ cc, w.z ^ cc, w.w ^ cc };
+    uint32_t m = 0;
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t t = ~(((x[i] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x[i] | 0x7f7f7f7fu);      // 0x80 in every byte of x[i] that is 0
+        m |= (((t >> 7) * 0x00204081u) >> 21 & 0xfu) << (4 * i);
+    }
+    return m;
+}
+// bits [lo, hi) of a 16-bit mask, clipped to it
+__device__ __forceinline__ uint32_t bit_range(int lo, int hi)
+{
+    lo = lo < 0 ? 0 : lo; hi = hi > 16 ? 16 : hi;
+    return lo < hi ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+}
+// One value of a FORMAT field: p[i .. n) starts with it, and it ends at ',' (more follow), ':' or n.  '.' alone is `missing`, anything
+// else must be [+-]?[0-9]+ inside int32 (the sum saturates far above it, so that leading zeros cost nothing and the test is exact).
+// i moves behind the value; false: an empty value, another byte in it, or out of range
+__device__ __forceinline__ bool get_text_value(const unsigned char *p, int &i, int n, int32_t &x)
+{
+    if (i < n && p[i] == '.' && (i + 1 == n || p[i + 1] == ',' || p[i + 1] == ':')) { x = BCFGPU_INT32_MISSING; ++i; return true; }
+    bool neg = false;
+    if (i < n && (p[i] == '+' || p[i] == '-')) { neg = p[i] == '-'; ++i; }
+    unsigned long long a = 0; const int i0 = i;
+    for (; i < n; ++i) {
+        const unsigned d = (unsigned)p[i] - '0';
+        if (d > 9u) break;
+        if (a < (1ull << 40)) a = a * 10u + d;
+    }
+    x = (int32_t)(neg ? 0u - (uint32_t)a : (uint32_t)a);
+    return i > i0 && (i == n || p[i] == ',' || p[i] == ':') && a <= (neg ? 2147483648ull : 2147483647ull);
+}
+// The planes of one called sample from its column's text: p[0] is the tab, the column ends at n.  Field idx (the fields are cut at
+// ':') is cut at ','; value j goes to o[j * S] for j < n_planes (the values past them are not looked at), `end of vector` to the planes
+// behind the last value; a column with fewer fields, or idx < 0, is '.': `missing`, then `end of vector`.  false: a malformed value
+__device__ __forceinline__ bool text_sample(int32_t *o, size_t S, int n_planes, const unsigned char *p, int n, int idx)
+{
+    int i = 1, f = 0, j = 0;
+    bool ok = true;
+    for (; f < idx && i < n; ++i) f += p[i] == ':';
+    if (idx >= 0 && f == idx) {
+        for (;;) {
+            int32_t x;
+            ok = get_text_value(p, i, n, x);
+            o[(size_t)j++ * S] = x;
+            if (!ok || j == n_planes || i == n || p[i] != ',') break;
+            ++i;
+        }
+    } else o[(size_t)j++ * S] = BCFGPU_INT32_MISSING;
+    for (; j < n_planes; ++j) o[(size_t)j * S] = BCFGPU_INT32_VECTOR_END;
+    return ok;
 }
 
 // ---- a pass-through key of a call record, read from the input record's bytes (bcfkeys.hip as BCF2, vcfcallenc.hip as text) ----

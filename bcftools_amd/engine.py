@@ -441,6 +441,33 @@ class Context:
             self.release(bufs)
         return out
 
+    def decode_vcf(self, text, vec, n_smpl_in, n_planes, col=None):
+        """bcfgpu_call_decode_vcf: one FORMAT key of VCF records' sample columns as int32 planes.  text: the records' columns (bytes
+        or np.uint8), uploaded here; vec: per record (off, len, idx), a sequence of triples or an array of abi.VCF_VEC; col: the
+        input column of each of the context's n_smpl called samples, or None.  Returns np.int32 [n_sites, n_planes, n_smpl]."""
+        text = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        v = np.zeros(len(vec), dtype=abi.VCF_VEC)
+        if len(vec):
+            a = np.asarray(vec)
+            if a.dtype.names:
+                v[:] = a
+            else:
+                v["off"], v["len"], v["idx"] = [[int(x[i]) for x in vec] for i in range(3)]
+        n, S = len(v), self.cfg.n_smpl
+        c = None if col is None else np.ascontiguousarray(col, np.int32)
+        assert c is None or len(c) == S
+        out = np.zeros((n, n_planes, S), np.int32)
+        bufs = [self.to_device(text), self.buf(out.nbytes)]
+        try:
+            check(self.L.bcfgpu_call_decode_vcf(self.h, n, n_smpl_in, bufs[0].ptr if text.nbytes else None, text.nbytes,
+                                                v.ctypes.data_as(C.POINTER(abi.VcfVec)), None if c is None else c.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                n_planes, bufs[1].ptr))
+            if out.nbytes:
+                bufs[1].download(out)
+        finally:
+            self.release(bufs)
+        return out
+
     def remap_call_bcf(self, indiv, keys, n_smpl_in, site, col=None, emit=None, cap_bytes=None):
         """bcfgpu_call_remap_bcf: the integer pass-through FORMAT keys of call records as BCF2 key blocks.  indiv: the input records'
         per-sample blocks (bytes or np.uint8) and site: the call's site records (a host array of abi.CallSite layout), both uploaded

@@ -2,7 +2,7 @@
  *  include/bcfgpu.h: the record loop of main_vcfcall (vcfcall.c:1089-1148) with mcall() on the device.
  *
  *      bcfgpu_call [-v] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]]
- *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] <in.vcf>
+ *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-parse] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] <in.vcf>
  *          -S: the samples to keep, in that order: NAME [PLOIDY|SEX] per line, or a PED file (vcfcall.c:202-344)
  *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c)
  *          -G: sample groups with their own allele frequencies, '-' = every sample alone, or NAME GROUP lines
@@ -13,6 +13,12 @@
  *              holds them and bcfgpu_call_decode_bcf makes the PL (and, with -G, AD / QS) planes there; the sample columns become
  *              text only for the records that are written.  Takes effect on BCF input without -C alleles and without -g (both read
  *              the samples' values on the host); in any other run the option does nothing.  The same output either way.
+ *          --device-parse: the same for VCF text input (plain, bgzipped or on a pipe): a line is split at its first nine tabs only, the
+ *              rest of it -- the sample columns, from their tab on -- goes to the device as text and bcfgpu_call_decode_vcf parses the PL
+ *              (and, with -G, AD / QS) planes there; a record's columns are split on the host only when the record is written.  Takes
+ *              effect on text input without -C alleles and without -g; in any other run the option does nothing, and it may stand
+ *              beside --device-input (each acts on its own kind of input).  Stricter than the host's atoi: a PL / AD / QS value that is
+ *              not '.' or [+-]?[0-9]+ inside int32 is "malformed VCF".  The same output either way.
  *          --device-records: with -O u|b the records' GT, PL and GQ do not come down as planes to be printed and parsed back: after the
  *              calls bcfgpu_call_encode_bcf turns them into BCF2 key blocks in HBM, for the records that are written only, and the host
  *              downloads the site records, the bytes and one offset per record and key.  A record is then its head and
@@ -39,7 +45,7 @@
  *              option does nothing.  The same output either way.
  *          --timing: lines on stderr: the seconds (reading records, building the planes on the host, uploads and device stages,
  *              writing records), how many records' planes were decoded on the device, and how many records' FORMAT blocks were
- *              encoded there; with --device-keys given, also how many pass-through key blocks were made on the device and on the host;
+ *              encoded there; with --device-parse given, also how many records' planes were parsed on the device; with --device-keys given, also how many pass-through key blocks were made on the device and on the host;
  *              with --device-text given, also how many records' sample columns were formatted on the device and on the host
  *
  *  Host: VCF text in, what mcall() reads from a record (alleles, FORMAT/PL, INFO/QS, INFO/I16) packed into the planes of
@@ -60,7 +66,8 @@
 #include "vcfio.h"
 #include "drv.h"
 
-/* with --device-input: line = the first nine columns, the per-sample block = ilen bytes at ioff of the byte buffer, its key headers in keys */
+/* with --device-input: line = the first nine columns, the per-sample block = ilen bytes at ioff of the byte buffer, its key headers in keys;
+ * with --device-parse: line = the first nine columns, the sample columns' text (from the ninth tab on) = ilen bytes at ioff */
 typedef struct { char *line; char **fld; int nfld; char **als; int nals, unseen, pl_idx, ad_idx; uint8_t *ploidy;
                  size_t ioff, ilen; int n_fmt, nkeys; vio_indiv_key *keys;
                  int *kjob; } rec_t;            /* --device-keys, a written record: key i's job of bcfgpu_call_remap_bcf, or -1 (the host's) */
@@ -398,7 +405,7 @@ static int unwanted_site(const char *line, int acgt_only, int skip_kind)
 
 /* ---- the state of a run, stage by stage ---- */
 typedef struct {                                                /* the command line */
-    int varonly, out_tags, keepalt, dev_in, dev_rec, dev_keys, keys_given, dev_text, text_given, want_timing;
+    int varonly, out_tags, keepalt, dev_in, dev_parse, parse_given, dev_rec, dev_keys, keys_given, dev_text, text_given, want_timing;
     int acgt_only, skip_kind;                                   /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
     const char *tgt_file, *smpl_file, *smpl_list, *ploidy_file, *ploidy_alias, *grp_arg, *grp_tag, *out_path, *in_path;
     double prior; char out_mode, prior_an_tag[64], prior_ac_tag[64];
@@ -409,11 +416,12 @@ typedef struct { preg_t *reg; int n; char last_sex[64]; } ploidy_t;
 /* the samples called, S of the input's S_in: output sample s = input column col[s] (bcf_subset with -S); the names of the input
  * columns; a sample's ploidy ("0", "1", "2") or sex name; -G: the group of every sample */
 typedef struct { int S, S_in, *col; char **names, (*spec)[64]; int32_t *grp; int ngrp; } smap_t;
-/* the records that are called; --device-input: their per-sample blocks, back to back; -i: where the last record lay */
+/* the records that are called; --device-input: their per-sample blocks, back to back (--device-parse: their sample columns' text); -i: where the last record lay */
 typedef struct { rec_t *rec; int n, cap, ngmax, namax; unsigned char *ibuf; size_t ibuf_l, ibuf_m; char *prev_chrom; long prev_pos0; } recs_t;
 /* what mcall() reads from the records: PL planes (missing / vector_end kept), QS, I16.
- * --device-input: no host PL / AD planes; per record where the PL vector (and the -G tag's) lies in the byte buffer */
-typedef struct { int32_t *nals, *unseen, *pl, *ad, *pan, *pac; float *qs, *i16; bcfgpu_bcf_vec *vec_pl, *vec_ad; int want_ad; } hplanes_t;
+ * --device-input: no host PL / AD planes; per record where the PL vector (and the -G tag's) lies in the byte buffer.
+ * --device-parse: likewise; per record where its columns lie in the byte buffer and the key's place in the FORMAT column */
+typedef struct { int32_t *nals, *unseen, *pl, *ad, *pan, *pac; float *qs, *i16; bcfgpu_bcf_vec *vec_pl, *vec_ad; bcfgpu_vcf_vec *txt_pl, *txt_ad; int want_ad; } hplanes_t;
 typedef struct {                                                /* the planes in HBM, and what came down of the results */
     bcfgpu_ctx *ctx;
     int32_t *d_nals, *d_unseen, *d_plin, *d_ad, *d_grp, *d_pan, *d_pac; float *d_qs, *d_i16;
@@ -457,6 +465,7 @@ static int parse_options(int argc, char **argv, opt_t *o)
         else if (!strcmp(argv[1], "--no-version")) { ++argv; --argc; }                                                       /* (no ##bcftools_callVersion lines are written anyway) */
         else if (!strcmp(argv[1], "-i")) { insert_missed = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-input")) { o->dev_in = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-parse")) { o->dev_parse = o->parse_given = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-records")) { o->dev_rec = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-keys")) { o->dev_keys = o->keys_given = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-text")) { o->dev_text = o->text_given = 1; ++argv; --argc; }
@@ -506,7 +515,7 @@ static int parse_options(int argc, char **argv, opt_t *o)
     }
     if (o->gv_n && o->varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (o->gv_n && cals) DIE("-g with -C alleles is not supported\n");
-    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-parse] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
     o->in_path = argv[1]; return 0;
 }
 static void load_ploidy(opt_t *o, ploidy_t *P)
@@ -558,6 +567,7 @@ static vio_file *open_input(opt_t *o, vio_hdr **hdr)
     if (!fin) DIE("%s\n", vio_error());
     if (!(*hdr = vio_read_hdr(fin))) DIE("%s\n", vio_error());
     o->dev_in = o->dev_in && vio_is_bcf(fin) && !cals && !o->gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
+    o->dev_parse = o->dev_parse && !vio_is_bcf(fin) && !cals && !o->gv_n;   /* the same two, for the same reasons, on text input */
     o->dev_rec = o->dev_rec && (o->out_mode == 'u' || o->out_mode == 'b') && !o->gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
     o->dev_keys = o->dev_keys && o->dev_in && o->dev_rec;      /* the input's bytes in HBM and key blocks to splice: both ends on the device */
     o->dev_text = o->dev_text && o->dev_in && (o->out_mode == 'v' || o->out_mode == 'z');     /* the input's bytes in HBM, text records to write */
@@ -671,9 +681,23 @@ static void read_records(const opt_t *o, const ploidy_t *P, const smap_t *M, vio
         if (R->n == R->cap) { R->cap = R->cap ? 2 * R->cap : 1024; R->rec = realloc(R->rec, (size_t)R->cap * sizeof *R->rec); }
         if (cals) push_event(0, R->n);
         rec_t *r = &R->rec[R->n++];
-        r->line = strdup(use); free(owned);
+        const char *smp = NULL;                                  /* --device-parse: the ninth tab, where the sample columns start */
+        if (o->dev_parse) {
+            smp = use;
+            for (int t = 0; t < 9 && smp; ++t) smp = strchr(smp + (t > 0), '\t');
+            if (!smp) DIE("malformed VCF\n");
+        }
+        r->line = smp ? strndup(use, (size_t)(smp - use)) : strdup(use);
         r->fld = split(r->line, '\t', &r->nfld);
         r->keys = NULL; r->nkeys = 0; r->kjob = NULL;
+        if (smp) {                                               /* the columns join the byte buffer as they are */
+            const size_t l_smp = strlen(smp);
+            if (R->ibuf_l + l_smp > R->ibuf_m) { R->ibuf_m = (R->ibuf_l + l_smp) * 2 + (1 << 20); R->ibuf = realloc(R->ibuf, R->ibuf_m); if (!R->ibuf) DIE("out of memory\n"); }
+            memcpy(R->ibuf + R->ibuf_l, smp, l_smp);
+            r->ioff = R->ibuf_l; r->ilen = l_smp; R->ibuf_l += l_smp;
+            if (l_smp > UINT32_MAX) DIE("malformed VCF\n");
+        }
+        free(owned);
         if (o->dev_in) {                                         /* the block joins the byte buffer; where its keys' values lie */
             if (r->nfld != 9 || n_sample != S_in) DIE("malformed VCF\n");
             if (R->ibuf_l + l_indiv > R->ibuf_m) { R->ibuf_m = (R->ibuf_l + l_indiv) * 2 + (1 << 20); R->ibuf = realloc(R->ibuf, R->ibuf_m); if (!R->ibuf) DIE("out of memory\n"); }
@@ -682,7 +706,7 @@ static void read_records(const opt_t *o, const ploidy_t *P, const smap_t *M, vio
             r->keys = malloc((size_t)(n_fmt > 0 ? (n_fmt < 64 ? n_fmt : 64) : 1) * sizeof *r->keys);
             if ((r->nkeys = vio_indiv_keys(hdr, indiv, l_indiv, n_fmt, n_sample, r->keys)) < 0) DIE("%s\n", vio_error());
         } else
-        if (S_in < 0 || r->nfld != 9 + S_in) DIE("malformed VCF\n");
+        if (S_in < 0 || r->nfld != (smp ? 9 : 9 + S_in)) DIE("malformed VCF\n");     /* (--device-parse: the device counts the columns) */
         record_alleles(r); record_ploidy(r, P, M);
         if (r->nals * (r->nals + 1) / 2 > R->ngmax) R->ngmax = r->nals * (r->nals + 1) / 2;
     }
@@ -728,8 +752,9 @@ static void read_groups(opt_t *o, smap_t *M)
 }
 
 /* ---- what mcall() reads from the records ---- */
-/* FORMAT/PL and the -G tag among the record's keys; --device-input: where their vectors lie in the byte buffer */
-static void format_lookup(const opt_t *o, rec_t *r, int want_ad, bcfgpu_bcf_vec *vec_pl, bcfgpu_bcf_vec *vec_ad)
+/* FORMAT/PL and the -G tag among the record's keys; --device-input: where their vectors lie in the byte buffer; --device-parse: the
+ * record's columns and the keys' places */
+static void format_lookup(const opt_t *o, rec_t *r, int want_ad, bcfgpu_bcf_vec *vec_pl, bcfgpu_bcf_vec *vec_ad, bcfgpu_vcf_vec *txt_pl, bcfgpu_vcf_vec *txt_ad)
 {
     r->pl_idx = r->ad_idx = -1;
     int nk = r->nkeys; char *fmt = NULL, **keys = NULL;          /* the keys' names: the block's, or the FORMAT column's */
@@ -742,6 +767,8 @@ static void format_lookup(const opt_t *o, rec_t *r, int want_ad, bcfgpu_bcf_vec 
     free(keys); free(fmt);
     if (r->pl_idx < 0) DIE("no FORMAT/PL at %s:%s\n", r->fld[0], r->fld[1]);
     if (want_ad && r->ad_idx < 0) DIE("FORMAT/%s is required with -G (%s:%s)\n", o->grp_tag, r->fld[0], r->fld[1]);     /* mcall.c:1476 */
+    if (txt_pl) { txt_pl->off = r->ioff; txt_pl->len = (uint32_t)r->ilen; txt_pl->idx = r->pl_idx; }
+    if (txt_ad) { *txt_ad = *txt_pl; txt_ad->idx = r->ad_idx; }
     if (!o->dev_in) return;
     const vio_indiv_key *kp = &r->keys[r->pl_idx], *ka = want_ad ? &r->keys[r->ad_idx] : NULL;
     if (kp->type < 1 || kp->type > 3) DIE("FORMAT/PL is not an integer vector at %s:%s\n", r->fld[0], r->fld[1]);
@@ -785,14 +812,15 @@ static void parse_info(const opt_t *o, const rec_t *r, hplanes_t *H, int k)
 }
 static void build_planes(const opt_t *o, const smap_t *M, recs_t *R, hplanes_t *H)
 {
-    const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_in = o->dev_in;
+    const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_in = o->dev_in, on_dev = o->dev_in || o->dev_parse;
     memset(H, 0, sizeof *H);
     H->nals = malloc((size_t)n * 4); H->unseen = malloc((size_t)n * 4);
-    H->pl = dev_in ? NULL : malloc((size_t)n * ngmax * S * 4);
+    H->pl = on_dev ? NULL : malloc((size_t)n * ngmax * S * 4);
     H->want_ad = M->ngrp > 1;
     H->vec_pl = dev_in ? calloc((size_t)n + 1, sizeof *H->vec_pl) : NULL; H->vec_ad = dev_in && H->want_ad ? calloc((size_t)n + 1, sizeof *H->vec_ad) : NULL;
+    H->txt_pl = o->dev_parse ? calloc((size_t)n + 1, sizeof *H->txt_pl) : NULL; H->txt_ad = o->dev_parse && H->want_ad ? calloc((size_t)n + 1, sizeof *H->txt_ad) : NULL;
     H->qs = calloc((size_t)n * 5, 4); H->i16 = calloc((size_t)n * 16, 4);
-    H->ad = H->want_ad && !dev_in ? malloc((size_t)n * namax * S * 4) : NULL;
+    H->ad = H->want_ad && !on_dev ? malloc((size_t)n * namax * S * 4) : NULL;
     H->pan = o->prior_an_tag[0] ? malloc((size_t)n * 4) : NULL; H->pac = o->prior_an_tag[0] ? malloc((size_t)n * 4 * 4) : NULL;
     for (int k = 0; k < n; ++k) {
         rec_t *r = &R->rec[k];
@@ -801,8 +829,8 @@ static void build_planes(const opt_t *o, const smap_t *M, recs_t *R, hplanes_t *
         if (pl) for (size_t i = 0; i < (size_t)ngmax * S; ++i) pl[i] = BCFGPU_INT32_VECTOR_END;
         if (ad) for (size_t i = 0; i < (size_t)namax * S; ++i) ad[i] = BCFGPU_INT32_VECTOR_END;
         if (H->pan) { H->pan[k] = BCFGPU_INT32_MISSING; for (int i = 0; i < 4; ++i) H->pac[(size_t)k * 4 + i] = BCFGPU_INT32_VECTOR_END; }
-        format_lookup(o, r, H->want_ad, dev_in ? &H->vec_pl[k] : NULL, H->vec_ad ? &H->vec_ad[k] : NULL);
-        for (int s = 0; s < S && !dev_in; ++s) {
+        format_lookup(o, r, H->want_ad, dev_in ? &H->vec_pl[k] : NULL, H->vec_ad ? &H->vec_ad[k] : NULL, H->txt_pl ? &H->txt_pl[k] : NULL, H->txt_ad ? &H->txt_ad[k] : NULL);
+        for (int s = 0; s < S && !on_dev; ++s) {
             char *smp = strdup(r->fld[9 + M->col[s]]); int nv; char **vals = split(smp, ':', &nv);
             parse_int_list(vals, nv, r->pl_idx, pl, ngmax, S, s);
             if (ad) parse_int_list(vals, nv, r->ad_idx, ad, namax, S, s);
@@ -815,6 +843,13 @@ static void build_planes(const opt_t *o, const smap_t *M, recs_t *R, hplanes_t *
 /* ---- the device ---- */
 /* everything goes up once; the records are called in runs of equal ploidy vectors (the ploidy is per call:
  * vcfcall.c:807-825 re-initialises it when it changes) -- the planes are [record][...]: a run is a slice */
+/* --device-parse: a record with the wrong number of columns, or a value that is no integer, is the text route's "malformed VCF" */
+static void decode_text_planes(bcfgpu_ctx *ctx, int n, int S_in, const void *d_text, size_t l_text, const bcfgpu_vcf_vec *vec, const int32_t *cmap, int n_planes, int32_t *d_out)
+{
+    const int rc = bcfgpu_call_decode_vcf(ctx, n, S_in, d_text, l_text, vec, cmap, n_planes, d_out);
+    if (rc == BCFGPU_E_ARG) DIE("malformed VCF\n");
+    if (rc) DIE("bcfgpu_call_decode_vcf: %s (%d)\n", bcfgpu_last_error(), rc);
+}
 static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, const hplanes_t *H, dev_t *D)
 {
     const rec_t *recs = R->rec; const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_rec = o->dev_rec || o->dev_text;
@@ -836,6 +871,17 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
             CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_ad, cmap, namax, D->d_ad));
         }
         if (!o->dev_keys && !o->dev_text) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
+    } else if (o->dev_parse) {                                   /* the columns' text goes up once and is parsed there */
+        void *dp = NULL;
+        D->d_indiv = dev_upload(ctx, R->ibuf, R->ibuf_l);
+        const int32_t *cmap = o->smpl_file ? (const int32_t *)M->col : NULL;
+        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4 + 16, &dp)); D->d_plin = dp;
+        decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_pl, cmap, ngmax, D->d_plin);
+        if (H->want_ad) {
+            CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); D->d_ad = dp;
+            decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_ad, cmap, namax, D->d_ad);
+        }
+        CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL;
     } else {
         D->d_plin = dev_upload(ctx, H->pl, (size_t)n * ngmax * S * 4);
         if (H->ad) D->d_ad = dev_upload(ctx, H->ad, (size_t)n * namax * S * 4);
@@ -1271,6 +1317,12 @@ static void write_record(writer_t *W, int k, int gv_min_dp)
         if (vio_indiv_text(W->hdr, R->ibuf + r->ioff, r->ilen, r->n_fmt, W->M->S_in, &W->smp_text, &W->smp_cap)) DIE("%s\n", vio_error());
         smp_fld = split(W->smp_text + 1, '\t', &ns);
         if (ns != W->M->S_in) DIE("malformed VCF\n");
+    } else if (o->dev_parse && want_text) {                    /* --device-parse: the columns' text is split here, for a record that is written */
+        int ns;
+        if (r->ilen + 1 > W->smp_cap) { W->smp_cap = (r->ilen + 1) * 2; W->smp_text = realloc(W->smp_text, W->smp_cap); if (!W->smp_text) DIE("out of memory\n"); }
+        memcpy(W->smp_text, R->ibuf + r->ioff, r->ilen); W->smp_text[r->ilen] = 0;
+        smp_fld = split(W->smp_text + 1, '\t', &ns);
+        if (ns != W->M->S_in) DIE("malformed VCF\n");
     }
     fputs("\tGT", LN);
     for (int i = 0; i < F.nk; ++i) if (i != r->pl_idx || !c->pl_dropped) fprintf(LN, ":%s", F.keys[i]);
@@ -1283,7 +1335,7 @@ static void write_record(writer_t *W, int k, int gv_min_dp)
         rewind(LN);
     } else if (dev_rec) splice_record(W, k, &F, head_end); else end_record(W->fout, W->hdr);
     free(F.keys); free(fmt);
-    if (o->dev_in && want_text) free(smp_fld);
+    if ((o->dev_in || o->dev_parse) && want_text) free(smp_fld);
 }
 static void write_records(writer_t *W)
 {
@@ -1354,6 +1406,7 @@ int main(int argc, char **argv)
     if (o.want_timing) fprintf(stderr, "[bcfgpu_call] seconds: reading records %.3f, building the planes on the host %.3f, uploads and device stages %.3f, writing records %.3f\n", t_read, t_planes, t_dev, t_write);
     if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", o.dev_in ? R.n : 0);
     if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device records: %d records' FORMAT blocks encoded on the device\n", B.n_enc);
+    if (o.want_timing && o.parse_given) fprintf(stderr, "[bcfgpu_call] device parse: %d records' planes parsed on the device\n", o.dev_parse ? R.n : 0);
     if (o.want_timing && o.keys_given) fprintf(stderr, "[bcfgpu_call] device keys: %ld pass-through key blocks made on the device, %ld on the host\n", B.n_pjob, B.n_phost);
     if (o.want_timing && o.text_given) fprintf(stderr, "[bcfgpu_call] device text: %ld records' sample columns formatted on the device, %ld on the host\n", B.n_tdev, B.n_thost);
     bcfgpu_destroy(D.ctx);

@@ -32,6 +32,8 @@
  *                                           and the writer's typed-value encoder, for GT, PL and GQ of the call records
  *    bcfgpu_call_decode_bcf              <- the bcf_get_format_int32 calls of mcall() (mcall.c:1444, :1475) and the unpacking of the
  *                                           per-sample block behind them: FORMAT/PL and AD / QS of BCF records as the planes of bcfgpu_call_in
+ *    bcfgpu_call_decode_vcf              <- the vcf_parse_format / bcf_get_format_int32 pair behind the same two calls (mcall.c:1444, :1475) on VCF
+ *                                           text input: FORMAT/PL and AD / QS of a record's sample columns as the planes of bcfgpu_call_in
  *    bcfgpu_call_remap_bcf               <- mcall_trim_and_update_numberR (mcall.c:1196-1265), bcf_subset's sample choice and the writer's
  *                                           typed-value encoder, for the integer FORMAT keys a call record passes through (AD, DP, SP, ...)
  *    bcfgpu_call_encode_vcf              <- the same three and the text vcf_format writes for them: the sample columns of a call record, the
@@ -731,6 +733,34 @@ typedef struct {
 } bcfgpu_bcf_vec;
 int  bcfgpu_call_decode_bcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_smpl_in, const void *d_indiv, uint64_t n_indiv_bytes,
                             const bcfgpu_bcf_vec *vec, const int32_t *col, int32_t n_planes, int32_t *d_out);
+
+/* The same planes from VCF text input (vcfdec.hip): one FORMAT key of n_sites records, read on the device from the records' sample
+ * columns as the text file holds them.
+ *   d_text   DEVICE, n_text_bytes: the records' sample columns, back to back (any other bytes may lie between them)
+ *   vec      HOST [n_sites]: run k is `len` bytes at `off`: exactly n_smpl_in columns, each a tab followed by the column's text (the rest
+ *            of a VCF line from its ninth tab on, without the newline); idx = the key's place in the record's FORMAT column
+ *   col      HOST [cfg.n_smpl] or NULL: the input column of each called sample (NULL: called sample s is input column s, cfg.n_smpl <= n_smpl_in)
+ *   d_out    DEVICE [n_sites][n_planes][cfg.n_smpl]
+ * The rule is the text route's (host/bcfgpu_call.c parse_int_list): the column is cut at ':', field idx at ','; for j < n_planes value j
+ * is BCFGPU_INT32_MISSING when it is '.', else the int32 of [+-]?[0-9]+ (the decimal text of the two sentinel values is stored as it
+ * stands); the planes at and past the number of values are BCFGPU_INT32_VECTOR_END, the values past n_planes are dropped unread; a column
+ * with fewer than idx + 1 fields (a whole-column '.' included), or idx < 0, has MISSING in plane 0 and VECTOR_END in the rest.  The
+ * other fields may hold any bytes but tab and ':'; they are only skipped.
+ * BCFGPU_E_ARG for NULL pointers, n_planes < 1 or a col entry outside [0, n_smpl_in), BCFGPU_E_RANGE when off + len passes n_text_bytes,
+ * and BCFGPU_E_ARG for a run whose first byte is no tab or whose tab count is not n_smpl_in (the "malformed VCF" of the host, found by an
+ * indexing pass over every record before any plane is written): nothing is written in any of these cases.
+ * Stricter than the host's atoi: a value of the selected field that is empty, holds a byte other than a digit behind the optional sign,
+ * or lies outside int32 is BCFGPU_E_ARG too; d_out is undefined then, nothing outside it is touched.
+ * The columns' offsets are a workspace of at most BCFGPU_VCFDEC_START_BYTES (or one record's, 4 (n_smpl_in + 1) bytes, when that is
+ * more): the two kernels run over chunks of that many sites.  n_sites == 0 is valid.  Runs on the context's stream and synchronises it. */
+#define BCFGPU_VCFDEC_START_BYTES (4u << 20)
+typedef struct {
+    uint64_t off;   /* byte offset, inside the text buffer, of the tab in front of input sample 0's column */
+    uint32_t len;   /* bytes from there to the end of the last sample's column (no newline) */
+    int32_t  idx;   /* the key's place among the record's FORMAT keys, 0-based; < 0: the record has no such key */
+} bcfgpu_vcf_vec;
+int  bcfgpu_call_decode_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_smpl_in, const void *d_text, uint64_t n_text_bytes,
+                            const bcfgpu_vcf_vec *vec, const int32_t *col, int32_t n_planes, int32_t *d_out);
 
 /* The caller's own records: FORMAT/GT, the trimmed FORMAT/PL and FORMAT/GQ of every call record as BCF2 bytes, made on the planes
  * bcfgpu_mcall / bcfgpu_pipeline left in HBM (bcfcallenc.hip) -- what bcf_update_genotypes and bcf_update_format_int32 (mcall.c:1158-1194,

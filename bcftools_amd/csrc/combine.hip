@@ -106,6 +106,8 @@ __device__ float wave_calc_vdb(const int *pos, int lane, double *s_term)
     float mean_diff = 0;
     if (lane == 0) {
         const double2 *t2 = reinterpret_cast<const double2*>(s_term);
+        // (25 pairs in flight, not all 50: requested all at once they pass the kernel's register budget by one load)
+        #pragma unroll 25
         for (i = 0; i < readlen / 2; i++) {
             const double2 t = t2[i];
             mean_diff = (float)((double)mean_diff + t.x);
@@ -171,9 +173,8 @@ __device__ __forceinline__ double dev_logsumexp2(double a, double b)
 }
 
 struct SiteShared {
-    int a[5]; int n_alleles, unseen, ori_ref, x;
+    int a[5]; int n_alleles, unseen, ori_ref;
     float qsum_out[5];
-    int g[15], g1[15], g2[15];
     unsigned long long tot[32];   // integer totals
     double segb_sum; double sum_min;
     float bias[6];
@@ -240,7 +241,7 @@ template <int V> __device__ __forceinline__ void store_i32(int32_t *p, const uin
     else p[0] = (int32_t)b[0];
 }
 template <int NAL, int V>
-__device__ __forceinline__ void sample_planes(const CombineParams &P, SampleTotals &T, const int (&gs)[15], const int (&g1s)[15], const int (&g2s)[15], const int (&as)[5],
+__device__ __forceinline__ void sample_planes(const CombineParams &P, SampleTotals &T, const int (&as)[5],
                                               int is, long c0, int base, int cn, int tid, long ncells, double *s_min, uint32_t &wide_seen)
 {
     constexpr int X = NAL * (NAL + 1) / 2;
@@ -269,21 +270,30 @@ __device__ __forceinline__ void sample_planes(const CombineParams &P, SampleTota
             }
             #pragma unroll
             for (int v = 0; v < V; ++v) mn[v] = FLT_MAX;
+            // genotype z = k (k + 1) / 2 + j of the site is the pair of alleles (j, k), j <= k (bam2bcf.c:634-640): both indices are
+            // known where the loops are unrolled, so its two bases are as[j] and as[k] (scalar) and no table of them is kept
             #pragma unroll
-            for (int j = 0; j < X; ++j) {
-                const int b1 = g1s[j], b2 = g2s[j];                // the two bases of genotype j (scalar)
+            for (int k = 0; k < NAL; ++k) {
                 #pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const int b = (int)(misc[v] & 7);
-                    pv[j][v] = b1 == b2 ? (b1 == b ? 0.0f : pa[v]) : ((b1 == b || b2 == b) ? ph[v] : pa[v]);
+                for (int j = 0; j <= k; ++j) {
+                    const int b1 = as[j], b2 = as[k];
+                    #pragma unroll
+                    for (int v = 0; v < V; ++v) {
+                        const int b = (int)(misc[v] & 7);
+                        pv[k * (k + 1) / 2 + j][v] = b1 == b2 ? (b1 == b ? 0.0f : pa[v]) : ((b1 == b || b2 == b) ? ph[v] : pa[v]);
+                    }
                 }
             }
             if (__any(any_full)) {
                 #pragma unroll
-                for (int j = 0; j < X; ++j) {
+                for (int k = 0; k < NAL; ++k) {
                     #pragma unroll
-                    for (int v = 0; v < V; ++v)
-                        if (misc[v] & CR_FULL) pv[j][v] = P.cr.p15[(size_t)(c0 + s + v) * 16 + gs[j]];
+                    for (int j = 0; j <= k; ++j) {
+                        const int g = tri_c(as[j], as[k]);          // the genotype's place among the cell's 15 stored likelihoods
+                        #pragma unroll
+                        for (int v = 0; v < V; ++v)
+                            if (misc[v] & CR_FULL) pv[k * (k + 1) / 2 + j][v] = P.cr.p15[(size_t)(c0 + s + v) * 16 + g];
+                    }
                 }
             }
             #pragma unroll
@@ -368,12 +378,17 @@ __device__ __forceinline__ void fix_wide_cells(const CombineParams &P, SampleTot
         const uint32_t cnt4 = P.cr.cnt4[c0 + s], adf = P.cr.adf[c0 + s], adr = P.cr.adr[c0 + s];
         const WideRec *w = P.cr.wide + (uint32_t)P.cr.qs64[c0 + s];
         const uint32_t wc[4] = { w->cnt[0] & 0xffffu, w->cnt[0] >> 16, w->cnt[1] & 0xffffu, w->cnt[1] >> 16 };
+        #pragma unroll
         for (int j = 0; j < 4; ++j) T.cnt[j] += wc[j] - ((cnt4 >> (8 * j)) & 0xff);
         if (!live) continue;
+        #pragma unroll
         for (int j = 0; j < 4; ++j) P.out.dp4[((size_t)is * 4 + j) * Ss + s] = (uint16_t)wc[j];
         T.scr += w->scr - ((misc >> 8) & 0xff);
         if (P.out.scr) P.out.scr[(size_t)is * Ss + s] = (uint16_t)w->scr;
-        for (int j = 0; j < nal; ++j) {
+        // (unrolled over all five alleles under a guard: the lane's totals are indexed with constants and stay in registers)
+        #pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            if (j >= nal) continue;
             const int aj = as[j];
             const uint32_t ad = aj < 4 ? w->ad[aj] : 0u, nf = ad & 0xffffu, nr = ad >> 16;
             T.adf[j] += nf - (aj < 4 ? (adf >> (8 * aj)) & 0xff : 0);
@@ -458,40 +473,44 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
 
     // ---- allele ordering (bam2bcf.c:577-632), lane 0 ----
     if (tid == 0) {
-        float qsum[5] = { s_q[0], s_q[1], s_q[2], s_q[3], 0.f };
-        int idx[5] = {0, 1, 2, 3, 4};
-        for (int i = 1; i < 4; i++)
-            for (int j = i; j > 0 && qsum[idx[j]] < qsum[idx[j - 1]]; j--) { int t = idx[j]; idx[j] = idx[j - 1]; idx[j - 1] = t; }
+        // The reference's insertion sort of the four bases by their sums (ascending; a base moves down only past a strictly larger
+        // sum, so equal sums keep the order of the bases) is the order of the pairs (sum, base): five compare-exchanges on four
+        // pairs held in registers -- no array is indexed with a value known only at run time, here or below.
+        float q0 = s_q[0], q1 = s_q[1], q2 = s_q[2], q3 = s_q[3];
+        int i0 = 0, i1 = 1, i2 = 2, i3 = 3;
+        #define CEX(qa, ia, qb, ib) do { if (qb < qa || (qb == qa && ib < ia)) { const float tq = qa; qa = qb; qb = tq; const int ti = ia; ia = ib; ib = ti; } } while (0)
+        CEX(q0, i0, q1, i1); CEX(q2, i2, q3, i3); CEX(q0, i0, q2, i2); CEX(q1, i1, q3, i3); CEX(q1, i1, q2, i2);
+        #undef CEX
+        const float sq[4] = { q0, q1, q2, q3 };
+        const int si[4] = { i0, i1, i2, i3 };
         for (int i = 0; i < 5; i++) { sh.a[i] = -1; sh.qsum_out[i] = 0; }
         sh.unseen = -1;
         sh.a[0] = ref4;
-        int i, j;
-        for (i = 3, j = 1; i >= 0; i--) {
-            const int ipos = idx[i];
-            if (ipos == ref4) sh.qsum_out[0] = qsum[ipos];
+        int j = 1, stop = -1, stop_base = 0;            // stop: where the walk from the largest sum down met a base without reads (-1: nowhere)
+        #pragma unroll
+        for (int i = 3; i >= 0; i--) {
+            if (stop >= 0) continue;
+            const int ipos = si[i];
+            if (ipos == ref4) sh.qsum_out[0] = sq[i];
+            else if (!sq[i]) { stop = i; stop_base = ipos; }
             else {
-                if (!qsum[ipos]) break;
-                sh.qsum_out[j] = qsum[ipos];
+                sh.qsum_out[j] = sq[i];
                 sh.a[j++] = ipos;
             }
         }
         int ret = 0;
         if (ref_base >= 0) {
-            if (((ref4 < 4 && j < 4) || (ref4 == 4 && j < 5)) && i >= 0) { sh.unseen = j; sh.a[j++] = idx[i]; }
+            if (((ref4 < 4 && j < 4) || (ref4 == 4 && j < 5)) && stop >= 0) { sh.unseen = j; sh.a[j++] = stop_base; }
             sh.n_alleles = j;
         } else {
             sh.n_alleles = j;
             if (j == 1) ret = -1;
         }
         sh.ori_ref = ref_base >= 0 ? nt16_int_c(ref_base) : -1;
-        sh.x = sh.n_alleles * (sh.n_alleles + 1) / 2;
-        int z = 0;
-        for (i = 0; i < sh.n_alleles; ++i)
-            for (j = 0; j <= i; ++j) { sh.g1[z] = sh.a[j]; sh.g2[z] = sh.a[i]; sh.g[z++] = tri_c(sh.a[j], sh.a[i]); }
         site->ret = ret;
     }
     __syncthreads();
-    const int nal = sh.n_alleles, x = sh.x;
+    const int nal = sh.n_alleles;
     const bool dead = (P.is_indel && nal == 1);     // bcf_call_combine returned -1 (bam2bcf.c:611)
 
     // ---- per-sample planes + integer totals ----
@@ -501,12 +520,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
     for (int j = 0; j < 5; ++j) T.adf[j] = T.adr[j] = 0;
     T.scr = T.ori = T.mq0 = 0; T.cnt[0] = T.cnt[1] = T.cnt[2] = T.cnt[3] = 0;
     // the allele order is uniform over the wavefront: keep it in scalar registers so that plane addresses are scalar
-    int gs[15], g1s[15], g2s[15], as[5];
-    #pragma unroll
-    for (int j = 0; j < 15; ++j) {
-        gs[j] = __builtin_amdgcn_readfirstlane(j < x ? sh.g[j] : 0);
-        g1s[j] = __builtin_amdgcn_readfirstlane(j < x ? sh.g1[j] : 0); g2s[j] = __builtin_amdgcn_readfirstlane(j < x ? sh.g2[j] : 0);
-    }
+    int as[5];
     #pragma unroll
     for (int j = 0; j < 5; ++j) as[j] = __builtin_amdgcn_readfirstlane(j < nal ? sh.a[j] : 4);
     double *s_min = reinterpret_cast<double*>(s_stage);
@@ -514,13 +528,15 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
     for (int base = 0; base < S; base += CHUNK) {
         const int cn = min(CHUNK, S - base);
         __syncthreads();
+        // (five alleles -- a reference N, rare -- a sample a lane whatever V: four samples of 15 likelihoods beside the lane's totals
+        // pass 128 VGPRs, and the kernel has no private segment otherwise; the same values either way)
         #define PLANES(V_) switch (dead ? 0 : nal) { \
-            case 1: sample_planes<1, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
-            case 2: sample_planes<2, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
-            case 3: sample_planes<3, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
-            case 4: sample_planes<4, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
-            case 5: sample_planes<5, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
-            default: sample_planes<0, V_>(P, T, gs, g1s, g2s, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; }
+            case 1: sample_planes<1, V_>(P, T, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
+            case 2: sample_planes<2, V_>(P, T, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
+            case 3: sample_planes<3, V_>(P, T, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
+            case 4: sample_planes<4, V_>(P, T, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
+            case 5: sample_planes<5, 1>(P, T, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; \
+            default: sample_planes<0, V_>(P, T, as, is, c0, base, cn, tid, ncells, s_min, wide_seen); break; }
         PLANES(V)
         #undef PLANES
         __syncthreads();

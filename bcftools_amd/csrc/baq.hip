@@ -8,10 +8,10 @@
 // side), and the backward pass re-forms the even ones from the row below while it forms their posterior (baq_fb_reg).  Wider
 // bands keep both matrices in a scratch buffer [row][cell][read] (baq_fb_scratch).  All arithmetic is fp64 in the
 // reference's operation order, so state / posterior quality, and therefore the new base qualities, are identical to
-// the CPU's.  The host half (window, band, 2-bit reference) is a few integer operations per read.
+// the CPU's.  Window, band and band class of a read are formed on the device too (baq_prep_kernel); the host side is one core
+// (baq_core) behind two fronts, bcfgpu_pool_baq for the pool in HBM and bcfgpu_baq for reads handed over as host pointers.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <vector>
 #include <algorithm>
 #include <type_traits>
 #include <cstring>
@@ -845,7 +845,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BAQ_WAVES(BW
     baq_cap(P, j, iqual, state, q, left, pst, qout, zout);
 }
 
-// ---- the same stage on the pool bcfgpu_pool_upload left in HBM: the host half above as a kernel ----
+// ---- the preparation: realn.c's window and band per read ----
 // One lane per read: the window and band of realn.c; the read's job goes to the list of its band class (class 0 = the
 // register-row kernel's band, class 1 = wider), reads that BAQ leaves alone get ret = -1 and keep their qualities.
 struct BaqPrepParams {
@@ -976,174 +976,36 @@ __global__ __launch_bounds__(256) void baq_ref4_kernel(const char *ref, size_t n
 
 using namespace bcfgpu;
 
-#define BQ_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return bcfgpu_set_error(BCFGPU_E_HIP, #call); } } while (0)
+#define BQ_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
 
 // the scratch class: BAQ_WIDE_LANES reads a wavefront; the working rows in LDS when two rows of the class's widest band fit (bands
 // to about 200), else every cell through the scratch matrices
 template <int BWM>          // 0: the wide class, -BAQ_MID_LANES: bands up to BAQ_BWM3
-static void launch_baq_wide(BaqParams P, hipStream_t st)
+static hipError_t launch_baq_wide(BaqParams P, hipStream_t st)
 {
     constexpr int LANES = BWM == 0 ? BAQ_WIDE_LANES : -BWM;
     // three rows of the class's widest band (two working rows, the forward row of the posterior) and the window's bases: a window is
     // at most the read and its band long (realn.c trims it to that)
     const size_t lds = 3 * (size_t)P.ncell * LANES * sizeof(double) + ((size_t)P.max_lq + (size_t)P.ncell / 6 + 16) * LANES;
     P.lds_rows = lds <= 150 * 1024 ? 1 : 0;
-    if (P.lds_rows && lds > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(baq_kernel<BWM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (P.lds_rows && lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(baq_kernel<BWM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(baq_kernel<BWM>, dim3((P.n_jobs + LANES - 1) / LANES), dim3(64), P.lds_rows ? lds : 0, st, P);
+    return hipSuccess;
 }
 
-extern "C" int bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const char *ref, int32_t ref_len, int flag,
-                          uint8_t *qual_out, uint8_t *zq_out, int32_t *ret)
+// sam_prob_realn on every read of D, reads in HBM: the context's pool (bcfgpu_pool_baq) or the uploaded view of the caller's reads
+// (bcfgpu_baq).  The new qualities go to d_qo, the ZQ bytes to d_zo ([D.n_bases] each), which reads have them to d_has_zq and
+// sam_prob_realn's return value to d_ret ([D.n_reads] each): device buffers of the caller's, none of them D's.  The host part:
+// the contig's length, one wait for the job counts (they size the scratch and the reference slice to upload), launches.  All of
+// it is queued on `stream` when the call returns; `ref` is the caller's again.
+static int baq_core(const char *who, bcfgpu_ctx *ctx, hipStream_t stream, const float *d_q2p, const DevPool &D, const char *ref, int32_t ref_len,
+                    int flag, uint8_t *d_qo, uint8_t *d_zo, uint8_t *d_has_zq, int32_t *d_ret)
 {
-    if (!ctx || !rd || !ref || !qual_out || !zq_out || !ret || rd->n_reads < 0)
-        return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_baq: bad arguments");
-    hipStream_t stream = nullptr;
-    const float *d_q2p = nullptr;
-    if (bcfgpu_internal_device(ctx, &stream, &d_q2p)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_baq: bad context");
-    const int n = rd->n_reads;
-    if (n == 0) return BCFGPU_OK;
-    static const uint8_t nt4[256] = {
-#define N4 4,4,4,4,4,4,4,4,4,4,4,4,4,4,4,4
-        N4,N4,N4,N4,
-        4,0,4,1,4,4,4,2,4,4,4,4,4,4,4,4, 4,4,4,4,3,4,4,4,4,4,4,4,4,4,4,4,
-        4,0,4,1,4,4,4,2,4,4,4,4,4,4,4,4, 4,4,4,4,3,4,4,4,4,4,4,4,4,4,4,4,
-        N4,N4,N4,N4,N4,N4,N4,N4
-#undef N4
-    };
-    // ---- host half: window and band of every read (realn.c), 0..4 codes of the window ----
-    std::vector<BaqJob> jobs(n);
-    std::vector<uint8_t> tref;
-    size_t nbase = 0, ncig = 0;
-    int max_lq = 1;
-    for (int r = 0; r < n; ++r) {
-        BaqJob &j = jobs[r];
-        const int l_qseq = rd->r_lq[r], pos = rd->r_pos[r];
-        const uint32_t *cigar = rd->cig + rd->r_cig_off[r];
-        j.seq_off = (uint32_t)rd->r_seq_off[r]; j.cig_off = (uint32_t)rd->r_cig_off[r];
-        j.l_query = l_qseq; j.n_cigar = rd->r_ncig[r]; j.pos = pos; j.ret = -1; j.l_ref = 0; j.bw = 0; j.xb = 0; j.ref_off = 0;
-        if ((size_t)j.seq_off + l_qseq > nbase) nbase = (size_t)j.seq_off + l_qseq;
-        if ((size_t)j.cig_off + j.n_cigar > ncig) ncig = (size_t)j.cig_off + j.n_cigar;
-        if (l_qseq > max_lq) max_lq = l_qseq;
-        ret[r] = -1;
-        if (l_qseq == 0 || rd->qual[j.seq_off] == 0xff || (rd->r_flag[r] & 4)) continue;
-        int x = pos, y = 0, yb = -1, ye = -1, xb = -1, xe = -1;
-        bool has_n = false;
-        for (int k = 0; k < j.n_cigar; ++k) {
-            const int op = cigar[k] & 0xf, l = (int)(cigar[k] >> 4);
-            if (op == 0 || op == 7 || op == 8) {
-                if (yb < 0) yb = y;
-                if (xb < 0) xb = x;
-                ye = y + l; xe = x + l;
-                x += l; y += l;
-            } else if (op == 4 || op == 1) y += l;
-            else if (op == 2) x += l;
-            else if (op == 3) { has_n = true; break; }
-        }
-        if (has_n || xb == -1) continue;
-        int bw = 7;
-        if (std::abs((xe - xb) - (ye - yb)) > bw) bw = std::abs((xe - xb) - (ye - yb)) + 3;
-        xb -= yb + bw / 2; if (xb < 0) xb = 0;
-        xe += l_qseq - ye + bw / 2;
-        if (xe - xb - l_qseq > bw) { xb += (xe - xb - l_qseq - bw) / 2; xe -= (xe - xb - l_qseq - bw) / 2; }
-        j.ref_off = (uint32_t)tref.size();
-        int k;
-        for (k = xb; k < xe && k < ref_len && ref[k]; ++k) tref.push_back(nt4[(uint8_t)ref[k]]);
-        xe = k;
-        j.l_ref = xe - xb; j.bw = bw; j.xb = xb; j.ret = 0;
-        ret[r] = 0;
-    }
-    if (tref.size() >> 32) return bcfgpu_set_error(BCFGPU_E_RANGE, "bcfgpu_baq: pool too large, use fewer reads per call");
-    // band classes: class 0 = bands that fit the register-row kernel (the default band of 7), class 1 = wide bands
-    // (long indels), run separately with both matrices in scratch and their own row width
-    auto eff_bw = [](const BaqJob &j) { int b = j.l_ref > j.l_query ? j.l_ref : j.l_query; if (b > j.bw) b = j.bw;
-                                        if (b < std::abs(j.l_ref - j.l_query)) b = std::abs(j.l_ref - j.l_query); return b; };
-    std::vector<BaqJob> cls[4];
-    int cls_bw[4] = {1, 1, 1, 1};
-    for (const BaqJob &j : jobs) {
-        const int b = j.ret < 0 ? 1 : eff_bw(j), c = b <= BAQ_BWM ? 0 : b <= BAQ_BWM2 ? 1 : b <= BAQ_BWM3 ? 3 : 2;
-        cls[c].push_back(j);
-        if (b > cls_bw[c]) cls_bw[c] = b;
-    }
-
-    // ---- device half ----
-    // grow-only workspaces of the context: GiB-sized scratch is not reallocated per call
-    void *d_jobs = nullptr, *d_F = nullptr, *d_B = nullptr, *d_S = nullptr;
-    auto cleanup = [&]() {};
-    void *d_tref = bcfgpu_internal_ws(ctx, WS_BAQ_TREF, tref.size() + 16), *d_seq = bcfgpu_internal_ws(ctx, WS_BAQ_SEQ, nbase + 16),
-         *d_qual = bcfgpu_internal_ws(ctx, WS_BAQ_QUAL, nbase + 16), *d_cig = bcfgpu_internal_ws(ctx, WS_BAQ_CIG, (ncig + 4) * 4),
-         *d_state = bcfgpu_internal_ws(ctx, WS_BAQ_STATE, (nbase + 4) * 4), *d_q = bcfgpu_internal_ws(ctx, WS_BAQ_Q, nbase + 16),
-         *d_tmp = bcfgpu_internal_ws(ctx, WS_BAQ_TMP, 2 * nbase + 16), *d_qo = bcfgpu_internal_ws(ctx, WS_BAQ_QUAL_OUT, nbase + 16),
-         *d_zo = bcfgpu_internal_ws(ctx, WS_BAQ_ZQ_OUT, nbase + 16);
-    if (!d_tref || !d_seq || !d_qual || !d_cig || !d_state || !d_q || !d_tmp || !d_qo || !d_zo)
-        return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_baq: device workspace");
-    BQ_CHK(hipMemcpyAsync(d_tref, tref.data(), tref.size(), hipMemcpyHostToDevice, stream));
-    BQ_CHK(hipMemcpyAsync(d_seq, rd->seq16, nbase, hipMemcpyHostToDevice, stream));
-    BQ_CHK(hipMemcpyAsync(d_qual, rd->qual, nbase, hipMemcpyHostToDevice, stream));
-    BQ_CHK(hipMemcpyAsync(d_cig, rd->cig, ncig * 4, hipMemcpyHostToDevice, stream));
-    BQ_CHK(hipMemsetAsync(d_zo, 0, nbase, stream));
-    BQ_CHK(hipMemcpyAsync(d_qo, rd->qual, nbase, hipMemcpyHostToDevice, stream));      // bases no job covers keep their quality
-    BaqParams P{};
-    P.flag = flag; P.max_lq = max_lq;
-    P.tref = (const uint8_t*)d_tref; P.seq16 = (const uint8_t*)d_seq; P.qual = (const uint8_t*)d_qual; P.cig = (const uint32_t*)d_cig;
-    P.q2p = d_q2p; P.state = (int32_t*)d_state; P.q = (uint8_t*)d_q; P.tmp = (uint8_t*)d_tmp;
-    P.qual_out = (uint8_t*)d_qo; P.zq_out = (uint8_t*)d_zo;
-    // (the wide class in descending order of the band, as baq_sort_wide_kernel leaves it in the pool form)
-    std::stable_sort(cls[2].begin(), cls[2].end(), [&](const BaqJob &x, const BaqJob &y) { return eff_bw(x) > eff_bw(y); });
-    for (int c = 0; c < 4; ++c) {
-        const size_t nj = cls[c].size();
-        if (!nj) continue;
-        const bool reg = c < 2;
-        P.ncell = reg ? 2 * (2 * (c ? BAQ_BWM2 : BAQ_BWM) + 3) : 3 * (2 * cls_bw[c] + 1) + 6;       // doubles per matrix row
-        const size_t per_mat = (size_t)(reg ? BAQ_ROWS_KEPT(max_lq) : max_lq + 2) * P.ncell * sizeof(double);    // one matrix of one read (register-row classes: the odd rows)
-        const size_t per_job = reg ? per_mat : 2 * per_mat;
-        size_t chunk = ((size_t)2 << 30) / per_job;
-        chunk = chunk < 64 ? 64 : (chunk & ~(size_t)63);
-        if (chunk > nj) chunk = (nj + 63) & ~(size_t)63;
-        P.stride = chunk;
-        d_jobs = bcfgpu_internal_ws(ctx, WS_BAQ_JOBS, nj * sizeof(BaqJob));
-        d_F = bcfgpu_internal_ws(ctx, WS_BAQ_F, per_mat * chunk);
-        d_B = reg ? nullptr : bcfgpu_internal_ws(ctx, WS_BAQ_B, per_mat * chunk);
-        d_S = bcfgpu_internal_ws(ctx, WS_BAQ_S, (size_t)(max_lq + 2) * chunk * sizeof(double));
-        if (!d_jobs || !d_F || (!reg && !d_B) || !d_S) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_baq: device workspace");
-        if (reg) {                                                   // state / posterior quality / left maxima, a wavefront's reads side by side
-            const size_t wn = chunk * (size_t)max_lq;
-            uint8_t *d_w = (uint8_t*)bcfgpu_internal_ws(ctx, WS_BAQ_W, wn * 6 + 64);
-            if (!d_w) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_baq: device workspace");
-            P.wstate = (int32_t*)d_w; P.wq = d_w + wn * 4; P.wleft = d_w + wn * 5;
-        }
-        BQ_CHK(hipMemcpyAsync(d_jobs, cls[c].data(), nj * sizeof(BaqJob), hipMemcpyHostToDevice, stream));
-        P.F = (double*)d_F; P.B = (double*)d_B; P.S = (double*)d_S;
-        for (size_t j0 = 0; j0 < nj; j0 += chunk) {
-            P.n_jobs = (int)(nj - j0 < chunk ? nj - j0 : chunk);
-            P.jobs = (const BaqJob*)d_jobs + j0;
-            if (c == 0)      hipLaunchKernelGGL(baq_kernel<BAQ_BWM>, dim3((P.n_jobs + 63) / 64), dim3(64), 0, stream, P);
-            else if (c == 1) hipLaunchKernelGGL(baq_kernel<BAQ_BWM2>, dim3((P.n_jobs + 63) / 64), dim3(64), 0, stream, P);
-            else if (c == 3) launch_baq_wide<-BAQ_MID_LANES>(P, stream);
-            else             launch_baq_wide<0>(P, stream);
-        }
-        BQ_CHK(hipGetLastError());
-    }
-    BQ_CHK(hipMemcpyAsync(qual_out, d_qo, nbase, hipMemcpyDeviceToHost, stream));
-    BQ_CHK(hipMemcpyAsync(zq_out, d_zo, nbase, hipMemcpyDeviceToHost, stream));
-    BQ_CHK(hipStreamSynchronize(stream));
-    return BCFGPU_OK;
-}
-
-// sam_prob_realn on every read of the pool in HBM: the pool's qualities become the new ones, the ZQ bytes stay there for
-// bcfgpu_gap_prep_tile.  The host part: the contig's length, one wait for the job counts (they size the scratch and the
-// reference slice to upload), launches.
-extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len, int flag, int32_t *ret)
-{
-    if (!ctx || !ref || ref_len < 0) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_baq: bad arguments");
-    hipStream_t stream = nullptr;
-    const float *d_q2p = nullptr;
-    if (bcfgpu_internal_device(ctx, &stream, &d_q2p)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_baq: bad context");
-    DevPool &D = *bcfgpu_internal_pool_state(ctx);
-    if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_baq: no read pool on this context (bcfgpu_pool_upload)");
+    auto nomem = [&]() { return bcfgpu_set_error(BCFGPU_E_NOMEM, who, "device workspace"); };
     const int n = D.n_reads;
-    if (n == 0) return BCFGPU_OK;
-    auto cleanup = [&]() {};
     const size_t nbase = D.n_bases;
     BaqPrepParams Q{};
     Q.D = D; Q.ref_len = (int)strnlen(ref, (size_t)ref_len);
@@ -1152,15 +1014,10 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     Q.jobs2 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS2, (size_t)n * sizeof(BaqJob) + 64);
     Q.jobs3 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS3, (size_t)n * sizeof(BaqJob) + 64);
     Q.counts = (int*)bcfgpu_internal_ws(ctx, WS_PBAQ_COUNTS, 64);
-    Q.ret = (int32_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_RET, (size_t)n * 4 + 64);
-    Q.has_zq = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_HAS_ZQ, (size_t)n + 64);
-    const WsSlot qo_slot = D.qual_slot == WS_PBAQ_QUAL_A ? WS_PBAQ_QUAL_B : WS_PBAQ_QUAL_A;    // not the buffer the pool's qualities are in now
-    uint8_t *d_qo = (uint8_t*)bcfgpu_internal_ws(ctx, qo_slot, nbase + 64);
-    uint8_t *d_zo = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_ZQ, nbase + 64);
+    Q.ret = d_ret; Q.has_zq = d_has_zq;
     void *d_state = bcfgpu_internal_ws(ctx, WS_PBAQ_STATE, (nbase + 4) * 4), *d_q = bcfgpu_internal_ws(ctx, WS_PBAQ_Q, nbase + 16),
          *d_tmp = bcfgpu_internal_ws(ctx, WS_PBAQ_TMP, 2 * nbase + 16);
-    if (!Q.jobs0 || !Q.jobs1 || !Q.jobs2 || !Q.jobs3 || !Q.counts || !Q.ret || !Q.has_zq || !d_qo || !d_zo || !d_state || !d_q || !d_tmp)
-        return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
+    if (!Q.jobs0 || !Q.jobs1 || !Q.jobs2 || !Q.jobs3 || !Q.counts || !d_state || !d_q || !d_tmp) return nomem();
     const int init[8] = {0, 0, 1, 1, INT32_MAX, 0, 0, 0};
     int counts[8];
     BQ_CHK(hipMemcpyAsync(Q.counts, init, sizeof init, hipMemcpyHostToDevice, stream));
@@ -1173,11 +1030,11 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     const int lo = counts[4] == INT32_MAX ? 0 : counts[4], hi = std::max(counts[5], lo);
     char *d_refc = (char*)bcfgpu_internal_ws(ctx, WS_PBAQ_REF, (size_t)(hi - lo) + 64);
     uint8_t *d_ref4 = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_REF4, (size_t)(hi - lo) + 64);
-    if (!d_refc || !d_ref4) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
+    if (!d_refc || !d_ref4) return nomem();
     if (hi > lo) {
         // (through the context's page-locked staging buffer: the call returns with the copy in flight, `ref` is the caller's)
         char *h_ref = (char*)bcfgpu_internal_pinned(ctx, PIN_PBAQ_REF, (size_t)(hi - lo));
-        if (!h_ref) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: host staging");
+        if (!h_ref) return bcfgpu_set_error(BCFGPU_E_NOMEM, who, "host staging");
         std::memcpy(h_ref, ref + lo, (size_t)(hi - lo));
         BQ_CHK(hipMemcpyAsync(d_refc, h_ref, (size_t)(hi - lo), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(baq_ref4_kernel, dim3((unsigned)(((size_t)(hi - lo) + 255) / 256)), dim3(256), 0, stream, d_refc, (size_t)(hi - lo), d_ref4);
@@ -1195,11 +1052,11 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     // wavefronts run beside the main class instead of after it -- a launch of 178 wavefronts takes as long as its slowest
     // wavefront, half a millisecond with the chip otherwise idle.
     hipStream_t *side = nullptr; hipEvent_t *sev = nullptr;
-    if (bcfgpu_internal_side(ctx, &side, &sev)) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_baq: side streams");
+    if (bcfgpu_internal_side(ctx, &side, &sev)) return bcfgpu_set_error(BCFGPU_E_HIP, who, "side streams");
     BaqJob *jobs2 = Q.jobs2;                               // the wide class's jobs, sorted by band (before anything else is on the chip:
     if (counts[6] > 0) {                                   // one workgroup, 20 us alone, 15 ms behind a launch that fills it)
         jobs2 = (BaqJob*)bcfgpu_internal_ws(ctx, WS_PBAQ_JOBS2_SORTED, (size_t)counts[6] * sizeof(BaqJob) + 64);
-        if (!jobs2) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
+        if (!jobs2) return nomem();
         hipLaunchKernelGGL(baq_sort_wide_kernel, dim3(1), dim3(1024), 0, stream, Q.jobs2, counts[6], jobs2);
     }
     BQ_CHK(hipEventRecord(sev[0], stream));
@@ -1222,31 +1079,82 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
         P.stride = chunk;
         void *d_F = bcfgpu_internal_ws(ctx, slotF[c], per_mat * chunk), *d_B = reg ? nullptr : bcfgpu_internal_ws(ctx, slotW[c], per_mat * chunk);
         void *d_S = bcfgpu_internal_ws(ctx, slotS[c], (size_t)(P.max_lq + 2) * chunk * sizeof(double));
-        if (!d_F || (!reg && !d_B) || !d_S) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
+        if (!d_F || (!reg && !d_B) || !d_S) return nomem();
         if (reg) {                                                   // state / posterior quality / left maxima, a wavefront's reads side by side
             const size_t wn = chunk * (size_t)P.max_lq;
             uint8_t *d_w = (uint8_t*)bcfgpu_internal_ws(ctx, slotW[c], wn * 6 + 64);
-            if (!d_w) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_baq: device workspace");
+            if (!d_w) return nomem();
             P.wstate = (int32_t*)d_w; P.wq = d_w + wn * 4; P.wleft = d_w + wn * 5;
         }
         P.F = (double*)d_F; P.B = (double*)d_B; P.S = (double*)d_S;
         for (size_t j0 = 0; j0 < nj; j0 += chunk) {
             P.n_jobs = (int)(nj - j0 < chunk ? nj - j0 : chunk);
             P.jobs = (c == 0 ? Q.jobs0 : c == 1 ? Q.jobs1 : c == 2 ? jobs2 : Q.jobs3) + j0;
+            hipError_t e = hipSuccess;
             if (c == 0)      hipLaunchKernelGGL(baq_kernel<BAQ_BWM>, dim3((P.n_jobs + 63) / 64), dim3(64), 0, st, P);
             else if (c == 1) hipLaunchKernelGGL(baq_kernel<BAQ_BWM2>, dim3((P.n_jobs + 63) / 64), dim3(64), 0, st, P);
-            else if (c == 3) launch_baq_wide<-BAQ_MID_LANES>(P, st);
-            else             launch_baq_wide<0>(P, st);
+            else if (c == 3) e = launch_baq_wide<-BAQ_MID_LANES>(P, st);
+            else             e = launch_baq_wide<0>(P, st);
+            if (e != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, who, "hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize)");
         }
         BQ_CHK(hipGetLastError());
     }
     for (int c = 1; c < 4; ++c)
         if (used_side[c]) { BQ_CHK(hipEventRecord(sev[c], side[c - 1])); BQ_CHK(hipStreamWaitEvent(stream, sev[c], 0)); }
-    if (ret) {
-        BQ_CHK(hipMemcpyAsync(ret, Q.ret, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-        BQ_CHK(hipStreamSynchronize(stream));
-    }
-    D.qual = d_qo; D.qual_slot = qo_slot; D.zq = d_zo; D.r_has_zq = Q.has_zq;
     return BCFGPU_OK;
 }
 
+// On the caller's reads: they go up as a view, the results come back.
+extern "C" int bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const char *ref, int32_t ref_len, int flag,
+                          uint8_t *qual_out, uint8_t *zq_out, int32_t *ret)
+{
+    const char *who = "bcfgpu_baq";
+    if (!ctx || !rd || !ref || !qual_out || !zq_out || !ret || rd->n_reads < 0) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad arguments");
+    hipStream_t stream = nullptr;
+    const float *d_q2p = nullptr;
+    if (bcfgpu_internal_device(ctx, &stream, &d_q2p)) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad context");
+    const int n = rd->n_reads;
+    if (n == 0) return BCFGPU_OK;
+    DevPool V{};
+    if (const int rc = pool_view_upload(who, ctx, rd, nullptr, READS_LQ | READS_FLAG, POOL_VIEW, stream, &V)) return rc;
+    // scratch of this call, not the slots the context's pool keeps its BAQ results in
+    const size_t nbase = V.n_bases;
+    uint8_t *d_qo = (uint8_t*)bcfgpu_internal_ws(ctx, WS_BAQ_QUAL_OUT, nbase + 64), *d_zo = (uint8_t*)bcfgpu_internal_ws(ctx, WS_BAQ_ZQ_OUT, nbase + 64);
+    uint8_t *d_has_zq = (uint8_t*)bcfgpu_internal_ws(ctx, WS_BAQ_HAS_ZQ, (size_t)n + 64);
+    int32_t *d_ret = (int32_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_RET, (size_t)n * 4 + 64);
+    int rc = d_qo && d_zo && d_has_zq && d_ret ? BCFGPU_OK : bcfgpu_set_error(BCFGPU_E_NOMEM, who, "device workspace");
+    if (!rc) rc = baq_core(who, ctx, stream, d_q2p, V, ref, std::max(ref_len, 0), flag, d_qo, d_zo, d_has_zq, d_ret);
+    if (!rc && (hipMemcpyAsync(qual_out, d_qo, nbase, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipMemcpyAsync(zq_out, d_zo, nbase, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipMemcpyAsync(ret, d_ret, (size_t)n * 4, hipMemcpyDeviceToHost, stream) != hipSuccess))
+        rc = bcfgpu_set_error(BCFGPU_E_HIP, who, "download");
+    if (hipStreamSynchronize(stream) != hipSuccess && !rc) rc = bcfgpu_set_error(BCFGPU_E_HIP, who, "hipStreamSynchronize");
+    return rc;
+}
+
+// On the pool in HBM: the pool's qualities become the new ones, the ZQ bytes stay there for bcfgpu_gap_prep_tile.
+extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len, int flag, int32_t *ret)
+{
+    const char *who = "bcfgpu_pool_baq";
+    if (!ctx || !ref || ref_len < 0) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad arguments");
+    hipStream_t stream = nullptr;
+    const float *d_q2p = nullptr;
+    if (bcfgpu_internal_device(ctx, &stream, &d_q2p)) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad context");
+    DevPool &D = *bcfgpu_internal_pool_state(ctx);
+    if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, who, "no read pool on this context (bcfgpu_pool_upload)");
+    const int n = D.n_reads;
+    if (n == 0) return BCFGPU_OK;
+    const size_t nbase = D.n_bases;
+    const WsSlot qo_slot = D.qual_slot == WS_PBAQ_QUAL_A ? WS_PBAQ_QUAL_B : WS_PBAQ_QUAL_A;    // not the buffer the pool's qualities are in now
+    uint8_t *d_qo = (uint8_t*)bcfgpu_internal_ws(ctx, qo_slot, nbase + 64), *d_zo = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_ZQ, nbase + 64);
+    uint8_t *d_has_zq = (uint8_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_HAS_ZQ, (size_t)n + 64);
+    int32_t *d_ret = (int32_t*)bcfgpu_internal_ws(ctx, WS_PBAQ_RET, (size_t)n * 4 + 64);
+    if (!d_qo || !d_zo || !d_has_zq || !d_ret) return bcfgpu_set_error(BCFGPU_E_NOMEM, who, "device workspace");
+    if (const int rc = baq_core(who, ctx, stream, d_q2p, D, ref, ref_len, flag, d_qo, d_zo, d_has_zq, d_ret)) return rc;
+    if (ret) {
+        BQ_CHK(hipMemcpyAsync(ret, d_ret, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+        BQ_CHK(hipStreamSynchronize(stream));
+    }
+    D.qual = d_qo; D.qual_slot = qo_slot; D.zq = d_zo; D.r_has_zq = d_has_zq;
+    return BCFGPU_OK;
+}

@@ -8,17 +8,13 @@
 // htslib is not part of the reference tree and no golden of the reference's tests runs `mpileup -C`: the function is
 // restated from htslib's published source and checked against the oracle's restatement only (parity unpinned).
 #include <hip/hip_runtime.h>
-#include <cstring>
-#include <climits>
 #include "ctx.h"
 
 namespace bcfgpu {
 
 struct CapParams {
-    int n_reads, thres;
-    const int32_t *r_pos, *r_lq, *r_ncig, *r_cig_off, *r_seq_off;
-    const uint32_t *cig;
-    const uint8_t *seq16, *qual;
+    int thres;
+    DevPool D;                                  // the reads
     const char *ref; long ref_lo, ref_hi;       // the slice of the contig the reads can touch; outside it: past the end
     int32_t *out;
 };
@@ -40,13 +36,14 @@ __device__ __forceinline__ int cap_nt16_of(char c)
 __global__ __launch_bounds__(256) void cap_mapq_kernel(const CapParams P)
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= P.n_reads) return;
-    const uint32_t *cigar = P.cig + P.r_cig_off[r];
-    const uint8_t *seq = P.seq16 + P.r_seq_off[r], *qual = P.qual + P.r_seq_off[r];
-    const int ncig = P.r_ncig[r];
+    const DevPool &D = P.D;
+    if (r >= D.n_reads) return;
+    const uint32_t *cigar = D.cig + D.r_cig_off[r];
+    const uint8_t *seq = D.seq16 + D.r_seq_off[r], *qual = D.qual + D.r_seq_off[r];
+    const int ncig = D.r_ncig[r];
     const int thres = P.thres < 0 ? 40 : P.thres;
     int mm = 0, q = 0, len = 0, clip_q = 0, y = 0;
-    long x = P.r_pos[r];
+    long x = D.r_pos[r];
     auto past_end = [&](long p) { return p >= P.ref_hi || p < P.ref_lo || P.ref[p - P.ref_lo] == '\0'; };
     for (int i = 0; i < ncig; ++i) {
         const int l = (int)(cigar[i] >> 4), op = (int)(cigar[i] & 0xf);
@@ -101,80 +98,55 @@ __global__ __launch_bounds__(256) void cap_apply_kernel(int n, const int32_t *ca
 }
 }
 
-// The same on the pool in HBM (after bcfgpu_pool_baq): the caps come back for the caller's filters (cap < 0: the read is
-// dropped, mpileup.c:237), the pool's mapping qualities are lowered in place.
-extern "C" int bcfgpu_pool_cap_mapq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len, int32_t thres, int32_t *cap)
+// sam_cap_mapq on reads in HBM, the pool (bcfgpu_pool_cap_mapq) or the uploaded view of the caller's reads (bcfgpu_cap_mapq): the
+// caps come back to `cap` (HOST); apply: the reads' mapping qualities (D.r_mapq) are lowered to them in place.
+static int cap_core(const char *who, bcfgpu_ctx *ctx, hipStream_t st, DevPool &D, const char *ref, int32_t ref_len, int32_t thres, int32_t *cap, bool apply)
 {
-    if (!ctx || !cap || (ref_len > 0 && !ref)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_cap_mapq: bad arguments");
-    hipStream_t st = nullptr;
-    if (bcfgpu_internal_device(ctx, &st, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_cap_mapq: bad context");
-    const DevPool &D = *bcfgpu_internal_pool_state(ctx);
-    if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_pool_cap_mapq: no read pool on this context (bcfgpu_pool_upload)");
     const int n = D.n_reads;
     if (!n) return BCFGPU_OK;
     int lo = 0, hi = 0;
-    if (bcfgpu_internal_pool_extent(ctx, &lo, &hi)) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_cap_mapq: pool extent");
+    if (bcfgpu_internal_pool_extent(ctx, D, &lo, &hi)) return bcfgpu_set_error(BCFGPU_E_HIP, who, "pool extent");
     if (lo < 0) lo = 0;
     if (hi > ref_len) hi = ref_len;
     if (hi < lo) hi = lo;
     CapParams P{};
-    P.n_reads = n; P.thres = thres;
-    P.r_pos = D.r_pos; P.r_lq = D.r_lq; P.r_ncig = D.r_ncig; P.r_cig_off = D.r_cig_off; P.r_seq_off = D.r_seq_off;
-    P.cig = D.cig; P.seq16 = D.seq16; P.qual = D.qual;
-    char *d_ref = (char*)bcfgpu_internal_ws(ctx, WS_PCAPQ_REF, (size_t)(hi - lo) + 64);
+    P.thres = thres; P.D = D;
+    char *d_ref = (char*)ws_upload(ctx, WS_PCAPQ_REF, ref + lo, (size_t)(hi - lo), 64, st);
     P.out = (int32_t*)bcfgpu_internal_ws(ctx, WS_PCAPQ_OUT, (size_t)n * 4 + 64);
-    if (!d_ref || !P.out) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_pool_cap_mapq: device workspace");
-    if (hi > lo && hipMemcpyAsync(d_ref, ref + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, st) != hipSuccess)
-        return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_cap_mapq: upload");
+    if (!d_ref || !P.out) return bcfgpu_set_error(BCFGPU_E_NOMEM, who, "device workspace or upload");
     P.ref = d_ref; P.ref_lo = lo; P.ref_hi = hi;
     hipLaunchKernelGGL(cap_mapq_kernel, dim3((n + 255) / 256), dim3(256), 0, st, P);
-    hipLaunchKernelGGL(cap_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, (const int32_t*)P.out, D.r_mapq);
-    if (hipGetLastError() != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_cap_mapq: launch");
+    if (apply) hipLaunchKernelGGL(cap_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, (const int32_t*)P.out, D.r_mapq);
+    if (hipGetLastError() != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, who, "launch");
     if (hipMemcpyAsync(cap, P.out, (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_pool_cap_mapq: download");
+        return bcfgpu_set_error(BCFGPU_E_HIP, who, "download");
     return BCFGPU_OK;
 }
 
+// On the pool in HBM (after bcfgpu_pool_baq): the caps come back for the caller's filters (cap < 0: the read is dropped,
+// mpileup.c:237), the pool's mapping qualities are lowered in place.
+extern "C" int bcfgpu_pool_cap_mapq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len, int32_t thres, int32_t *cap)
+{
+    const char *who = "bcfgpu_pool_cap_mapq";
+    if (!ctx || !cap || (ref_len > 0 && !ref)) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad arguments");
+    hipStream_t st = nullptr;
+    if (bcfgpu_internal_device(ctx, &st, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad context");
+    DevPool &D = *bcfgpu_internal_pool_state(ctx);
+    if (!D.valid) return bcfgpu_set_error(BCFGPU_E_ARG, who, "no read pool on this context (bcfgpu_pool_upload)");
+    return cap_core(who, ctx, st, D, ref, ref_len, thres, cap, true);
+}
+
+// On the caller's reads: the caps only (the caller lowers its mapping qualities itself).
 extern "C" int bcfgpu_cap_mapq(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const char *ref, int32_t ref_len, int32_t thres, int32_t *cap)
 {
-    if (!ctx || !rd || !cap || rd->n_reads < 0 || (ref_len > 0 && !ref)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_cap_mapq: bad arguments");
+    const char *who = "bcfgpu_cap_mapq";
+    if (!ctx || !rd || !cap || rd->n_reads < 0 || (ref_len > 0 && !ref)) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad arguments");
     hipStream_t st = nullptr;
-    if (bcfgpu_internal_device(ctx, &st, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_cap_mapq: bad context");
-    const int n = rd->n_reads;
-    if (!n) return BCFGPU_OK;
-    size_t nbase = 0, ncig = 0;
-    long lo = LONG_MAX, hi = 0;
-    for (int r = 0; r < n; ++r) {
-        const size_t e = (size_t)rd->r_seq_off[r] + rd->r_lq[r], c = (size_t)rd->r_cig_off[r] + rd->r_ncig[r];
-        if (e > nbase) nbase = e;
-        if (c > ncig) ncig = c;
-        long x = rd->r_pos[r];
-        if (x < lo) lo = x;
-        for (int k = 0; k < rd->r_ncig[r]; ++k) { const uint32_t cg = rd->cig[rd->r_cig_off[r] + k]; const int op = cg & 15; if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) x += cg >> 4; }
-        if (x > hi) hi = x;
-    }
-    if (lo < 0) lo = 0;
-    if (hi > ref_len) hi = ref_len;
-    if (hi < lo) hi = lo;
-    #define CQ_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
-    CapParams P{};
-    P.n_reads = n; P.thres = thres;
-    P.r_pos = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_POS, rd->r_pos, (size_t)n * 4, 16, st);
-    P.r_lq = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_LQ, rd->r_lq, (size_t)n * 4, 16, st);
-    P.r_ncig = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_NCIG, rd->r_ncig, (size_t)n * 4, 16, st);
-    P.r_cig_off = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_CIG_OFF, rd->r_cig_off, (size_t)n * 4, 16, st);
-    P.r_seq_off = (const int32_t*)ws_upload(ctx, WS_CAPQ_R_SEQ_OFF, rd->r_seq_off, (size_t)n * 4, 16, st);
-    P.cig = (const uint32_t*)ws_upload(ctx, WS_CAPQ_CIG, rd->cig, ncig * 4, 16, st);
-    P.seq16 = (const uint8_t*)ws_upload(ctx, WS_CAPQ_SEQ, rd->seq16, nbase, 16, st);
-    P.qual = (const uint8_t*)ws_upload(ctx, WS_CAPQ_QUAL, rd->qual, nbase, 16, st);
-    P.ref = (const char*)ws_upload(ctx, WS_CAPQ_REF, ref + lo, (size_t)(hi - lo), 16, st); P.ref_lo = lo; P.ref_hi = hi;
-    P.out = (int32_t*)bcfgpu_internal_ws(ctx, WS_CAPQ_OUT, (size_t)n * 4 + 16);
-    if (!P.r_pos || !P.r_lq || !P.r_ncig || !P.r_cig_off || !P.r_seq_off || !P.cig || !P.seq16 || !P.qual || !P.ref || !P.out)
-        return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_cap_mapq: device workspace");
-    hipLaunchKernelGGL(cap_mapq_kernel, dim3((n + 255) / 256), dim3(256), 0, st, P);
-    CQ_CHK(hipGetLastError());
-    CQ_CHK(hipMemcpyAsync(cap, P.out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CQ_CHK(hipStreamSynchronize(st));
-    #undef CQ_CHK
-    return BCFGPU_OK;
+    if (bcfgpu_internal_device(ctx, &st, nullptr)) return bcfgpu_set_error(BCFGPU_E_ARG, who, "bad context");
+    if (!rd->n_reads) return BCFGPU_OK;
+    DevPool V{};
+    int rc = pool_view_upload(who, ctx, rd, nullptr, 0, POOL_VIEW, st, &V);
+    if (!rc) rc = cap_core(who, ctx, st, V, ref, ref_len, thres, cap, false);
+    if (rc) hipStreamSynchronize(st);                           // (the copies read the caller's arrays)
+    return rc;
 }

@@ -1,6 +1,6 @@
 // ctx.h -- the context's internal interface, for the stages in their own translation units: the workspace slots and the
-// accessors of bcfgpu_ctx.  Defined in api.hip, except bcfgpu_internal_pool_extent (pileup.hip) and bcfgpu_internal_gap_core
-// (gap_prep.hip).  C++ linkage: none of it is part of the C-ABI of include/bcfgpu.h.
+// accessors of bcfgpu_ctx.  Defined in api.hip, except pool_view_upload and bcfgpu_internal_pool_extent (pileup.hip) and
+// bcfgpu_internal_gap_core (gap_prep.hip).  C++ linkage: none of it is part of the C-ABI of include/bcfgpu.h.
 #pragma once
 #include "kernels.h"
 
@@ -12,16 +12,13 @@ namespace bcfgpu {
 // "Kept" marks the slots whose contents a later entry point reads: they are listed in WS_KEPT below, and no other use may
 // share their numbers (tests/test_ctx_slots.py checks both against this enum).
 enum WsSlot : int {
-    // bcfgpu_baq (reads from the host): scratch for one call
-    WS_BAQ_JOBS = 0, WS_BAQ_B = 1, WS_BAQ_S = 2, WS_BAQ_F = 4, WS_BAQ_W = 5,
-    WS_BAQ_TREF = 7, WS_BAQ_SEQ = 8, WS_BAQ_QUAL = 9, WS_BAQ_CIG = 10, WS_BAQ_STATE = 11, WS_BAQ_Q = 12, WS_BAQ_TMP = 13,
-    WS_BAQ_QUAL_OUT = 14, WS_BAQ_ZQ_OUT = 15,
-    // bcfgpu_overlap_tweak: scratch for one call
-    WS_OVL_PAIR_A = 7, WS_OVL_PAIR_B = 8, WS_OVL_R_POS = 9, WS_OVL_R_NCIG = 10, WS_OVL_R_CIG_OFF = 11, WS_OVL_R_SEQ_OFF = 12,
-    WS_OVL_CIG = 13, WS_OVL_SEQ = 14, WS_OVL_QUAL = 15,
-    // bcfgpu_cap_mapq: scratch for one call
-    WS_CAPQ_R_POS = 0, WS_CAPQ_R_LQ = 1, WS_CAPQ_R_NCIG = 2, WS_CAPQ_R_CIG_OFF = 3, WS_CAPQ_R_SEQ_OFF = 4, WS_CAPQ_CIG = 5,
-    WS_CAPQ_SEQ = 6, WS_CAPQ_QUAL = 7, WS_CAPQ_REF = 8, WS_CAPQ_OUT = 9,
+    // the uploaded view of a bcfgpu_reads (pool_view_upload, the PoolSlots set POOL_VIEW below): scratch for one call of
+    // bcfgpu_baq, bcfgpu_cap_mapq, bcfgpu_overlap_tweak or bcfgpu_gap_prep; bcfgpu_gap_prep_tile forms its per-read arrays and
+    // uploads the caller's ZQ bytes there
+    WS_VIEW_R_MAPQ = 38, WS_VIEW_R_POS = 40, WS_VIEW_R_LQ = 41, WS_VIEW_R_FLAG = 42, WS_VIEW_R_NCIG = 43, WS_VIEW_R_CIG_OFF = 44,
+    WS_VIEW_R_SEQ_OFF = 45, WS_VIEW_CIG = 46, WS_VIEW_SEQ16 = 47, WS_VIEW_QUAL = 48, WS_VIEW_ZQ = 49, WS_VIEW_HAS_ZQ = 50,
+    // bcfgpu_baq: what baq_core writes for it (bcfgpu_pool_baq hands the core the pool's kept slots instead): scratch for one call
+    WS_BAQ_QUAL_OUT = 14, WS_BAQ_ZQ_OUT = 15, WS_BAQ_HAS_ZQ = 8,
 
     // the read pool (pileup.hip pool_upload_impl).  Kept: DevPool, read by the pool stages below and bcfgpu_pool_pileup
     WS_POOL_CIG = 27, WS_POOL_SEQ16 = 28, WS_POOL_QUAL = 29,
@@ -30,14 +27,14 @@ enum WsSlot : int {
     //   the upload's packed inputs: scratch for one call
     WS_POOL_SEQ4 = 111, WS_POOL_QUAL4 = 112, WS_POOL_RECS = 128, WS_POOL_SCAN_TMP = 129,
     WS_POOL_KEEP = 114,                 // kept: DevPool::keep (bcfgpu_pool_keep), read by bcfgpu_pool_pileup
-    WS_POOL_EXTENT = 122,               // bcfgpu_internal_pool_extent: scratch for one call
+    WS_POOL_EXTENT = 122,               // bcfgpu_internal_pool_extent (of the pool or of a view): scratch for one call
     //   the second set of the pool's arrays.  Kept: the pool bcfgpu_pool_stage brings up lands in the set the context's pool
     //   is not in, and bcfgpu_pool_adopt makes that set the pool's (PoolStage::set says which one DevPool points into)
     WS_POOL_B_CIG = 154, WS_POOL_B_SEQ16 = 155, WS_POOL_B_QUAL = 156, WS_POOL_B_R_POS = 157, WS_POOL_B_R_LQ = 158,
     WS_POOL_B_R_FLAG = 159, WS_POOL_B_R_NCIG = 160, WS_POOL_B_R_CIG_OFF = 161, WS_POOL_B_R_SEQ_OFF = 162, WS_POOL_B_R_MAPQ = 163,
     //   a staged pool's packed inputs.  Kept from bcfgpu_pool_stage to bcfgpu_pool_adopt, which expands them
     WS_POOL_STAGE_SEQ4 = 164, WS_POOL_STAGE_QUAL4 = 165, WS_POOL_STAGE_RECS = 166,
-    // bcfgpu_pool_baq: scratch for one call
+    // baq_core (bcfgpu_pool_baq and, on a view, bcfgpu_baq): scratch for one call
     WS_PBAQ_JOBS0 = 0, WS_PBAQ_JOBS1 = 3, WS_PBAQ_JOBS2 = 127, WS_PBAQ_JOBS3 = 135, WS_PBAQ_JOBS2_SORTED = 128,
     WS_PBAQ_COUNTS = 115, WS_PBAQ_RET = 116, WS_PBAQ_STATE = 11, WS_PBAQ_Q = 12, WS_PBAQ_TMP = 13,
     WS_PBAQ_REF = 121, WS_PBAQ_REF4 = 7,
@@ -47,7 +44,7 @@ enum WsSlot : int {
     //   kept: the pool's new qualities (DevPool::qual; the call writes to the one of the two it is not in), ZQ and which reads
     //   have it (DevPool::zq, r_has_zq), read by the pool stages after it, bcfgpu_pool_download and bcfgpu_gap_prep_tile
     WS_PBAQ_QUAL_A = 118, WS_PBAQ_QUAL_B = 119, WS_PBAQ_ZQ = 120, WS_PBAQ_HAS_ZQ = 117,
-    // bcfgpu_pool_overlap_tweak, bcfgpu_pool_cap_mapq: scratch for one call
+    // overlap_core, cap_core (the pool forms and, on a view, bcfgpu_overlap_tweak / bcfgpu_cap_mapq): scratch for one call
     WS_POVL_PAIR_A = 123, WS_POVL_PAIR_B = 124,
     WS_PCAPQ_REF = 125, WS_PCAPQ_OUT = 126,
 
@@ -67,10 +64,9 @@ enum WsSlot : int {
     //   scratch for one call
     WS_GTILE_COLS = 21, WS_GTILE_N_KEPT = 143, WS_GTILE_SEL = 153, WS_GTILE_SCAN_TMP = 23, WS_GTILE_ENT = 24, WS_GTILE_LIVE = 130,
 
-    // bcfgpu_gap_prep and bcfgpu_gap_prep_tile: scratch for one call.  The inputs as bcfgpu_gap_prep uploads them (those
-    // bcfgpu_gap_prep_tile forms or uploads itself: the per-read arrays 40-45, ZQ, the positions, the reference slice, p->aux)
-    WS_GAP_R_POS = 40, WS_GAP_R_LQ = 41, WS_GAP_R_FLAG = 42, WS_GAP_R_NCIG = 43, WS_GAP_R_CIG_OFF = 44, WS_GAP_R_SEQ_OFF = 45,
-    WS_GAP_CIG = 46, WS_GAP_SEQ = 47, WS_GAP_QUAL = 48, WS_GAP_ZQ = 49, WS_GAP_HAS_ZQ = 50, WS_GAP_POS = 51, WS_GAP_SMPL_OFF = 52,
+    // bcfgpu_gap_prep and bcfgpu_gap_prep_tile: scratch for one call.  The inputs beside the reads (the view above) as
+    // bcfgpu_gap_prep uploads them (those bcfgpu_gap_prep_tile forms or uploads itself: the positions, the reference slice, p->aux)
+    WS_GAP_POS = 51, WS_GAP_SMPL_OFF = 52,
     WS_GAP_P_READ = 53, WS_GAP_P_QPOS = 54, WS_GAP_P_INDEL = 55, WS_GAP_REF = 64, WS_GAP_AUX = 67,
     //   bcfgpu_internal_gap_core
     WS_GAP_INSCNT = 56, WS_GAP_INSCNS = 57, WS_GAP_REF2 = 58, WS_GAP_SCORE1 = 59, WS_GAP_SCORE2 = 60, WS_GAP_WIDE = 61,
@@ -180,8 +176,22 @@ void bcfgpu_internal_drop_plan(bcfgpu_ctx *c, WsSlot recs);
 int bcfgpu_set_error(int code, const char *what);               // bcfgpu_last_error() becomes `what`; returns `code`
 int bcfgpu_set_error(int code, const char *name, const char *what);     // ... becomes "`name`: `what`"
 
-// [lowest start, highest end) of the pool's reads (pileup.hip)
-int bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, int *lo, int *hi);
+// ---- a bcfgpu_reads in HBM (pileup.hip) ----
+// One slot per array.  The context's pool lies in one of two sets of kept slots (POOL_SET, pileup.hip); the host-pointer forms of
+// the read stages upload their reads to POOL_VIEW, scratch for one call, and run the pool forms' cores on that view.
+struct PoolSlots { WsSlot cig, seq16, qual, r_pos, r_lq, r_flag, r_ncig, r_cig_off, r_seq_off, r_mapq, zq, r_has_zq; };
+constexpr PoolSlots POOL_VIEW = {WS_VIEW_CIG, WS_VIEW_SEQ16, WS_VIEW_QUAL, WS_VIEW_R_POS, WS_VIEW_R_LQ, WS_VIEW_R_FLAG, WS_VIEW_R_NCIG,
+                                 WS_VIEW_R_CIG_OFF, WS_VIEW_R_SEQ_OFF, WS_VIEW_R_MAPQ, WS_VIEW_ZQ, WS_VIEW_HAS_ZQ};
+// the arrays only some stages read: they go up when the caller asks for them, and may be NULL otherwise
+enum : unsigned { READS_LQ = 1, READS_FLAG = 2, READS_MAPQ = 4, READS_ZQ = 8 };
+// The arrays of `rd` (and r_mapq), as they are, to the slots `ps`, the copies queued on `stream`: the extents of the pools (the
+// caller hands over pointers, not lengths), then *D = their description, valid = 0 (it is not the context's pool).  r_pos, r_ncig,
+// r_cig_off, r_seq_off, cig, seq16 and qual always go up; r_lq (the host reads it in any case, for the extents), r_flag, r_mapq and
+// zq / r_has_zq (those two: when `rd` has both) as `want` says, D's pointer NULL otherwise.  Errors are set as "`who`: ...".
+int pool_view_upload(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const uint8_t *r_mapq, unsigned want,
+                     const PoolSlots &ps, hipStream_t stream, DevPool *D);
+// [lowest start, highest end) of D's reads, kept in D once computed
+int bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, DevPool &D, int *lo, int *hi);
 // The size pass of an encoder entry `name` behind its size kernel (gather.hip): d_off[0 .. n_off) holds the blocks' sizes and a
 // last 0 and becomes their exclusive sum, the offsets; *n_bytes = their total, d_off[n_off - 1].  The stream is synchronised.
 // n_off == 1 (nothing to encode, no size kernel): the one offset is set to 0.  Returns 0 -- the caller goes on to its write

@@ -783,20 +783,10 @@ extern "C" int bcfgpu_gap_prep(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bc
     const auto t_begin = std::chrono::steady_clock::now();
     auto ms_since = [](std::chrono::steady_clock::time_point t0) {
         return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    const int ns = in->n_sites, n = in->n_smpl, nr = rd->n_reads;
+    const int ns = in->n_sites, n = in->n_smpl;
     if (ns <= 0) return BCFGPU_OK;
     if (n <= 0) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_gap_prep: n_smpl");
     const size_t n_ent = (size_t)in->smpl_off[(size_t)ns * n];
-    // extents of the pools (the caller hands over pointers, not lengths)
-    size_t nbase = 0, ncig = 0;
-    bool any_zq = false;
-    for (int r = 0; r < nr; ++r) {
-        const size_t e = (size_t)rd->r_seq_off[r] + rd->r_lq[r], c = (size_t)rd->r_cig_off[r] + rd->r_ncig[r];
-        if (e > nbase) nbase = e;
-        if (c > ncig) ncig = c;
-        if (rd->r_has_zq && rd->r_has_zq[r] && rd->zq) any_zq = true;
-    }
-    if (nbase >> 31 || n_ent >> 31) return bcfgpu_set_error(BCFGPU_E_RANGE, "bcfgpu_gap_prep: batch too large (32-bit offsets), use fewer sites per call");
     // the slice of the reference the batch can touch: from the leftmost window to 64 kb past the rightmost position (the
     // scans of est_indelreg and of the homopolymer run stop at the end of the slice: exact unless a repeat is longer)
     int pmin = INT_MAX, pmax = 0;
@@ -805,36 +795,27 @@ extern "C" int bcfgpu_gap_prep(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bc
     const long ref_hi = pmax + 1 + (long)strnlen(in->ref + pmax + 1, 65536 + 4096);   // the caller guarantees ref[pos+1] exists (mpileup.c:341)
 
     // ---- inputs to HBM (queued on the stream; the kernels follow in order) ----
-    int32_t *d_rpos = (int32_t*)WS(WS_GAP_R_POS, (size_t)nr * 4), *d_rlq = (int32_t*)WS(WS_GAP_R_LQ, (size_t)nr * 4), *d_rflag = (int32_t*)WS(WS_GAP_R_FLAG, (size_t)nr * 4);
-    int32_t *d_rncig = (int32_t*)WS(WS_GAP_R_NCIG, (size_t)nr * 4), *d_rcoff = (int32_t*)WS(WS_GAP_R_CIG_OFF, (size_t)nr * 4), *d_rsoff = (int32_t*)WS(WS_GAP_R_SEQ_OFF, (size_t)nr * 4);
-    uint32_t *d_cig = (uint32_t*)WS(WS_GAP_CIG, ncig * 4);
-    uint8_t *d_seq = (uint8_t*)WS(WS_GAP_SEQ, nbase), *d_qual = (uint8_t*)WS(WS_GAP_QUAL, nbase), *d_zq = any_zq ? (uint8_t*)WS(WS_GAP_ZQ, nbase) : nullptr;
-    uint8_t *d_haszq = any_zq ? (uint8_t*)WS(WS_GAP_HAS_ZQ, (size_t)nr) : nullptr;
+    DevPool V{};
+    if (const int rc = pool_view_upload("bcfgpu_gap_prep", ctx, rd, nullptr, READS_LQ | READS_FLAG | READS_ZQ, POOL_VIEW, st, &V)) return rc;
+    if (V.n_bases >> 31 || n_ent >> 31) {
+        hipStreamSynchronize(st);                               // (the copies read the caller's arrays)
+        return bcfgpu_set_error(BCFGPU_E_RANGE, "bcfgpu_gap_prep: batch too large (32-bit offsets), use fewer sites per call");
+    }
     int32_t *d_pos = (int32_t*)WS(WS_GAP_POS, (size_t)ns * 4), *d_soff = (int32_t*)WS(WS_GAP_SMPL_OFF, ((size_t)ns * n + 1) * 4);
     int32_t *d_pread = (int32_t*)WS(WS_GAP_P_READ, n_ent * 4), *d_pqpos = (int32_t*)WS(WS_GAP_P_QPOS, n_ent * 4), *d_pindel = (int32_t*)WS(WS_GAP_P_INDEL, n_ent * 4);
     char *d_ref = (char*)WS(WS_GAP_REF, (size_t)(ref_hi - ref_lo));
     uint32_t *d_aux = (uint32_t*)WS(WS_GAP_AUX, n_ent * 4);
-    if (!d_rpos || !d_rlq || !d_rflag || !d_rncig || !d_rcoff || !d_rsoff || !d_cig || !d_seq || !d_qual || (any_zq && (!d_zq || !d_haszq)) ||
-        !d_pos || !d_soff || !d_pread || !d_pqpos || !d_pindel || !d_ref || !d_aux)
+    if (!d_pos || !d_soff || !d_pread || !d_pqpos || !d_pindel || !d_ref || !d_aux)
         return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep: device workspace");
     #define UP(dst, src, bytes) GP_CHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st))
-    UP(d_rpos, rd->r_pos, (size_t)nr * 4); UP(d_rlq, rd->r_lq, (size_t)nr * 4); UP(d_rflag, rd->r_flag, (size_t)nr * 4);
-    UP(d_rncig, rd->r_ncig, (size_t)nr * 4); UP(d_rcoff, rd->r_cig_off, (size_t)nr * 4); UP(d_rsoff, rd->r_seq_off, (size_t)nr * 4);
-    if (ncig) UP(d_cig, rd->cig, ncig * 4);
-    if (nbase) { UP(d_seq, rd->seq16, nbase); UP(d_qual, rd->qual, nbase); }
-    if (any_zq) { UP(d_zq, rd->zq, nbase); UP(d_haszq, rd->r_has_zq, (size_t)nr); }
     UP(d_pos, in->pos, (size_t)ns * 4); UP(d_soff, in->smpl_off, ((size_t)ns * n + 1) * 4);
     if (n_ent) { UP(d_pread, in->p_read, n_ent * 4); UP(d_pqpos, in->p_qpos, n_ent * 4); UP(d_pindel, in->p_indel, n_ent * 4); }
     UP(d_ref, in->ref + ref_lo, (size_t)(ref_hi - ref_lo));
     #undef UP
-    GapIn g{};
-    g.n_sites = ns; g.n_smpl = n; g.n_reads = nr;
+    GapIn g = gap_in_of(V, *in);
+    g.n_sites = ns; g.n_smpl = n;
     g.pos = d_pos; g.smpl_off = d_soff; g.p_read = d_pread; g.p_qpos = d_pqpos; g.p_indel = d_pindel;
-    g.r_pos = d_rpos; g.r_lq = d_rlq; g.r_flag = d_rflag; g.r_ncig = d_rncig; g.r_cig_off = d_rcoff; g.r_seq_off = d_rsoff;
-    g.cig = d_cig; g.seq16 = d_seq; g.qual = d_qual; g.zq = d_zq; g.r_has_zq = d_haszq;
     g.ref = d_ref; g.ref_lo = ref_lo; g.ref_hi = ref_hi;
-    g.openQ = in->openQ; g.extQ = in->extQ; g.tandemQ = in->tandemQ; g.min_support = in->min_support; g.per_sample_flt = in->per_sample_flt;
-    g.min_frac = in->min_frac;
     gs.prepare_ms = ms_since(t_begin);
     const int rc = bcfgpu_internal_gap_core(ctx, g, n_ent, d_aux, out, inscns_cap);
     if (rc) return rc;

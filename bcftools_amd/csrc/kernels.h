@@ -183,6 +183,17 @@ struct GapIn {
     int openQ, extQ, tandemQ, min_support, per_sample_flt;
     double min_frac;
 };
+// the reads of `V` and the caller's parameters; the sites, their entries and the reference slice are the caller's to fill in
+inline GapIn gap_in_of(const DevPool &V, const bcfgpu_indel_in &par)
+{
+    GapIn g{};
+    g.n_reads = V.n_reads;
+    g.r_pos = V.r_pos; g.r_lq = V.r_lq; g.r_flag = V.r_flag; g.r_ncig = V.r_ncig; g.r_cig_off = V.r_cig_off; g.r_seq_off = V.r_seq_off;
+    g.cig = V.cig; g.seq16 = V.seq16; g.qual = V.qual; g.zq = V.zq; g.r_has_zq = V.r_has_zq;
+    g.openQ = par.openQ; g.extQ = par.extQ; g.tandemQ = par.tandemQ; g.min_support = par.min_support; g.per_sample_flt = par.per_sample_flt;
+    g.min_frac = par.min_frac;
+    return g;
+}
 // what bcf_call_gap_prep keeps in local variables for one position
 struct GapSite {
     int32_t live;                                // 0: bcf_call_gap_prep returns -1 before the realignment

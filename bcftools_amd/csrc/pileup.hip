@@ -591,10 +591,12 @@ template <class F> static void on_threads(int nthr, F &&fn)
 }
 
 // The pool's kept slots come in two sets (ctx.h): the context's pool lies in one, the pool bcfgpu_pool_stage brings up in the other.
-struct PoolSlots { WsSlot cig, seq16, qual, r_pos, r_lq, r_flag, r_ncig, r_cig_off, r_seq_off, r_mapq; };
+// (zq / r_has_zq: no upload writes them; bcfgpu_pool_baq leaves the pool's there, whichever set it is in)
 static const PoolSlots POOL_SET[2] = {
-    {WS_POOL_CIG, WS_POOL_SEQ16, WS_POOL_QUAL, WS_POOL_R_POS, WS_POOL_R_LQ, WS_POOL_R_FLAG, WS_POOL_R_NCIG, WS_POOL_R_CIG_OFF, WS_POOL_R_SEQ_OFF, WS_POOL_R_MAPQ},
-    {WS_POOL_B_CIG, WS_POOL_B_SEQ16, WS_POOL_B_QUAL, WS_POOL_B_R_POS, WS_POOL_B_R_LQ, WS_POOL_B_R_FLAG, WS_POOL_B_R_NCIG, WS_POOL_B_R_CIG_OFF, WS_POOL_B_R_SEQ_OFF, WS_POOL_B_R_MAPQ},
+    {WS_POOL_CIG, WS_POOL_SEQ16, WS_POOL_QUAL, WS_POOL_R_POS, WS_POOL_R_LQ, WS_POOL_R_FLAG, WS_POOL_R_NCIG, WS_POOL_R_CIG_OFF, WS_POOL_R_SEQ_OFF, WS_POOL_R_MAPQ,
+     WS_PBAQ_ZQ, WS_PBAQ_HAS_ZQ},
+    {WS_POOL_B_CIG, WS_POOL_B_SEQ16, WS_POOL_B_QUAL, WS_POOL_B_R_POS, WS_POOL_B_R_LQ, WS_POOL_B_R_FLAG, WS_POOL_B_R_NCIG, WS_POOL_B_R_CIG_OFF, WS_POOL_B_R_SEQ_OFF,
+     WS_POOL_B_R_MAPQ, WS_PBAQ_ZQ, WS_PBAQ_HAS_ZQ},
 };
 // where the packed inputs go: scratch of one call (bcfgpu_pool_upload), or kept from the stage to the adopt
 struct PackedSlots { WsSlot seq4, qual4, recs; };
@@ -619,6 +621,60 @@ static int pool_check_args(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads 
     return BCFGPU_OK;
 }
 
+// the per-read arrays of `rd` as they are (pool_view_upload, and the packed form that brings its own bases only)
+static void upload_read_arrays(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const uint8_t *r_mapq, unsigned want, const PoolSlots &ps, hipStream_t stream, DevPool &D)
+{
+    const size_t n = (size_t)rd->n_reads;
+    D.r_pos = (const int32_t*)ws_upload(ctx, ps.r_pos, rd->r_pos, n * 4, 64, stream);
+    D.r_lq = (want & READS_LQ) ? (const int32_t*)ws_upload(ctx, ps.r_lq, rd->r_lq, n * 4, 64, stream) : nullptr;
+    D.r_flag = (want & READS_FLAG) ? (const int32_t*)ws_upload(ctx, ps.r_flag, rd->r_flag, n * 4, 64, stream) : nullptr;
+    D.r_ncig = (const int32_t*)ws_upload(ctx, ps.r_ncig, rd->r_ncig, n * 4, 64, stream);
+    D.r_cig_off = (const int32_t*)ws_upload(ctx, ps.r_cig_off, rd->r_cig_off, n * 4, 64, stream);
+    D.r_seq_off = (const int32_t*)ws_upload(ctx, ps.r_seq_off, rd->r_seq_off, n * 4, 64, stream);
+    D.r_mapq = (want & READS_MAPQ) ? (uint8_t*)ws_upload(ctx, ps.r_mapq, r_mapq, n, 64, stream) : nullptr;
+}
+
+int bcfgpu::pool_view_upload(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const uint8_t *r_mapq, unsigned want,
+                             const PoolSlots &ps, hipStream_t stream, DevPool *out)
+{
+    const int n = rd->n_reads;
+    if (n && (!rd->r_pos || !rd->r_lq || !rd->r_ncig || !rd->r_cig_off || !rd->r_seq_off || !rd->seq16 || !rd->qual ||
+              ((want & READS_FLAG) && !rd->r_flag) || ((want & READS_MAPQ) && !r_mapq)))
+        return pool_fail(who, BCFGPU_E_ARG, "a read array is missing");
+    const int nthr = host_threads(n);
+    std::vector<size_t> t_nbase(nthr, 0), t_ncig(nthr, 0);
+    on_threads(nthr, [&](int t) {
+        const int k0 = (int)((long)n * t / nthr), k1 = (int)((long)n * (t + 1) / nthr);
+        size_t nb = 0, nc = 0;
+        for (int r = k0; r < k1; ++r) {
+            const size_t e = (size_t)rd->r_seq_off[r] + (size_t)std::max(rd->r_lq[r], 0), c = (size_t)rd->r_cig_off[r] + (size_t)std::max(rd->r_ncig[r], 0);
+            if (e > nb) nb = e;
+            if (c > nc) nc = c;
+        }
+        t_nbase[t] = nb; t_ncig[t] = nc;
+    });
+    size_t nbase = 0, ncig = 0;
+    for (int t = 0; t < nthr; ++t) { nbase = std::max(nbase, t_nbase[t]); ncig = std::max(ncig, t_ncig[t]); }
+    if (nbase >> 32) return pool_fail(who, BCFGPU_E_RANGE, "the pool holds 2^32 or more bases");
+    DevPool D{};
+    D.n_reads = n; D.n_bases = (uint32_t)nbase; D.n_cig = (uint32_t)ncig;
+    upload_read_arrays(ctx, rd, r_mapq, want, ps, stream, D);
+    D.cig = (const uint32_t*)ws_upload(ctx, ps.cig, rd->cig, ncig * 4, 64, stream);
+    D.seq16 = (const uint8_t*)ws_upload(ctx, ps.seq16, rd->seq16, nbase, 64, stream);
+    D.qual = (uint8_t*)ws_upload(ctx, ps.qual, rd->qual, nbase, 64, stream);
+    D.qual_slot = ps.qual;
+    const bool zq = (want & READS_ZQ) && rd->zq && rd->r_has_zq;
+    if (zq) {
+        D.zq = (uint8_t*)ws_upload(ctx, ps.zq, rd->zq, nbase, 64, stream);
+        D.r_has_zq = (uint8_t*)ws_upload(ctx, ps.r_has_zq, rd->r_has_zq, (size_t)n, 64, stream);
+    }
+    if (!D.r_pos || ((want & READS_LQ) && !D.r_lq) || ((want & READS_FLAG) && !D.r_flag) || !D.r_ncig || !D.r_cig_off || !D.r_seq_off || ((want & READS_MAPQ) && !D.r_mapq) ||
+        !D.cig || !D.seq16 || !D.qual || (zq && (!D.zq || !D.r_has_zq)))
+        return pool_fail(who, BCFGPU_E_NOMEM, "device workspace");
+    *out = D;
+    return BCFGPU_OK;
+}
+
 // The caller's arrays to HBM: every host-to-device copy of a pool, queued on `stream`, into set `ps` of the pool's slots and (the
 // packed inputs) into `pks`.  `in` becomes the pool's description: D's arrays all have their room, those of the packed forms are
 // formed by pool_form.  No kernel is launched here.
@@ -626,30 +682,14 @@ static int pool_copy(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, c
                      const PoolSlots &ps, const PackedSlots &pks, hipStream_t stream, PoolStage &in)
 {
     auto fail = [&](int code, const char *what) { return pool_fail(who, code, what); };
+    in.d_rec = nullptr; in.d_seq4 = in.d_qual4 = nullptr; in.qual_bits = 0; in.pal[0] = in.pal[1] = 0;
+    if (!pk) return pool_view_upload(who, ctx, rd, r_mapq, READS_LQ | READS_FLAG | READS_MAPQ, ps, stream, &in.D);
+    // the packed forms state the extent of the pools
     DevPool D{};
     const int n = rd->n_reads;
-    // the extent of the pools (the packed form states it)
-    size_t nbase = 0, ncig = 0;
-    if (pk) { nbase = (size_t)pk->n_bases; ncig = (size_t)pk->n_cig; }
-    else {
-        const int nthr = host_threads(n);
-        std::vector<size_t> t_nbase(nthr, 0), t_ncig(nthr, 0);
-        on_threads(nthr, [&](int t) {
-            const int k0 = (int)((long)n * t / nthr), k1 = (int)((long)n * (t + 1) / nthr);
-            size_t nb = 0, nc = 0;
-            for (int r = k0; r < k1; ++r) {
-                const size_t e = (size_t)rd->r_seq_off[r] + (size_t)std::max(rd->r_lq[r], 0), c = (size_t)rd->r_cig_off[r] + (size_t)std::max(rd->r_ncig[r], 0);
-                if (e > nb) nb = e;
-                if (c > nc) nc = c;
-            }
-            t_nbase[t] = nb; t_ncig[t] = nc;
-        });
-        for (int t = 0; t < nthr; ++t) { nbase = std::max(nbase, t_nbase[t]); ncig = std::max(ncig, t_ncig[t]); }
-        if (nbase >> 32) return fail(BCFGPU_E_RANGE, "the pool holds 2^32 or more bases");
-    }
+    const size_t nbase = (size_t)pk->n_bases, ncig = (size_t)pk->n_cig;
     D.n_reads = n; D.n_bases = (uint32_t)nbase; D.n_cig = (uint32_t)ncig;
-    in.d_rec = nullptr; in.d_seq4 = in.d_qual4 = nullptr; in.qual_bits = 0; in.pal[0] = in.pal[1] = 0;
-    if (pk && pk->recs) {
+    if (pk->recs) {
         // the 12-byte records: the arrays are formed from them, the offsets by two prefix sums (pool_form)
         in.d_rec = (const bcfgpu_read12*)ws_upload(ctx, pks.recs, pk->recs, (size_t)n * sizeof(bcfgpu_read12), 64, stream);
         D.r_pos = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_pos, (size_t)n * 4 + 64); D.r_lq = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_lq, (size_t)n * 4 + 64);
@@ -657,34 +697,20 @@ static int pool_copy(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, c
         D.r_cig_off = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_cig_off, (size_t)(n + 1) * 4 + 64); D.r_seq_off = (const int32_t*)bcfgpu_internal_ws(ctx, ps.r_seq_off, (size_t)(n + 1) * 4 + 64);
         D.r_mapq = (uint8_t*)bcfgpu_internal_ws(ctx, ps.r_mapq, (size_t)n + 64);
         if (!in.d_rec) return fail(BCFGPU_E_NOMEM, "device workspace");
-    } else {
-        D.r_pos = (const int32_t*)ws_upload(ctx, ps.r_pos, rd->r_pos, (size_t)n * 4, 64, stream);
-        D.r_lq = (const int32_t*)ws_upload(ctx, ps.r_lq, rd->r_lq, (size_t)n * 4, 64, stream);
-        D.r_flag = (const int32_t*)ws_upload(ctx, ps.r_flag, rd->r_flag, (size_t)n * 4, 64, stream);
-        D.r_ncig = (const int32_t*)ws_upload(ctx, ps.r_ncig, rd->r_ncig, (size_t)n * 4, 64, stream);
-        D.r_cig_off = (const int32_t*)ws_upload(ctx, ps.r_cig_off, rd->r_cig_off, (size_t)n * 4, 64, stream);
-        D.r_seq_off = (const int32_t*)ws_upload(ctx, ps.r_seq_off, rd->r_seq_off, (size_t)n * 4, 64, stream);
-        D.r_mapq = (uint8_t*)ws_upload(ctx, ps.r_mapq, r_mapq, (size_t)n, 64, stream);
-    }
+    } else upload_read_arrays(ctx, rd, r_mapq, READS_LQ | READS_FLAG | READS_MAPQ, ps, stream, D);
     D.cig = (const uint32_t*)ws_upload(ctx, ps.cig, rd->cig, ncig * 4, 64, stream);
-    uint8_t *d_seq16 = nullptr, *d_qual = nullptr;
-    if (pk) {
-        const size_t n_in = (nbase + 1) / 2;
-        d_seq16 = (uint8_t*)bcfgpu_internal_ws(ctx, ps.seq16, nbase + 64);
-        in.d_seq4 = (const uint8_t*)ws_upload(ctx, pks.seq4, pk->seq4, n_in, 64, stream);
-        if (pk->qual4) {
-            d_qual = (uint8_t*)bcfgpu_internal_ws(ctx, ps.qual, nbase + 64);
-            in.d_qual4 = (const uint8_t*)ws_upload(ctx, pks.qual4, pk->qual4, pk->qual_bits == 2 ? (nbase + 3) / 4 : n_in, 64, stream);
-        } else d_qual = (uint8_t*)ws_upload(ctx, ps.qual, rd->qual, nbase, 64, stream);
-        if (!in.d_seq4 || (pk->qual4 && !in.d_qual4) || !d_seq16 || !d_qual) return fail(BCFGPU_E_NOMEM, "device workspace");
-        std::memcpy(in.pal, pk->palette, 16);
-        in.qual_bits = (int)pk->qual_bits;
-    } else {
-        d_seq16 = (uint8_t*)ws_upload(ctx, ps.seq16, rd->seq16, nbase, 64, stream);
-        d_qual = (uint8_t*)ws_upload(ctx, ps.qual, rd->qual, nbase, 64, stream);
-    }
-    D.seq16 = d_seq16; D.qual = d_qual; D.qual_slot = ps.qual;
-    if (!D.r_pos || !D.r_lq || !D.r_flag || !D.r_ncig || !D.r_cig_off || !D.r_seq_off || !D.r_mapq || !D.cig || !D.seq16 || !D.qual)
+    const size_t n_in = (nbase + 1) / 2;
+    D.seq16 = (const uint8_t*)bcfgpu_internal_ws(ctx, ps.seq16, nbase + 64);
+    in.d_seq4 = (const uint8_t*)ws_upload(ctx, pks.seq4, pk->seq4, n_in, 64, stream);
+    if (pk->qual4) {
+        D.qual = (uint8_t*)bcfgpu_internal_ws(ctx, ps.qual, nbase + 64);
+        in.d_qual4 = (const uint8_t*)ws_upload(ctx, pks.qual4, pk->qual4, pk->qual_bits == 2 ? (nbase + 3) / 4 : n_in, 64, stream);
+    } else D.qual = (uint8_t*)ws_upload(ctx, ps.qual, rd->qual, nbase, 64, stream);
+    D.qual_slot = ps.qual;
+    std::memcpy(in.pal, pk->palette, 16);
+    in.qual_bits = (int)pk->qual_bits;
+    if (!in.d_seq4 || (pk->qual4 && !in.d_qual4) || !D.r_pos || !D.r_lq || !D.r_flag || !D.r_ncig || !D.r_cig_off || !D.r_seq_off || !D.r_mapq ||
+        !D.cig || !D.seq16 || !D.qual)
         return fail(BCFGPU_E_NOMEM, "device workspace");
     in.D = D;
     return BCFGPU_OK;
@@ -925,13 +951,11 @@ extern "C" int bcfgpu_pileup_packed(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, con
 }
 
 // ---- the pool as an object of its own: upload once, run the stages on it, build the tile ----
-// [lowest start, highest end) of the pool's reads (one small kernel and a wait, once per pool)
-int bcfgpu::bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, int *lo, int *hi)
+// [lowest start, highest end) of D's reads (one small kernel and a wait, once per pool)
+int bcfgpu::bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, DevPool &D, int *lo, int *hi)
 {
     hipStream_t stream = nullptr;
     if (bcfgpu_internal_device(ctx, &stream, nullptr)) return BCFGPU_E_ARG;
-    DevPool &D = *bcfgpu_internal_pool_state(ctx);
-    if (!D.valid) return BCFGPU_E_ARG;
     if (!D.ext_valid) {
         int *d = (int*)bcfgpu_internal_ws(ctx, WS_POOL_EXTENT, 64);
         if (!d) return BCFGPU_E_NOMEM;
@@ -1213,8 +1237,8 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     GT_CHK(hipMemcpyAsync(h_k, d_nk, 4, hipMemcpyDeviceToHost, stream));
     GT_CHK(hipMemcpyAsync(h_k + 16, d_kidx, (size_t)n_cols * 4, hipMemcpyDeviceToHost, stream));
     // meanwhile: the reads as bcfgpu_gap_prep's kernels index them
-    int32_t *d_rpos = (int32_t*)GWS(WS_GAP_R_POS, (size_t)nr * 4), *d_rlq = (int32_t*)GWS(WS_GAP_R_LQ, (size_t)nr * 4), *d_rflag = (int32_t*)GWS(WS_GAP_R_FLAG, (size_t)nr * 4);
-    int32_t *d_rncig = (int32_t*)GWS(WS_GAP_R_NCIG, (size_t)nr * 4), *d_rcoff = (int32_t*)GWS(WS_GAP_R_CIG_OFF, (size_t)nr * 4), *d_rsoff = (int32_t*)GWS(WS_GAP_R_SEQ_OFF, (size_t)nr * 4);
+    int32_t *d_rpos = (int32_t*)GWS(WS_VIEW_R_POS, (size_t)nr * 4), *d_rlq = (int32_t*)GWS(WS_VIEW_R_LQ, (size_t)nr * 4), *d_rflag = (int32_t*)GWS(WS_VIEW_R_FLAG, (size_t)nr * 4);
+    int32_t *d_rncig = (int32_t*)GWS(WS_VIEW_R_NCIG, (size_t)nr * 4), *d_rcoff = (int32_t*)GWS(WS_VIEW_R_CIG_OFF, (size_t)nr * 4), *d_rsoff = (int32_t*)GWS(WS_VIEW_R_SEQ_OFF, (size_t)nr * 4);
     if (!d_rpos || !d_rlq || !d_rflag || !d_rncig || !d_rcoff || !d_rsoff) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep_tile: device workspace");
     if (nr) hipLaunchKernelGGL(gap_unpack_reads_kernel, dim3((nr + 255) / 256), dim3(256), 0, stream, P, d_rpos, d_rlq, d_rflag, d_rncig, d_rcoff, d_rsoff);
     GT_CHK(hipStreamSynchronize(stream));                       // how many columns go on
@@ -1250,7 +1274,7 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     const long ref_hi = ref_from + (long)strnlen(par->ref + ref_from, (size_t)std::min<long>(65536 + 4096, ref_end - ref_from));
     char *d_ref = (char*)GWS(WS_GAP_REF, (size_t)(ref_hi - ref_lo));
     const bool any_zq = reads && reads->zq && reads->r_has_zq;
-    uint8_t *d_zq = any_zq ? (uint8_t*)GWS(WS_GAP_ZQ, (size_t)P.n_bases) : nullptr, *d_haszq = any_zq ? (uint8_t*)GWS(WS_GAP_HAS_ZQ, (size_t)nr) : nullptr;
+    uint8_t *d_zq = any_zq ? (uint8_t*)GWS(WS_VIEW_ZQ, (size_t)P.n_bases) : nullptr, *d_haszq = any_zq ? (uint8_t*)GWS(WS_VIEW_HAS_ZQ, (size_t)nr) : nullptr;
     {   // no ZQ bytes from the host: those bcfgpu_pool_baq left in HBM, if the pool of the pileup is still the context's pool
         const DevPool &D = *bcfgpu_internal_pool_state(ctx);
         if (!any_zq && D.valid && D.zq && D.r_has_zq && D.n_reads == nr && D.seq16 == P.seq16) { d_zq = D.zq; d_haszq = D.r_has_zq; }
@@ -1271,14 +1295,14 @@ extern "C" int bcfgpu_gap_prep_tile(bcfgpu_ctx *ctx, int32_t n_cols, const int32
     E.e_read = d_e; E.e_qpos = d_e + total; E.e_indel = d_e + 2 * (size_t)total;
     if (total) hipLaunchKernelGGL(entries_kernel<true>, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, E);
     GT_CHK(hipGetLastError());
-    GapIn g{};
-    g.n_sites = nk; g.n_smpl = S; g.n_reads = nr;
+    DevPool V{};                                                // the pileup's reads, as a view
+    V.n_reads = nr;
+    V.r_pos = d_rpos; V.r_lq = d_rlq; V.r_flag = d_rflag; V.r_ncig = d_rncig; V.r_cig_off = d_rcoff; V.r_seq_off = d_rsoff;
+    V.cig = P.cig; V.seq16 = P.seq16; V.qual = const_cast<uint8_t*>(P.qual); V.zq = d_zq; V.r_has_zq = d_haszq;
+    GapIn g = gap_in_of(V, *par);
+    g.n_sites = nk; g.n_smpl = S;
     g.pos = d_pos; g.smpl_off = reinterpret_cast<const int32_t*>(d_sel); g.p_read = E.e_read; g.p_qpos = E.e_qpos; g.p_indel = E.e_indel;
-    g.r_pos = d_rpos; g.r_lq = d_rlq; g.r_flag = d_rflag; g.r_ncig = d_rncig; g.r_cig_off = d_rcoff; g.r_seq_off = d_rsoff;
-    g.cig = P.cig; g.seq16 = P.seq16; g.qual = P.qual; g.zq = d_zq; g.r_has_zq = d_haszq;
     g.ref = d_ref; g.ref_lo = ref_lo; g.ref_hi = ref_hi;
-    g.openQ = par->openQ; g.extQ = par->extQ; g.tandemQ = par->tandemQ; g.min_support = par->min_support; g.per_sample_flt = par->per_sample_flt;
-    g.min_frac = par->min_frac;
     gs.prepare_ms = ms_since(t_begin);
     // the stage's per-column results, by kept column; scattered to the caller's rows afterwards
     std::vector<int32_t> k_ret(nk), k_types((size_t)nk * 4), k_maxins(nk), k_ireg(nk), k_msup(nk);

@@ -381,7 +381,9 @@ int  bcfgpu_gap_prep(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const bcfgpu_in
  *   qual_out[r_seq_off[r] + i]  new quality of base i (= qual when the read is left alone, ret[r] < 0)
  *   zq_out  [r_seq_off[r] + i]  the "ZQ" tag byte (64 + cap offset), 0 when the read is left alone
  *   ret[r]                      0 applied, -1 left alone (no sequence, qual 0xff, N in CIGAR, no aligned base)
- * Reads that already carry BQ/ZQ tags are the caller's business (realn.c:60-90); this entry is the computation. */
+ * Reads that already carry BQ/ZQ tags are the caller's business (realn.c:60-90); this entry is the computation.
+ * The host side uploads the reads, runs what bcfgpu_pool_baq runs on the pool (windows and bands are formed on the device) and
+ * brings the results back; the context's pool and its BAQ results are not touched.  Of `reads`, zq / r_has_zq are not read. */
 int  bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const char *ref, int32_t ref_len, int flag,
                 uint8_t *qual_out, uint8_t *zq_out, int32_t *ret);
 
@@ -389,7 +391,9 @@ int  bcfgpu_baq(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const char *ref, int
  * BAQ (mpileup.c:235-239, only when thres > 10): a cap on the read's mapping quality from its mismatches against the
  * reference (their count and capped base qualities, the aligned length, the clipped bases).  HOST pointers; reads->qual =
  * the qualities after bcfgpu_baq.  cap[r]: -1 = the read is dropped (mpileup.c:237), else the caller lowers the read's
- * mapping quality to cap[r] when it is above it (:238).  The filters that follow in mplp_func (-q, orphans) are the caller's. */
+ * mapping quality to cap[r] when it is above it (:238).  The filters that follow in mplp_func (-q, orphans) are the caller's.
+ * The host side uploads the reads and runs what bcfgpu_pool_cap_mapq runs on the pool, without lowering anything.  Of `reads`,
+ * r_flag and zq / r_has_zq are not read (they may be NULL). */
 int  bcfgpu_cap_mapq(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const char *ref, int32_t ref_len, int32_t thres, int32_t *cap);
 
 /* ---- mate overlaps: what bam_mplp_init_overlaps() (mpileup.c:640) makes htslib's pileup do to read pairs whose mates
@@ -398,7 +402,9 @@ int  bcfgpu_cap_mapq(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, const char *ref
  * first read's on ties); the other read's base gets quality 0.  Pair p is (pair_a[p] = the mate that entered the
  * pileup first, pair_b[p]); which reads pair up (proper pair, same contig, first mate still buffered) is the pileup
  * engine's bookkeeping and stays with the caller.  A read may be in one pair only.  HOST pointers; `reads->qual` (the
- * qualities after BAQ) is not modified: qual_out is the whole quality pool with the pairs' bases rewritten. */
+ * qualities after BAQ) is not modified: qual_out is the whole quality pool with the pairs' bases rewritten.
+ * The host side uploads the reads, runs what bcfgpu_pool_overlap_tweak runs on the pool and brings the qualities back.  Of
+ * `reads`, r_flag and zq / r_has_zq are not read (they may be NULL). */
 int  bcfgpu_overlap_tweak(bcfgpu_ctx *ctx, const bcfgpu_reads *reads, int32_t n_pairs, const int32_t *pair_a,
                           const int32_t *pair_b, uint8_t *qual_out);
 

@@ -11,9 +11,9 @@ CTX_H = os.path.join(ROOT, "bcftools_amd", "csrc", "ctx.h")
 
 # the entry points and the name prefixes of the slots each takes during one call (a prefix may serve several calls)
 CALLS = {
-    "bcfgpu_baq": ("WS_BAQ_",),
-    "bcfgpu_overlap_tweak": ("WS_OVL_",),
-    "bcfgpu_cap_mapq": ("WS_CAPQ_",),
+    "bcfgpu_baq": ("WS_VIEW_", "WS_BAQ_", "WS_PBAQ_"),              # the view of the caller's reads, its outputs, baq_core's scratch
+    "bcfgpu_overlap_tweak": ("WS_VIEW_", "WS_POVL_"),
+    "bcfgpu_cap_mapq": ("WS_VIEW_", "WS_PCAPQ_", "WS_POOL_EXTENT"),
     "bcfgpu_pool_upload": ("WS_POOL_",),
     "bcfgpu_pool_keep": ("WS_POOL_KEEP",),
     "bcfgpu_pool_baq": ("WS_PBAQ_",),
@@ -23,8 +23,8 @@ CALLS = {
     "bcfgpu_pileup": ("WS_POOL_", "WS_PLP_"),
     "bcfgpu_pileup_entries": ("WS_ENT_",),
     "bcfgpu_pileup_indel_tile": ("WS_ITILE_",),
-    "bcfgpu_gap_prep": ("WS_GAP_",),
-    "bcfgpu_gap_prep_tile": ("WS_GTILE_", "WS_GAP_"),
+    "bcfgpu_gap_prep": ("WS_VIEW_", "WS_GAP_"),
+    "bcfgpu_gap_prep_tile": ("WS_GTILE_", "WS_VIEW_", "WS_GAP_"),
     "bcfgpu_gvcf_blocks": ("WS_GVCF_",),
     "bcfgpu_compact_calls": ("WS_COMPACT_",),
     "bcfgpu_errmod_plan": ("WS_DRAW_",),

@@ -211,6 +211,20 @@ class VcfField(C.Structure):
 VCF_FIELD = [("off", "<u8"), ("site", "<i4"), ("kind", "<i4"), ("type", "<i4"), ("width", "<i4"), ("nals", "<i4"), ("flags", "<i4")]
 
 
+# bcfgpu_call_rewrite_vcf: the most FORMAT keys of a record (a bit of r_mask each)
+VCF_REWRITE_MAX_KEYS = 64
+
+
+class VcfRewrite(C.Structure):
+    """bcfgpu_vcf_rewrite: one record of bcfgpu_call_rewrite_vcf -- where its sample columns lie in the text buffer, which of its
+    FORMAT keys are Number=R, PL's place, the keys' and alleles' counts, whether PL and GQ are listed (32 bytes)."""
+    _fields_ = [("off", C.c_uint64), ("r_mask", C.c_uint64), ("len", C.c_uint32), ("pl_idx", C.c_int32), ("n_fmt", C.c_int16),
+                ("nals", C.c_int16), ("flags", C.c_int32)]
+
+
+VCF_REWRITE = [("off", "<u8"), ("r_mask", "<u8"), ("len", "<u4"), ("pl_idx", "<i4"), ("n_fmt", "<i2"), ("nals", "<i2"), ("flags", "<i4")]
+
+
 class Timing(C.Structure):
     _fields_ = [("glfgen_ms", C.c_float), ("combine_ms", C.c_float),
                 ("mcall_ms", C.c_float), ("total_ms", C.c_float)]
@@ -291,7 +305,9 @@ PROTOTYPES = {
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_call_encode_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.c_int32, C.POINTER(VcfField), C.c_int32, C.c_void_p,
                                          C.c_uint64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
-    "bcfgpu_comm_init_all": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
+    "bcfgpu_call_rewrite_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.POINTER(VcfRewrite), C.c_int32, C.c_void_p,
+                                          C.c_uint64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bcfgpu_comm_init_all":(C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
     "bcfgpu_comm_destroy": (None, [C.c_void_p]),
     "bcfgpu_gather_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "bcfgpu_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -94,13 +94,16 @@ enum WsSlot : int {
     // bcfgpu_call_decode_vcf (vcfdec.hip): the uploaded copies of the records' runs and of the sample map, the offsets of the columns
     // of one chunk of sites (at most BCFGPU_VCFDEC_START_BYTES, or one site's), the two error words
     WS_COMPACT_VCFDEC_VEC = 178, WS_COMPACT_VCFDEC_COL = 179, WS_COMPACT_VCFDEC_START = 180, WS_COMPACT_VCFDEC_ERR = 181,
+    // bcfgpu_call_rewrite_vcf (vcfcallrw.hip): the uploaded copies of the records' runs (as the indexing kernel reads them), of the
+    // records and of the sample map, the offsets of the columns of one chunk of sites (bounded as bcfgpu_call_decode_vcf's), the error word
+    WS_COMPACT_VCFRW_VEC = 182, WS_COMPACT_VCFRW_REC = 183, WS_COMPACT_VCFRW_COL = 184, WS_COMPACT_VCFRW_START = 185, WS_COMPACT_VCFRW_ERR = 186,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_COMPACT_VCFDEC_ERR + 1       // one past the highest slot
+    WS_COUNT = WS_COMPACT_VCFRW_ERR + 1       // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names
@@ -124,7 +127,8 @@ enum PinnedSlot : int {
     PIN_PBAQ_REF = 6,                   // bcfgpu_pool_baq: the reference slice (the call returns with its copy in flight)
     PIN_ENC_TOTAL = 7,                  // enc_offsets: the size of all blocks of an encoder entry (each synchronises before it returns)
     PIN_VCFDEC_ERR = 8,                 // bcfgpu_call_decode_vcf: the error words of its two passes (it synchronises before it reads them)
-    PINNED_COUNT = PIN_VCFDEC_ERR + 1       // one past the highest slot
+    PIN_VCFRW_ERR = 9,                  // bcfgpu_call_rewrite_vcf: the error word of its indexing pass (it synchronises before it reads it)
+    PINNED_COUNT = PIN_VCFRW_ERR + 1        // one past the highest slot
 };
 
 // workspace / pinned host buffer `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails

@@ -275,5 +275,9 @@ void launch_glfgen(const GlfgenParams &p, hipStream_t s);
 void launch_glfgen_prefix(const double *fk, const double *beta, double *pfx, hipStream_t s);   // pfx: GLF_PFX_DOUBLES doubles
 void launch_combine(const CombineParams &p, hipStream_t s);
 void launch_mcall(const McallParams &p, hipStream_t s);
+// vcfdec_index_kernel (vcfdec.hip) over sites k0 .. k0 + n_sites - 1 of `vec`, a workgroup a site: the offsets of the n_smpl_in columns'
+// tabs inside each run and the run's length to start[site - k0][0 .. n_smpl_in] (nullptr: counting only); err[0] = the smallest site
+// whose run does not begin with a tab or does not hold n_smpl_in of them (atomicMin: the caller sets the word to all ones first)
+void launch_vcfdec_index(const unsigned char *text, const bcfgpu_vcf_vec *vec, int k0, int n_sites, int n_smpl_in, uint32_t *start, uint32_t *err, hipStream_t s);
 
 }  // namespace bcfgpu

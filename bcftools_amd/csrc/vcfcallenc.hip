@@ -46,17 +46,6 @@ struct CallVcfArgs {
     int n_smpl;
 };
 
-// one value: '.' for `missing`, else in decimal with its sign; the bytes it takes
-template <bool WRITE>
-__device__ __forceinline__ int text_value(unsigned char *p, int32_t v)
-{
-    if (v == BCFGPU_INT32_MISSING) { if (WRITE) *p = '.'; return 1; }
-    if (WRITE) put_signed(p, v);
-    return signed_len(v);
-}
-// one GT entry: an allele index as its digit, anything else '.'
-__device__ __forceinline__ unsigned char gt_char(int g) { return g >= 0 && g <= 9 ? (unsigned char)('0' + g) : (unsigned char)'.'; }
-
 // The text of called sample s at site k (fields f0 .. f1 - 1): its length, and with WRITE its bytes at p (LDS).
 template <bool WRITE>
 __device__ __forceinline__ int sample_text(const CallVcfArgs &A, const bcfgpu_call_site &c, size_t k, int f0, int f1, int s, unsigned char *p)

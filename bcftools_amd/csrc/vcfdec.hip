@@ -29,7 +29,6 @@ namespace bcfgpu {
 constexpr int VDEC_LANE_LINES = 4;                              // lines a lane of the index kernel looks at in a slice
 static_assert((COD_LINE + COD_SLICE + COD_LINE - 1) / COD_LINE <= VDEC_LANE_LINES * COD_THREADS, "the lanes' lines cover the stage");
 static_assert(COD_SLICE % COD_LINE == 0, "the stage is whole lines");
-constexpr uint32_t VDEC_NO_ERROR = 0xffffffffu;                 // an error word nobody has touched; else the smallest site at fault
 
 __global__ __launch_bounds__(COD_THREADS) void vcfdec_index_kernel(const unsigned char *text, const bcfgpu_vcf_vec *vec, int k0, int n_smpl_in,
                                                                    uint32_t *start, uint32_t *err)
@@ -113,6 +112,12 @@ __global__ __launch_bounds__(COD_THREADS) void vcfdec_parse_kernel(const unsigne
     if (!ok) atomicMin(err + 1, (uint32_t)k);
 }
 
+// (kernels.h: bcfgpu_call_rewrite_vcf of vcfcallrw.hip indexes its records' columns with the same kernel)
+void launch_vcfdec_index(const unsigned char *text, const bcfgpu_vcf_vec *vec, int k0, int n_sites, int n_smpl_in, uint32_t *start, uint32_t *err, hipStream_t s)
+{
+    hipLaunchKernelGGL(vcfdec_index_kernel, dim3(n_sites), dim3(COD_THREADS), 0, s, text, vec, k0, n_smpl_in, start, err);
+}
+
 }  // namespace bcfgpu
 
 extern "C" int bcfgpu_call_decode_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_smpl_in, const void *d_text, uint64_t n_text_bytes,
@@ -141,13 +146,13 @@ extern "C" int bcfgpu_call_decode_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t 
     const unsigned char *text = (const unsigned char*)d_text;
     // the indexing pass over every site before any plane is written: with the offsets when they all fit the slot, else counting only
     if (hipMemsetAsync(d_err, 0xff, 8, st) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_call_decode_vcf: error word");
-    hipLaunchKernelGGL(vcfdec_index_kernel, dim3(n_sites), dim3(COD_THREADS), 0, st, text, d_vec, 0, n_smpl_in, once ? d_start : nullptr, d_err);
+    launch_vcfdec_index(text, d_vec, 0, n_sites, n_smpl_in, once ? d_start : nullptr, d_err, st);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_err, d_err, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_call_decode_vcf: indexing pass");
     if (h_err[0] != VDEC_NO_ERROR) return bcfgpu_set_error(BCFGPU_E_ARG, "bcfgpu_call_decode_vcf: a record does not hold n_smpl_in sample columns, each behind a tab");
     for (int k0 = 0; k0 < n_sites; k0 += chunk) {
         const int nk = n_sites - k0 < chunk ? n_sites - k0 : chunk;
-        if (!once) hipLaunchKernelGGL(vcfdec_index_kernel, dim3(nk), dim3(COD_THREADS), 0, st, text, d_vec, k0, n_smpl_in, d_start, d_err);
+        if (!once) launch_vcfdec_index(text, d_vec, k0, nk, n_smpl_in, d_start, d_err, st);
         hipLaunchKernelGGL(vcfdec_parse_kernel, dim3(nk), dim3(COD_THREADS), 0, st, text, d_vec, k0, d_start, d_col, n_smpl_in, S, n_planes, d_out, d_err);
     }
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_err, d_err, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)

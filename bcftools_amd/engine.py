@@ -548,6 +548,46 @@ class Context:
             self.release(bufs)
         return data, offs
 
+    def rewrite_call_vcf(self, planes, n_sites, n_gt_max, rec, n_smpl_in, text, col=None, emit=None, cap_bytes=None):
+        """bcfgpu_call_rewrite_vcf on call planes already in HBM (an abi.CallOut of device pointers): the call records' sample columns
+        as VCF text, rewritten from the input records' own columns.  rec: one record a site, an array of abi.VCF_REWRITE; text: the
+        input records' sample columns (bytes or np.uint8), uploaded here; col: the input column of each called sample, or None; emit:
+        host u8 [n_sites] or None; cap_bytes: the buffer's size (None: asked from the size pass first).  Returns (bytes as np.uint8,
+        offsets as np.uint64 [n_sites + 1]); BcfGpuError with code E_RANGE and .needed = the size when cap_bytes is too small."""
+        text = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        r = np.ascontiguousarray(rec, dtype=abi.VCF_REWRITE)
+        assert len(r) == n_sites
+        c = None if col is None else np.ascontiguousarray(col, np.int32)
+        assert c is None or len(c) == self.cfg.n_smpl
+        off, n = self.buf(8 * (n_sites + 1)), C.c_uint64(0)
+        bufs = [off, self.to_device(text)]
+        args = (n_sites, n_gt_max, C.byref(planes), r.ctypes.data_as(C.POINTER(abi.VcfRewrite)), n_smpl_in,
+                bufs[1].ptr if text.nbytes else None, text.nbytes, None if c is None else c.ctypes.data_as(C.POINTER(C.c_int32)))
+        d_emit = None
+        if emit is not None:
+            bufs.append(self.to_device(np.ascontiguousarray(emit, dtype=np.uint8)))
+            d_emit = bufs[-1].ptr
+        try:
+            if cap_bytes is None:
+                rc = self.L.bcfgpu_call_rewrite_vcf(self.h, *args, d_emit, None, 0, off.ptr, C.byref(n))
+                if rc not in (0, abi.E_RANGE):
+                    check(rc)
+                cap_bytes = n.value
+            out = self.buf(cap_bytes)
+            bufs.append(out)
+            rc = self.L.bcfgpu_call_rewrite_vcf(self.h, *args, d_emit, out.ptr, cap_bytes, off.ptr, C.byref(n))
+            if rc:
+                e = BcfGpuError(rc, self.L.bcfgpu_last_error().decode())
+                e.needed = n.value
+                raise e
+            data, offs = np.zeros(n.value, np.uint8), np.zeros(n_sites + 1, np.uint64)
+            if n.value:
+                out.download(data)
+            off.download(offs)
+        finally:
+            self.release(bufs)
+        return data, offs
+
     def timing(self, on=True):
         check(self.L.bcfgpu_timing_enable(self.h, 1 if on else 0))
 

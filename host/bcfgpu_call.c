@@ -41,8 +41,13 @@
  *              all of them.  The host prints the head up to the FORMAT column and hands both to vio_write_record_text.  A record
  *              stays on the host (the route without options) when an input key other than PL is not stored as integers of at most
  *              255 values, a key is named GT, the record carries GP, or it has more than 16 fields or passes the bound of
- *              include/bcfgpu.h; when no written record does, the GT, PL and GQ planes are not downloaded.  In any other run the
- *              option does nothing.  The same output either way.
+ *              include/bcfgpu.h; when no written record does, the GT, PL and GQ planes are not downloaded.
+ *              With -O v|z and --device-parse in effect (text in, text out) the same for VCF text input: the columns' text stays in
+ *              HBM after the decode and bcfgpu_call_rewrite_vcf rewrites every written record's columns there, token by token -- GT
+ *              in front, the trimmed PL in PL's place (nothing when PL is dropped), the -S sample choice, the Number=R tokens
+ *              following als_map, every other token as the bytes it is, GQ behind.  A Float or String key keeps no record from the
+ *              device here; a record stays on the host when it carries GP, a key is named GT, or it has more than 64 FORMAT keys.
+ *              In any other run the option does nothing.  The same output either way.
  *          --timing: lines on stderr: the seconds (reading records, building the planes on the host, uploads and device stages,
  *              writing records), how many records' planes were decoded on the device, and how many records' FORMAT blocks were
  *              encoded there; with --device-parse given, also how many records' planes were parsed on the device; with --device-keys given, also how many pass-through key blocks were made on the device and on the host;
@@ -425,7 +430,7 @@ typedef struct { int32_t *nals, *unseen, *pl, *ad, *pan, *pac; float *qs, *i16; 
 typedef struct {                                                /* the planes in HBM, and what came down of the results */
     bcfgpu_ctx *ctx;
     int32_t *d_nals, *d_unseen, *d_plin, *d_ad, *d_grp, *d_pan, *d_pac; float *d_qs, *d_i16;
-    void *d_indiv;                                              /* --device-keys, --device-text: kept until the pass-through keys are made */
+    void *d_indiv;                                              /* --device-keys, --device-text: kept until the pass-through keys / the columns are made */
     void *d_site, *d_gt, *d_pl, *d_ploidy, *d_gq, *d_gp;
     bcfgpu_call_site *cs; int8_t *gt; int32_t *opl, *gq; float *gp;
 } dev_t;
@@ -515,7 +520,8 @@ static int parse_options(int argc, char **argv, opt_t *o)
     }
     if (o->gv_n && o->varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (o->gv_n && cals) DIE("-g with -C alleles is not supported\n");
-    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-parse] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-parse] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"
+        "       --device-text acts with -O v|z where --device-input (BCF in) or --device-parse (VCF text in) is in effect\n"); return 2; }
     o->in_path = argv[1]; return 0;
 }
 static void load_ploidy(opt_t *o, ploidy_t *P)
@@ -570,7 +576,7 @@ static vio_file *open_input(opt_t *o, vio_hdr **hdr)
     o->dev_parse = o->dev_parse && !vio_is_bcf(fin) && !cals && !o->gv_n;   /* the same two, for the same reasons, on text input */
     o->dev_rec = o->dev_rec && (o->out_mode == 'u' || o->out_mode == 'b') && !o->gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
     o->dev_keys = o->dev_keys && o->dev_in && o->dev_rec;      /* the input's bytes in HBM and key blocks to splice: both ends on the device */
-    o->dev_text = o->dev_text && o->dev_in && (o->out_mode == 'v' || o->out_mode == 'z');     /* the input's bytes in HBM, text records to write */
+    o->dev_text = o->dev_text && (o->dev_in || o->dev_parse) && (o->out_mode == 'v' || o->out_mode == 'z');   /* the input's bytes or text in HBM, text records to write */
     return fin;
 }
 /* the samples of the header, or those of -S / -s in that order (vcfcall.c:202-344) */
@@ -881,7 +887,7 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
             CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); D->d_ad = dp;
             decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_ad, cmap, namax, D->d_ad);
         }
-        CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL;
+        if (!o->dev_text) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
     } else {
         D->d_plin = dev_upload(ctx, H->pl, (size_t)n * ngmax * S * 4);
         if (H->ad) D->d_ad = dev_upload(ctx, H->ad, (size_t)n * namax * S * 4);
@@ -914,7 +920,8 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
     }
     D->cs = malloc((size_t)n * sizeof *D->cs);
     /* --device-records: the site records alone come down here (and GP); GT, PL and GQ follow as bytes once the writer's header is known.
-     * --device-text: the site records alone; the planes follow only when a written record is left to the host (download_planes) */
+     * --device-text (on either kind of input): the site records alone; the planes follow only when a written record is left to the host
+     * (download_planes) */
     D->gt = dev_rec ? NULL : malloc((size_t)n * 2 * S); D->opl = dev_rec ? NULL : malloc((size_t)n * ngmax * S * 4);
     CHECK(bcfgpu_memcpy_d2h(ctx, D->cs, D->d_site, (size_t)n * sizeof *D->cs));
     if (D->gt) CHECK(bcfgpu_memcpy_d2h(ctx, D->gt, D->d_gt, (size_t)n * 2 * S));
@@ -1080,6 +1087,52 @@ static void encode_text_columns(const opt_t *o, const smap_t *M, const recs_t *R
     encode_two_pass(D->ctx, text_call, &a, "bcfgpu_call_encode_vcf", (size_t)n + 1, &B->tblk, &B->toff);
     CHECK(bcfgpu_free(D->ctx, d_emit)); CHECK(bcfgpu_free(D->ctx, D->d_indiv)); D->d_indiv = NULL;
     free(fld); free(emit);
+    if (n_host) download_planes(M, R, D);                       /* (GP with them: a record that carries it is the host's) */
+}
+
+/* ---- --device-text on text input: the same columns rewritten in HBM from the input's own text where --device-parse left it.  One
+ * bcfgpu_vcf_rewrite per record; a record the device does not rewrite (GP, a key named GT, more than 64 keys) has d_emit = 0 and a
+ * record that only describes its run: the host's route writes it, from planes that come down only then ---- */
+typedef struct { bcfgpu_ctx *ctx; int n, ngmax; bcfgpu_call_out planes; const bcfgpu_vcf_rewrite *rec; int S_in; const void *d_text; size_t l_text;
+                 const int32_t *cmap; const void *d_emit; } rewrite_arg;
+static int rewrite_call(void *arg, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *need)
+{
+    const rewrite_arg *a = arg;
+    return bcfgpu_call_rewrite_vcf(a->ctx, a->n, a->ngmax, &a->planes, a->rec, a->S_in, a->d_text, a->l_text, a->cmap, a->d_emit, d_buf, cap, d_off, need);
+}
+static void rewrite_text_columns(const opt_t *o, const smap_t *M, const recs_t *R, dev_t *D, blocks_t *B)
+{
+    const int n = R->n;
+    uint8_t *emit = malloc((size_t)n + 1);
+    bcfgpu_vcf_rewrite *rw = calloc((size_t)n + 1, sizeof *rw); long n_host = 0;
+    if (!rw) DIE("out of memory\n");
+    for (int k = 0; k < n; ++k) {
+        const rec_t *r = &R->rec[k]; const bcfgpu_call_site *c = &D->cs[k];
+        bcfgpu_vcf_rewrite *w = &rw[k];
+        w->off = r->ioff; w->len = (uint32_t)r->ilen; w->pl_idx = -1; w->n_fmt = 1; w->nals = (int16_t)r->nals;
+        emit[k] = 0;
+        if (c->ret < 0 || (o->varonly && c->ret == 0)) continue;                /* the record loop's rule: not written */
+        const int called = c->nals_new > 1 && c->ret > 0;
+        int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
+        int ok = !(called && D->d_gp) && nk <= BCFGPU_VCF_REWRITE_MAX_KEYS;
+        for (int i = 0; ok && i < nk; ++i) if (!strcmp(keys[i], "GT")) ok = 0;
+        if (ok) {
+            w->n_fmt = (int16_t)nk; w->pl_idx = r->pl_idx;
+            for (int i = 0; i < nk; ++i) if (is_numberR(fmtR, n_fmtR, keys[i], strlen(keys[i]))) w->r_mask |= 1ull << i;
+            w->flags = (c->pl_dropped ? 0 : 1) | (called && D->d_gq ? 2 : 0);
+        }
+        free(keys); free(fmt);
+        emit[k] = (uint8_t)ok;
+        if (ok) ++B->n_tdev; else ++n_host;
+    }
+    rewrite_arg a; memset(&a, 0, sizeof a);
+    a.ctx = D->ctx; a.n = n; a.ngmax = R->ngmax; a.rec = rw; a.S_in = M->S_in; a.d_text = D->d_indiv; a.l_text = R->ibuf_l;
+    a.cmap = o->smpl_file ? (const int32_t *)M->col : NULL;
+    void *d_emit = dev_upload(D->ctx, emit, (size_t)n); a.d_emit = d_emit;
+    a.planes.site = D->d_site; a.planes.gt = D->d_gt; a.planes.pl = D->d_pl; a.planes.gq = D->d_gq;
+    encode_two_pass(D->ctx, rewrite_call, &a, "bcfgpu_call_rewrite_vcf", (size_t)n + 1, &B->tblk, &B->toff);
+    CHECK(bcfgpu_free(D->ctx, d_emit)); CHECK(bcfgpu_free(D->ctx, D->d_indiv)); D->d_indiv = NULL;
+    free(rw); free(emit);
     if (n_host) download_planes(M, R, D);                       /* (GP with them: a record that carries it is the host's) */
 }
 
@@ -1391,7 +1444,7 @@ int main(int argc, char **argv)
     }
     if (o.dev_text) {
         const double te = now_s();
-        encode_text_columns(&o, &M, &R, &D, &B);
+        if (o.dev_parse) rewrite_text_columns(&o, &M, &R, &D, &B); else encode_text_columns(&o, &M, &R, &D, &B);
         t_enc = now_s() - te;
     }
     vio_file *fout = vio_open_write(o.out_path, o.out_mode);

@@ -38,6 +38,8 @@
  *                                           typed-value encoder, for the integer FORMAT keys a call record passes through (AD, DP, SP, ...)
  *    bcfgpu_call_encode_vcf              <- the same three and the text vcf_format writes for them: the sample columns of a call record, the
  *                                           caller's GT / PL / GQ and the pass-through keys interleaved in FORMAT order
+ *    bcfgpu_call_rewrite_vcf             <- the same for VCF text input: the written records' sample columns rewritten token by token
+ *                                           from the input columns' text, around GT, the trimmed PL and GQ
  *
  *  Memory model: all bulk arrays are *device* pointers (HBM).  Hosts that do
  *  not link HIP use bcfgpu_malloc/free/memcpy_*.  Kernels are enqueued on the
@@ -900,6 +902,51 @@ int  bcfgpu_call_encode_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_gt_max, 
                             int32_t n_fields, const bcfgpu_vcf_field *fields,
                             int32_t n_smpl_in, const void *d_indiv, uint64_t n_indiv_bytes, const int32_t *col,
                             const uint8_t *d_emit, void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
+
+/* The same columns where the input is VCF text (vcfcallrw.hip): for every emitted site the bytes the text route appends after the FORMAT
+ * column, rewritten on the device from the input record's own sample columns -- the text bcfgpu_call_decode_vcf parsed, still in HBM --
+ * and the caller's planes.  Text to text is a rewrite of tokens: a pass-through field is copied as the bytes it is, whatever its type
+ * (Integer, Float, String), so no key keeps a record from this entry for its type.  The rule is print_sample_text / print_gt /
+ * print_numberR of host/bcfgpu_call.c over the input column's text, byte for byte.  With nn = site[k].nals_new (1 .. 5),
+ * map = site[k].als_map and ngn = min(nn(nn+1)/2, n_gt_max), called sample s reads input column c = col ? col[s] : s and writes a tab,
+ * then its fields joined by ':' (no newline):
+ *     GT      first, by the GT rule of bcfgpu_call_encode_vcf
+ *     keys    the input column is cut at ':' into nv tokens (nv >= 1: an empty column is one empty token).  For i = 0 .. n_fmt-1:
+ *             at i == pl_idx the PL text by the PL rule of bcfgpu_call_encode_vcf when flags bit 0 is set, nothing -- no ':' either --
+ *             when it is clear; at any other i token i, or '.' when i >= nv.  When i < nv, bit i of r_mask is set and nn != nals the
+ *             token is cut at ',': if it does not hold exactly nals values it stays as it is; else if nn == 1 value 0 is written;
+ *             else nn values, each '.' unless out[map[j]] = value[j] fills it, for every j < nals with map[j] >= 0 in turn.  Tokens
+ *             may be empty and may hold any byte but tab and ':'; the tokens past n_fmt are dropped
+ *     GQ      last, when flags bit 1 is set, by the GQ rule
+ *   planes    DEVICE pointers: site and gt are required; pl when a record's flags bit 0 is set, gq when a bit 1 is; gp is not read
+ *   rec       HOST [n_sites]: one record a site, the sites without a record (d_emit[k] == 0) included: their runs are indexed and
+ *             checked like the others'
+ *   d_text, n_text_bytes, n_smpl_in, col   as for bcfgpu_call_decode_vcf
+ *   d_emit, d_buf, d_off, n_bytes   as for bcfgpu_call_encode_vcf: the texts back to back in site order, d_off[n_sites + 1] 64-bit and
+ *             set whether or not the texts fit, zero length for a site without a record
+ * No sample's input or output is bounded by the LDS stages: a column or a text longer than one is handled by its own lane from or to
+ * global memory.  When the texts do not fit cap_bytes nothing is written to d_buf, *n_bytes is the size needed and the call returns
+ * BCFGPU_E_RANGE (cap_bytes = 0 asks for the size).  BCFGPU_E_ARG, checked before anything is written (d_off included): NULL pointers,
+ * n_fmt outside 1 .. BCFGPU_VCF_REWRITE_MAX_KEYS, nals outside 1 .. 5, n_gt_max outside 1 .. 15, pl_idx >= n_fmt, flags bit 0 with
+ * pl_idx < 0 or planes->pl NULL, flags bit 1 with planes->gq NULL, a col entry outside [0, n_smpl_in), more called samples than input
+ * samples without a map, and -- found by the indexing pass of bcfgpu_call_decode_vcf over every record -- a run whose first byte is no
+ * tab or whose tab count is not n_smpl_in; BCFGPU_E_RANGE when off + len passes n_text_bytes or len passes 1 GiB.  The columns'
+ * offsets are a workspace bounded as bcfgpu_call_decode_vcf's: the kernels run over chunks of that many sites.  n_sites == 0 is valid.
+ * Runs on the context's stream and synchronises it. */
+#define BCFGPU_VCF_REWRITE_MAX_KEYS 64
+typedef struct {            /* one record; 32 bytes */
+    uint64_t off;           /* as bcfgpu_vcf_vec: the tab in front of input sample 0's column */
+    uint64_t r_mask;        /* bit i: input FORMAT key i is declared Number=R */
+    uint32_t len;           /* as bcfgpu_vcf_vec */
+    int32_t  pl_idx;        /* PL's place among the input FORMAT keys; < 0: none */
+    int16_t  n_fmt;         /* keys of the input FORMAT column, 1 .. BCFGPU_VCF_REWRITE_MAX_KEYS */
+    int16_t  nals;          /* alleles of the input record, 1 .. 5 */
+    int32_t  flags;         /* bit 0: the record lists PL (the caller sets it when !pl_dropped); bit 1: it lists GQ */
+} bcfgpu_vcf_rewrite;
+int  bcfgpu_call_rewrite_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_gt_max, const bcfgpu_call_out *planes,
+                             const bcfgpu_vcf_rewrite *rec /* HOST [n_sites] */, int32_t n_smpl_in,
+                             const void *d_text, uint64_t n_text_bytes, const int32_t *col,
+                             const uint8_t *d_emit, void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
 
 /* One communicator over the contexts of a node, rank i = ctxs[i] (RCCL ncclCommInitAll; every context on its own device;
  * librccl is loaded at this call, a single context needs none). */

@@ -37,7 +37,26 @@ namespace bcfgpu {
 // seq_nt16_int packed in nibbles: {4,0,1,4,2,4,4,4,3,4,4,4,4,4,4,4}
 #define NT16_INT_TBL 0x4444444344424104ull
 __device__ __forceinline__ int nt16_int(int c) { return (int)((NT16_INT_TBL >> (4 * (c & 15))) & 7); }
-__device__ __forceinline__ int tri(int j, int k) { return k * (k + 1) / 2 + j; }   // j<=k
+__host__ __device__ constexpr int tri(int j, int k) { return k * (k + 1) / 2 + j; }   // j<=k
+// (j, k) of likelihood z = tri(j, k), z = 0..14, a nibble each (nibble 15: lanes past the last likelihood form (0, 0) and store nothing)
+#define GLF_TRI_J 0x0432103210210100ull
+#define GLF_TRI_K 0x0444443333222110ull
+constexpr bool tri_tables_ok()
+{
+    int z = 0;
+    for (int k = 0; k < 5; ++k) for (int j = 0; j <= k; ++j, ++z)
+        if (tri(j, k) != z || (int)(GLF_TRI_J >> (4 * z) & 15) != j || (int)(GLF_TRI_K >> (4 * z) & 15) != k) return false;
+    return z == 15 && (GLF_TRI_J >> 60) == 0 && (GLF_TRI_K >> 60) == 0;
+}
+static_assert(tri_tables_ok(), "GLF_TRI_J / GLF_TRI_K list (j, k) in the order of tri(j, k)");
+// Lane l's value in every lane (every lane of the wavefront runs this).  ds_bpermute_b32, not v_readlane_b32: no vector ALU
+// instruction, and the values stay out of the scalar registers, which the kernel is short of.
+__device__ __forceinline__ uint32_t lane_u32(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_ds_bpermute(l << 2, (int)x); }
+__device__ __forceinline__ double lane_f64(double x, int l)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
+    return __longlong_as_double((long long)((unsigned long long)lane_u32((uint32_t)(u >> 32), l) << 32 | lane_u32((uint32_t)u, l)));
+}
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {
@@ -643,6 +662,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         // P.trunc (bcfgpu_truncated_cells: cells whose PLs may deviate from a reference run).
         if (__any(cnt_raw > BCFGPU_MAX_DEPTH)) {
             if (cnt_raw > BCFGPU_MAX_DEPTH) {
+                int tw = tid;                                    // (the cell's index, formed here: see cellE below)
+                asm volatile("" : "+v"(tw));
+                const long cellW = cell0 + tw;
                 uint32_t nus = 0;
                 for (int i = 0; i < cnt_raw; ++i) nus += kp_w[i] != 0 ? 1u : 0u;
                 const volatile unsigned long long *t = reinterpret_cast<const volatile unsigned long long*>(P.crp);
@@ -683,13 +705,13 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                         #pragma unroll
                         for (int x = 0; x < 4; ++x) { w->qs[x] = qs[x]; w->ad[x] = af[x] | ar[x] << 16; }
                         w->cnt[0] = cn[0] | cn[1] << 16; w->cnt[1] = cn[2] | cn[3] << 16;
-                        w->scr = sc; w->n = nus; w->cell = (uint32_t)cell; w->pad[0] = w->pad[1] = w->pad[2] = 0;
-                        qs64_p[cell] = WIDE_QS_MARK | slot;      // where combine_kernel's frequency pass finds the record
+                        w->scr = sc; w->n = nus; w->cell = (uint32_t)cellW; w->pad[0] = w->pad[1] = w->pad[2] = 0;
+                        qs64_p[cellW] = WIDE_QS_MARK | slot;      // where combine_kernel's frequency pass finds the record
                         mark = CR_WIDE;
                     }
                     if (!planned) atomicAdd(P.trunc, 1u);
                 }
-                misc_p[cell] = mark;             // read back where the cell's planes are stored (below)
+                misc_p[cellW] = mark;             // read back where the cell's planes are stored (below)
             }
         }
         // the soft-clipped reads, when SCR is asked for (mpileup's default leaves it out): a pass of its own
@@ -747,7 +769,22 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         for (int b = 0; b < 4; ++b) c[b] = (int)((ad64 >> (8 * b)) & 0xff) + (int)((ad64 >> (8 * b + 32)) & 0xff);
         c[4] = (int)n_b4;
         // (b) the other bases present in the wave
-        if (__any(n_other > 0)) {
+        const bool any_other = __any(n_other > 0);
+        if (any_other && __all(n_other <= 1)) {
+            // No cell of the wavefront has two other reads (99 wavefronts in 100 of those that have any): the lane's other read
+            // is kp[0], alone of its base -- the walk of that base is fk[0] * beta[q][0][n] added to +0, the expression of the
+            // loop's "no cell shows a base twice" form below, without the loops over bases and keys.
+            const bool one = n_other == 1 && !dead_cell;
+            const uint32_t k = kp[0];
+            const int b = (int)KEY_B(k);
+            const uint32_t off1 = one ? (KEY_Q(k) << 19) + brow : brow;
+            const double B1 = *reinterpret_cast<const double*>(bbase + off1);
+            const double F1 = one ? s_fk[0] : s_fk[256];
+            double bs = 0.;
+            bs += F1 * B1;
+            #pragma unroll
+            for (int bb = 0; bb < 5; ++bb) if (one && bb == b) bsum[bb] = bs;
+        } else if (any_other) {
             #pragma unroll 1
             for (int b = 0; b < 5; ++b) {
                 int cb = b == 0 ? c[0] : b == 1 ? c[1] : b == 2 ? c[2] : b == 3 ? c[3] : c[4];
@@ -795,6 +832,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
             cr.adr = reinterpret_cast<uint32_t*>(t[4]); cr.cnt4 = reinterpret_cast<uint32_t*>(t[5]);
             cr.misc = reinterpret_cast<uint32_t*>(t[6]);
         }
+        int te = tid;                                            // (the cell's index is formed here again: `cell` need not live
+        asm volatile("" : "+v"(te));                             // through both phases for the stores below)
+        const long cellE = cell0 + te;
         if (part) {
             const int nbases = (c[0] > 0) + (c[1] > 0) + (c[2] > 0) + (c[3] > 0) + (c[4] > 0);
             if (nbases <= 1) {
@@ -805,35 +845,46 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                 for (int k = 1; k < 5; ++k) if (k == b) bsb = bsum[k];
                 float A = n > 0 ? (float)((double)0.0f + bsb) : 0.0f;
                 if (A < 0.0f) A = 0.0f;
-                cr.pa[cell] = A;
+                cr.pa[cellE] = A;
                 code = (uint32_t)b;
             } else {
-                code = CR_FULL;
-                float *p15c = cr.p15 + (size_t)cell * 16;        // the cell's record: 15 likelihoods in 64 bytes
+                code = CR_FULL;                                  // (its 15 likelihoods are formed below, a lane each)
+            }
+        }
+        // A cell with reads of two or more bases (one cell in a hundred; every other wavefront holds one or two): the wavefront
+        // takes them one after the other, the cell's sums and counts handed to every lane, and lane z < 15 forms likelihood
+        // z = tri(j, k) -- errmod_cal's expressions (errmod.c: the float accumulators tmp1 / tmp3 over the bases other than j and
+        // k in ascending order, lhet for j != k), "base i is left out" being a select on the lane's (j, k) around the same additions.
+        if (const uint64_t fmask = __ballot(code == CR_FULL)) {
+            int tl = tid;                                        // (the lane's genotype is formed here, every time: hoisted out of the
+            asm volatile("" : "+v"(tl));                         // rounds it is three more values alive through both phases)
+            const uint32_t lane = (uint32_t)tl & 63u, z = min(lane, 15u);
+            const uint32_t j = (uint32_t)(GLF_TRI_J >> (4 * z)) & 7u, k = (uint32_t)(GLF_TRI_K >> (4 * z)) & 7u;
+            // c[0..3] a byte each (forward + reverse strand: no sum passes n <= 255), c[4] | n << 8
+            const uint32_t cpk = (uint32_t)ad64 + (uint32_t)(ad64 >> 32), c4n = n_b4 | n << 8;
+            for (uint64_t fm = fmask; fm; fm &= fm - 1) {
+                const int l = __builtin_ctzll(fm);                // the lane that owns the cell
+                double bu[5];
                 #pragma unroll
-                for (int j = 0; j < 5; ++j) {
-                    float tmp1 = 0.0f; int tmp2 = 0;
-                    #pragma unroll
-                    for (int k = 0; k < 5; ++k) { if (k == j) continue; tmp1 = (float)((double)tmp1 + bsum[k]); tmp2 += c[k]; }
-                    float v = 0.0f;
-                    if (n > 0 && tmp2) v = tmp1;
-                    if (v < 0.0f) v = 0.0f;
-                    p15c[tri(j, j)] = v;
-                    #pragma unroll
-                    for (int k = j + 1; k < 5; ++k) {
-                        const int cjk = c[j] + c[k];
-                        float t1 = 0.0f; int t2 = 0;
-                        #pragma unroll
-                        for (int i = 0; i < 5; ++i) { if (i == j || i == k) continue; t1 = (float)((double)t1 + bsum[i]); t2 += c[i]; }
-                        float h = 0.0f;
-                        if (n > 0) {
-                            const double lh = -4.343 * P.lhet[cjk << 8 | c[k]];
-                            h = t2 ? (float)(lh + (double)t1) : (float)lh;
-                            if (h < 0.0f) h = 0.0f;
-                        }
-                        p15c[tri(j, k)] = h;
-                    }
+                for (int i = 0; i < 5; ++i) bu[i] = lane_f64(bsum[i], l);
+                const uint32_t c03 = lane_u32(cpk, l), c4nu = lane_u32(c4n, l), nu = c4nu >> 8;
+                const int cj = (int)perm(c4nu, c03, 0x0c0c0c00u | j), ck = (int)perm(c4nu, c03, 0x0c0c0c00u | k);     // byte 4: c[4]
+                const bool het = j != k;
+                float t1 = 0.0f;
+                #pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    const float tn = (float)((double)t1 + bu[i]);
+                    t1 = ((uint32_t)i == j || (uint32_t)i == k) ? t1 : tn;
                 }
+                const int t2 = (int)nu - cj - (het ? ck : 0);      // the reads of the bases other than j and k: n is the sum of c[]
+                float v = 0.0f;
+                if (nu > 0) {
+                    const double lh = -4.343 * P.lhet[het ? (cj + ck) << 8 | ck : 0];
+                    const float h = t2 ? (float)(lh + (double)t1) : (float)lh;
+                    v = het ? h : t2 ? t1 : 0.0f;
+                }
+                if (v < 0.0f) v = 0.0f;
+                if (lane < 15u) cr.p15[(size_t)(cellE + (l - (int)lane)) * 16 + lane] = v;       // the cell's record: 15 likelihoods in 64 bytes
             }
         }
         if (part) {
@@ -846,10 +897,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
             // (an over-deep cell: its mark and its WideRec index were left above; qs64 keeps the index, the packed counts below are
             // those of the 255 reads the likelihoods were made of -- their sum is the n of errmod_cal)
             uint32_t wm = 0;
-            if (cnt_raw > BCFGPU_MAX_DEPTH) wm = *reinterpret_cast<volatile uint32_t*>(&cr.misc[cell]) & CR_WIDE;
-            if (!wm) cr.qs64[cell] = qs64;
-            cr.adf[cell] = (uint32_t)ad64; cr.adr[cell] = (uint32_t)(ad64 >> 32); cr.cnt4[cell] = cnt4;
-            cr.misc[cell] = code | wm | (scr & 0xff) << 8;  // mq0 and ori_depth only feed site totals: site_sums[12..13]
+            if (cnt_raw > BCFGPU_MAX_DEPTH) wm = *reinterpret_cast<volatile uint32_t*>(&cr.misc[cellE]) & CR_WIDE;
+            if (!wm) cr.qs64[cellE] = qs64;
+            cr.adf[cellE] = (uint32_t)ad64; cr.adr[cellE] = (uint32_t)(ad64 >> 32); cr.cnt4[cellE] = cnt4;
+            cr.misc[cellE] = code | wm | (scr & 0xff) << 8;  // mq0 and ori_depth only feed site totals: site_sums[12..13]
             done = true;
         }
         if (nb == 0xffffffffu) break;

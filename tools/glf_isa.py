@@ -24,7 +24,10 @@ Phase B's loops follow, each found by what it holds, not by its label (static co
   rank code   "the quality of every rank joins its counts": the blocks that read and write one slot dword (ds_read_b32 and
               ds_write_b32) with the v_ffbh_u32 blocks around them -- a loop, or the unrolled copies, then counted per copy
   walk        the innermost loops with four global_load_dwordx2 and double-precision arithmetic, with the s_waitcnt that
-              opens the trip; and the walk's start, from the prefix-table load to the loop (walk_start below)"""
+              opens the trip; and the walk's start, from the prefix-table load to the loop (walk_start below)
+
+The straight-line code around the loops comes last (straight_line below): the prologue up to the rounds' loop, the 15
+likelihoods of a cell with two or more bases, and the other bases' short paths."""
 import re
 import sys
 
@@ -129,10 +132,81 @@ def main():
         print("  loop total (static, every block once): v_*=%d readlane=%d writelane=%d ds=%d mem=%d" % (
             tot["v"], tot["rl"], tot["wl"], tot["ds"], tot["gl"]))
         phase_b(bl, parent, {id(b) for b in mem})
+        straight_line(bl, parent, loop)
 
 
 def cnt(ins, *prefix):
     return sum(i.startswith(prefix) for i in ins)
+
+
+def straight_line(bl, parent, phase_a_loop):
+    """The code run once per workgroup or once per cell and round, by content (static counts, every block once):
+      prologue         every block in front of the header of the rounds' loop (the outermost loop around phase A's)
+      two-base cells   the 15 likelihoods of a cell with reads of two or more bases: from the first to the last block that widens a
+                       float accumulator (v_cvt_f64_f32; the single-base store needs none), a loop over such cells when it reads
+                       them with ds_bpermute_b32
+      other bases      the loop over the five bases (the loop around the deepest count_runs loops) without its count_runs, rank
+                       and walk blocks, i.e. its "no cell shows a base twice" path with the key loop; and the one-product form:
+                       the block outside every inner loop with one v_mul_f64, one v_add_f64 and one 8-byte global load"""
+    rounds = phase_a_loop
+    while parent.get(rounds) is not None:
+        rounds = parent[rounds]
+    k0 = next(k for k, b in enumerate(bl) if b["lab"].lstrip(".L") == rounds)
+    pro = [i for b in bl[:k0] for i in b["ins"]]
+    print("  straight-line code:")
+    print("  %-34s %d blocks: v_*=%3d of them v_rcp*=%d v_mad_u64_u32=%d; s_*=%d" % (
+        "prologue, to the rounds' loop", k0, cnt(pro, "v_"), cnt(pro, "v_rcp"), cnt(pro, "v_mad_u64_u32"), cnt(pro, "s_")))
+    wide = [k for k, b in enumerate(bl) if cnt(b["ins"], "v_cvt_f64_f32")]
+    two = set()
+    if wide:
+        # a block inside a loop of its own brings the whole loop; behind the last one, the blocks that still narrow a sum
+        inner = {bl[k]["hdr"] for k in wide if bl[k]["hdr"] != rounds}
+        wide += [k for k, b in enumerate(bl) if b["hdr"] in inner]
+        last = max(wide)
+        while last + 1 < len(bl) and bl[last + 1]["hdr"] == bl[last]["hdr"] and last + 1 - max(wide) <= 3:
+            last += 1
+            if cnt(bl[last]["ins"], "v_cvt_f32_f64"):
+                wide.append(last)
+        mem = bl[min(wide):max(wide) + 1]
+        two = {id(b) for b in mem}
+        ins = [i for b in mem for i in b["ins"]]
+        print("  %-34s from %-9s %2d blocks: v_*=%3d (f64 add/mul/cvt=%d) ds_bpermute=%d mem=%d%s" % (
+            "two-base cells", mem[0]["lab"], len(mem), cnt(ins, "v_"), cnt(ins, "v_add_f64", "v_mul_f64", "v_cvt_f64", "v_cvt_f32_f64"),
+            cnt(ins, "ds_bpermute"), cnt(ins, "global_", "buffer_", "flat_"), "  a loop, a trip a cell" if inner else "  once a wavefront"))
+    def depth(h):
+        d = 1
+        while parent.get(h) is not None:
+            h, d = parent[h], d + 1
+        return d
+    hdrs = {b["hdr"] for b in bl if b["hdr"]}
+    def within(h, loop):
+        while h is not None:
+            if h == loop:
+                return True
+            h = parent.get(h)
+        return False
+    deepest = max((depth(h) for h in hdrs), default=0)
+    counters = [h for h in hdrs if depth(h) == deepest and cnt([i for b in bl if b["hdr"] == h for i in b["ins"]], "ds_add_u32") == 4]
+    if counters and deepest >= 3:
+        base = counters[0]
+        while depth(base) > 2:
+            base = parent[base]
+        # the blocks of the base loop itself and of its inner loops that neither count (ds_add_u32), rank (ds_write_b32) nor walk
+        keep = []
+        for h in hdrs:
+            if within(h, base):
+                ins = [i for b in bl if b["hdr"] and within(b["hdr"], h) for i in b["ins"]]
+                if h == base or not (cnt(ins, "ds_add_u32") or cnt(ins, "ds_write_b32") or cnt(ins, "v_fma_f64", "v_mul_f64") > 1):
+                    keep += [b for b in bl if b["hdr"] == h]
+        ins = [i for b in keep for i in b["ins"]]
+        print("  %-34s header %-9s %2d blocks: v_*=%3d ds=%2d mem=%2d (a trip a base present in the wavefront)" % (
+            "other bases, the loop's short path", base, len(keep), cnt(ins, "v_"), cnt(ins, "ds_"), cnt(ins, "global_", "buffer_", "flat_")))
+    for b in bl:
+        ins = b["ins"]
+        if b["hdr"] == rounds and cnt(ins, "v_mul_f64") == 1 and cnt(ins, "v_add_f64") == 1 and cnt(ins, "global_load_dwordx2") == 1 \
+                and id(b) not in two:
+            print("  %-34s block  %-9s           v_*=%3d ds=%2d mem=%2d" % (
+                "other bases, one product a lane", b["lab"], cnt(ins, "v_"), cnt(ins, "ds_"), cnt(ins, "global_", "buffer_", "flat_")))
 
 
 def phase_b(bl, parent, phase_a):

@@ -545,6 +545,22 @@ static float *grp_q_for(bcfgpu_ctx *c, int n_sites)
     return c->d_grp_q;
 }
 
+// What the stand-alone caller and the fused pipeline hand to launch_mcall alike (m zero-initialised): the sizes, the flags, theta,
+// the tables and workspaces of the context, the PL planes (n_gt_max of them, u8 or int32), ploidy, groups and the output planes.
+static int mcall_params(bcfgpu_ctx *c, McallParams &m, int n_sites, int n_gt_max, int n_al_max, const void *pl, int pl_is_u8,
+                        const uint8_t *ploidy, const int32_t *grp, const bcfgpu_call_out *out)
+{
+    m.n_sites = n_sites; m.n_smpl = c->cfg.n_smpl; m.n_gt_max = n_gt_max; m.n_al_max = n_al_max;
+    m.pl_is_u8 = pl_is_u8; m.call_flag = c->cfg.call_flag; m.output_tags = c->cfg.output_tags; m.n_grp = c->cfg.n_grp;
+    m.theta = c->call_theta_log; m.pl2p = c->d_pl2p;
+    m.pl = pl;
+    m.grp_rng = c->d_grp_rng; m.grp_q = grp_q_for(c, m.n_sites);
+    if (c->cfg.n_grp > 1 && !m.grp_q) return set_err(BCFGPU_E_NOMEM, "call -G: workspace of the groups' frequency sums");
+    m.ploidy = ploidy; m.grp = c->cfg.n_grp > 1 ? grp : nullptr;
+    m.out = *out; m.out_n_gt_max = n_gt_max; m.err = c->d_err;
+    return 0;
+}
+
 int bcfgpu_mcall(bcfgpu_ctx *c, const bcfgpu_call_in *in, const bcfgpu_call_out *out)
 {
     if (!c || !in || !out || !out->site || !out->gt) return set_err(BCFGPU_E_ARG, "bcfgpu_mcall: bad arguments");
@@ -556,14 +572,10 @@ int bcfgpu_mcall(bcfgpu_ctx *c, const bcfgpu_call_in *in, const bcfgpu_call_out 
     if (in->ad && (in->n_al_max < 1 || in->n_al_max > BCFGPU_MAX_ALLELES)) return set_err(BCFGPU_E_ARG, "bcfgpu_mcall: n_al_max out of range");
     hipSetDevice(c->cfg.device);
     McallParams m{};
-    m.n_sites = in->n_sites; m.n_smpl = c->cfg.n_smpl; m.n_gt_max = in->n_gt_max; m.n_al_max = in->n_al_max;
-    m.pl_is_u8 = 0; m.call_flag = c->cfg.call_flag; m.output_tags = c->cfg.output_tags; m.n_grp = c->cfg.n_grp;
-    m.theta = c->call_theta_log; m.pl2p = c->d_pl2p;
-    m.nals = in->nals; m.unseen = in->unseen; m.msite = nullptr; m.pl = in->pl; m.qs = in->qs; m.ad = in->ad;
-    m.grp_rng = c->d_grp_rng; m.grp_q = grp_q_for(c, m.n_sites);
-    if (c->cfg.n_grp > 1 && !m.grp_q) return set_err(BCFGPU_E_NOMEM, "call -G: workspace of the groups' frequency sums");
-    m.ploidy = in->ploidy; m.grp = c->cfg.n_grp > 1 ? in->grp : nullptr; m.prior_an = in->prior_an; m.prior_ac = in->prior_ac; m.i16 = in->i16;
-    m.out = *out; m.out_n_gt_max = in->n_gt_max; m.err = c->d_err;
+    int rc = mcall_params(c, m, in->n_sites, in->n_gt_max, in->n_al_max, in->pl, 0, in->ploidy, in->grp, out);
+    if (rc) return rc;
+    m.nals = in->nals; m.unseen = in->unseen; m.qs = in->qs; m.ad = in->ad;
+    m.prior_an = in->prior_an; m.prior_ac = in->prior_ac; m.i16 = in->i16;
     if (c->timing == 1) hipEventRecord(c->ev[2], c->stream);
     launch_mcall(m, c->stream);
     if (c->timing == 1) { hipEventRecord(c->ev[3], c->stream); hipEventSynchronize(c->ev[3]);
@@ -586,16 +598,11 @@ int bcfgpu_pipeline(bcfgpu_ctx *c, const bcfgpu_tile *tile, const uint8_t *ploid
     rc = enqueue_mpileup(c, tile, mout);
     if (rc) return rc;
     McallParams m{};
-    m.n_sites = tile->n_sites; m.n_smpl = c->cfg.n_smpl; m.n_gt_max = BCFGPU_MAX_PL; m.n_al_max = 5;
-    m.pl_is_u8 = 1; m.call_flag = c->cfg.call_flag; m.output_tags = c->cfg.output_tags; m.n_grp = c->cfg.n_grp;
-    m.theta = c->call_theta_log; m.pl2p = c->d_pl2p;
-    m.msite = mout->site; m.pl = mout->pl; m.qs = nullptr; m.ad = nullptr;
+    rc = mcall_params(c, m, tile->n_sites, BCFGPU_MAX_PL, 5, mout->pl, 1, ploidy, grp, cout);
+    if (rc) return rc;
+    m.msite = mout->site;
     m.qs_i32 = (c->cfg.n_grp > 1 && c->cfg.grp_tag_is_qs) ? mout->qs : nullptr;
     if (c->cfg.n_grp > 1 && !c->cfg.grp_tag_is_qs) { m.ad_u16 = mout->adf; m.ad_u16b = mout->adr; }   // FORMAT/AD = ADF+ADR (bam2bcf.c:892-896)
-    m.grp_rng = c->d_grp_rng; m.grp_q = grp_q_for(c, m.n_sites);
-    if (c->cfg.n_grp > 1 && !m.grp_q) return set_err(BCFGPU_E_NOMEM, "call -G: workspace of the groups' frequency sums");
-    m.ploidy = ploidy; m.grp = c->cfg.n_grp > 1 ? grp : nullptr;
-    m.out = *cout; m.out_n_gt_max = BCFGPU_MAX_PL; m.err = c->d_err;
     launch_mcall(m, c->stream);
     if (c->timing == 1) hipEventRecord(c->ev[3], c->stream);
     else if (c->timing == 2) { hipEventRecord(c->pool[c->pool_used - 1], c->stream); c->pool_call.back() = 1; }

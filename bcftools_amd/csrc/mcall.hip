@@ -22,12 +22,29 @@
 #include <math.h>
 #include "kernels.h"
 #include "kfunc_dev.h"
+#include "mcall_route.h"
+
+// wavefronts per SIMD that the instantiations of mcall_kernel are compiled for (mcall_waves below)
+#ifndef MCALL_WAVES
+#define MCALL_WAVES 4        // the all-diploid FAST instantiations
+#endif
+#ifndef MCALL_WAVES_GRP
+#define MCALL_WAVES_GRP 3    // ... those with sample groups
+#endif
+#ifndef MCALL_WAVES_HAP
+#define MCALL_WAVES_HAP 3    // ... with a ploidy array (two coefficient matrices)
+#endif
+#ifndef MCALL_SMALL_TOO_SAMPLES
+#define MCALL_SMALL_TOO_SAMPLES 256   // launch_mcall: from this many samples on the small instantiation is not launched
+#endif
 
 namespace bcfgpu {
 
-#define WGS 64
-#define MISSING BCFGPU_INT32_MISSING
-#define VEND    BCFGPU_INT32_VECTOR_END
+constexpr int WGS = 64;
+constexpr int MISSING = BCFGPU_INT32_MISSING;
+constexpr int VEND = BCFGPU_INT32_VECTOR_END;
+constexpr double LN2 = 0.693147180559945309417232121458;
+constexpr int NZ_MAX_S = 4096;           // samples up to which the subset scan keeps its notes of who carries data (s_nz)
 
 __device__ __forceinline__ int a2gt(int a, int b) { return a > b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
 __device__ __attribute__((noinline)) double lse2(double a, double b)
@@ -181,7 +198,41 @@ __device__ __forceinline__ double set_pdg_one(const double *pl2p, int (&pl)[NG],
 }
 
 // a group id outside [0, n_grp) is reported by grp_check_kernel (BCFGPU_E_RANGE); clamped here so that it cannot index past the tables
-#define GRP_OF(s_) (min(max(P.grp[s_], 0), ngrp - 1))
+__device__ __forceinline__ int grp_of(const McallParams &P, int s, int ngrp) { return min(max(P.grp[s], 0), ngrp - 1); }
+// the logarithm of a running product kept as (mantissa, binary exponent)
+__device__ __forceinline__ double log_of_product(double m, int e) { return log(m) + (double)e * LN2; }
+// a group's samples lie in [first, last) (grp_check_kernel): consecutive for populations listed one after the other, and then the
+// groups' scans together read every sample once; the start rounded down to a multiple of `align` (a power of two).  (A group no
+// sample belongs to keeps {INT_MAX, 0, 0}: an empty range, not a start that overflows when a lane number is added.)
+__device__ __forceinline__ void group_sample_range(const McallParams &P, int g, int ngrp, int S, int align, int &s_first, int &s_last)
+{
+    s_last = (ngrp > 1 && P.grp_rng) ? P.grp_rng[3 * g + 1] : S;
+    s_first = (ngrp > 1 && P.grp_rng) ? (min(P.grp_rng[3 * g], s_last) & ~(align - 1)) : 0;
+}
+// ploidy bytes (byte j of pw) and membership of group g (bit j of gm) of the samples sb .. sb+3, of which rem = S - sb > 0 exist;
+// ONE: of sample sb alone.  The caller presets pw = 0x02020202 and gm = 0xf and calls this with a ploidy array or groups only.
+template <bool HAP, bool ONE>
+__device__ __forceinline__ void load_ploidy_group(const McallParams &P, int sb, int rem, int g, int ngrp, uint32_t &pw, uint32_t &gm)
+{
+    if (ONE) {
+        if (HAP) pw = P.ploidy[sb];
+        if (ngrp > 1) gm = P.grp[sb] == g ? 1u : 0u;
+    } else if (rem >= 4) {
+        if (HAP) __builtin_memcpy(&pw, P.ploidy + sb, 4);
+        if (ngrp > 1) {
+            int gv[4];
+            __builtin_memcpy(gv, P.grp + sb, 16);
+            gm = (gv[0] == g ? 1u : 0u) | (gv[1] == g ? 2u : 0u) | (gv[2] == g ? 4u : 0u) | (gv[3] == g ? 8u : 0u);
+        }
+    } else {
+        #pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < rem) {
+                if (HAP) pw = (pw & ~(0xffu << (8 * j))) | (uint32_t)P.ploidy[sb + j] << (8 * j);
+                if (ngrp > 1 && grp_of(P, sb + j, ngrp) != g) gm &= ~(1u << j);
+            }
+    }
+}
 __device__ __forceinline__ void write_skipped(bcfgpu_call_site *cs, int ret)
 {
     cs->ret = ret; cs->nals_new = 0; cs->als_new = 0; cs->an = 0; cs->qual = 0; cs->qual_missing = 0; cs->pl_dropped = 0;
@@ -290,26 +341,7 @@ __device__ __forceinline__ void sparse_scan(const McallParams &P, const uint8_t 
             }
         }
         uint32_t pw = 0x02020202u, gm = live ? 0xfu : 0u;
-        if (live && (HAP || ngrp > 1)) {
-            if (SPL == 1) {
-                if (HAP) pw = P.ploidy[sb];
-                if (ngrp > 1) gm = P.grp[sb] == g ? 1u : 0u;
-            } else if (rem >= 4) {
-                if (HAP) __builtin_memcpy(&pw, P.ploidy + sb, 4);
-                if (ngrp > 1) {
-                    int gv[4];
-                    __builtin_memcpy(gv, P.grp + sb, 16);
-                    gm = (gv[0] == g ? 1u : 0u) | (gv[1] == g ? 2u : 0u) | (gv[2] == g ? 4u : 0u) | (gv[3] == g ? 8u : 0u);
-                }
-            } else {
-                #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < rem) {
-                        if (HAP) pw = (pw & ~(0xffu << (8 * j))) | (uint32_t)P.ploidy[sb + j] << (8 * j);
-                        if (ngrp > 1 && GRP_OF(sb + j) != g) gm &= ~(1u << j);
-                    }
-            }
-        }
+        if (live && (HAP || ngrp > 1)) load_ploidy_group<HAP, SPL == 1>(P, sb, rem, g, ngrp, pw, gm);
         uint32_t any = 0;
         #pragma unroll
         for (int c = 0; c < 15; ++c) any |= w[c];
@@ -393,49 +425,38 @@ __device__ __forceinline__ void sparse_scan(const McallParams &P, const uint8_t 
     }
 }
 
-// FAST: the u8-PL case of the fused pipeline (HAP: with a ploidy array; sample groups in both).  The subset scan of find_best_alleles is the
-// product (subset coefficients [rows] x genotypes [k]) * (genotypes [k] x samples [cols]); a row for each sample's
-// normalisation sum comes with it, whose product is divided out at the end.  NSUB <= 15: sparse_scan() above, a lane per sample;
-// NSUB = 25 (five alleles with a frequency): dense tiles on the f64 matrix cores (v_mfma_f64_16x16x4_f64), 16 samples per issue.
-#ifndef MCALL_WAVES
-#define MCALL_WAVES 4        // wavefronts per SIMD of the all-diploid FAST instantiations
-#endif
-template <int MAXA, int NSUB, bool FAST, bool HAP, bool GRP>
-#ifndef MCALL_WAVES_GRP
-#define MCALL_WAVES_GRP 3    // ... of the instantiations with sample groups
-#endif
-#ifndef MCALL_WAVES_HAP
-#define MCALL_WAVES_HAP 3    // ... with a ploidy array (two coefficient matrices)
-#endif
-__global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 : (HAP || GRP) && NSUB > 15 ? 3 : HAP ? MCALL_WAVES_HAP : GRP ? MCALL_WAVES_GRP : MCALL_WAVES, !FAST ? 8 : (HAP || GRP) && NSUB > 15 ? 3 : HAP ? MCALL_WAVES_HAP : GRP ? MCALL_WAVES_GRP : MCALL_WAVES))) void mcall_kernel(const McallParams P)
+// ================================ mcall_kernel's phases, in the order the kernel calls them ================================
+
+// the site's wavefront-uniform values and the two LDS tables every phase reads
+struct Site {
+    int is, S, nals, unseen, ngts, ngrp;
+    float *gq;                  // [ngrp][5] the groups' allele frequencies
+    int *grp_als;               // [ngrp][2] a group's best allele set and the number of its alleles
+};
+// destination of a group's row products (mantissa, exponent; log taken later, one row per lane) and of the HAP product over the
+// samples of ploidy 1 or 2
+struct RowDst { double *m; int *e; double *dip_m; int *dip_e; };
+// FAST && GRP: the arrays of a batch of groups, [GB] or [GB][CPG]
+struct BatchLds {
+    uint32_t *sid;              // a group's subsets: ia | ib << 8 | ic << 16 (0xff: absent)
+    int *nsub, *set, *rede, *dipe, *rals;
+    double *red, *dipm, *rmax, *rsum, *rref, *rqual;
+};
+// the LDS the genotype calling works in: the lane's current sample (column tid, stride WGS)
+struct GtLds {
+    const double *p2;           // FAST: 10^(-PL/10)
+    uint8_t *plb;               // FAST: PL bytes
+    float *gps;                 // genotype posteriors
+    double *pdg; int *plc;      // general: raw P(D|G), PLs after set_pdg's in-place fills
+    int *fill;                  // general: scratch of set_pdg's missing-value path
+};
+
+// ---- the site header: nals / unseen; a site that is refused (ret = -2), skipped, another instantiation's (mcall_route.h) or --
+// with -v -- a REF-only record that never reaches mcall() (vcfcall.c:1112-1115) ends the workgroup: false ----
+template <int MAXA, int NSUB>
+__device__ __forceinline__ bool site_header(const McallParams &P, const int is, const int tid, const bool grouped, int &nals_out, int &unseen_out)
 {
-    constexpr int NG = MAXA * (MAXA + 1) / 2;
-    constexpr int TILES = NSUB >= 16 ? 2 : 1;     // 16-row tiles of the coefficient matrix (subsets + the sum row)
-    extern __shared__ __align__(16) unsigned char dsm[];
-    float *s_gq = reinterpret_cast<float*>(dsm);              // [n_grp][5] group qsum, then [n_grp][2] best allele sets
-    __shared__ CallShared<(FAST && GRP) ? 1 : NSUB> sh;        // (the batched groups of FAST && GRP keep their subsets in s_sid)
-    __shared__ double s_pdg[FAST ? 1 : NG * WGS];   // the lane's current sample: raw P(D|G) (not yet divided by its sum)
-    int *s_fill = reinterpret_cast<int*>(s_pdg);   // scratch of set_pdg's rare missing-value path (used before s_pdg is written)
-    // pass 1: per-lane running products of the subset likelihoods, kept as mantissa (f64) and exponent (i32):
-    //         sum_s log(val_s) = log(prod_s val_s), so each sample costs a multiply + frexp instead of a log()
-    // pass 2: the lane's current sample: PLs after set_pdg's in-place fills, genotype posteriors
-    // FAST: pass 1 = the coefficient matrix; pass 2 = the lane's PL bytes (u8) and genotype posteriors (f32)
-    constexpr int U1 = FAST ? TILES * 16 * 16 * 8 * (HAP ? 2 : 1) : NSUB * WGS * 12, U2 = FAST ? NG * WGS * 5 : NG * WGS * 8,
-                  UB = U1 > U2 ? U1 : U2;
-    __shared__ __align__(8) unsigned char s_union[UB];
-    double *s_man = reinterpret_cast<double*>(s_union);
-    int    *s_exp = reinterpret_cast<int*>(s_union + NSUB * WGS * 8);
-    int    *s_plc = reinterpret_cast<int*>(s_union);
-    float  *s_gps = reinterpret_cast<float*>(s_union + (FAST ? 0 : NG * WGS * 4));
-    uint8_t *s_plb = s_union + NG * WGS * 4;               // FAST only
-
-    const int tid = threadIdx.x;
-    const int is = blockIdx.x;
-    const int S = P.n_smpl;
-    const size_t Ss = (size_t)S;
-    const int ngrp = GRP ? (P.n_grp > 1 ? P.n_grp : 1) : 1;         // GRP = false: launched only for a single group
     bcfgpu_call_site *cs = &P.out.site[is];
-
     int nals, unseen;
     if (P.msite) {
         nals = P.msite[is].n_alleles;
@@ -444,46 +465,45 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
     } else { nals = P.nals[is]; unseen = P.unseen[is]; }
     // (one site per workgroup: the same in every lane -- said so, these decide scalar branches instead of lane masks)
     nals = __builtin_amdgcn_readfirstlane(nals); unseen = __builtin_amdgcn_readfirstlane(unseen);
+    nals_out = nals; unseen_out = unseen;
     if (P.msite && nals == -1) {                                      // nothing to call: the site's call record says "skipped", no error
-        if ((MAXA == 3 || (P.small_too && NSUB == 15)) && tid == 0) write_skipped(cs, 0);
-        return;
+        if (mcall_writes_skip(MAXA, NSUB, P.small_too) && tid == 0) write_skipped(cs, 0);
+        return false;
     }
     const int ngts = nals * (nals + 1) / 2;
     // A record outside what the planes can hold (mcall() itself takes up to 32 alleles, mcall.c:1539; B2B_MAX_ALLELES = 5 is
     // what mpileup writes): refused record by record, ret = -2, and the call as a whole reports BCFGPU_E_RANGE at the next sync.
     if (nals < 1 || nals > BCFGPU_MAX_ALLELES || ngts > P.n_gt_max || (P.ad && nals > P.n_al_max) || unseen < 0 || unseen >= nals) {
-        if ((MAXA == 3 || (P.small_too && NSUB == 15)) && tid == 0) { write_skipped(cs, -2); atomicExch(P.err, BCFGPU_E_RANGE); }
-        return;
+        if (mcall_writes_skip(MAXA, NSUB, P.small_too) && tid == 0) { write_skipped(cs, -2); atomicExch(P.err, BCFGPU_E_RANGE); }
+        return false;
     }
-    // the instantiations share the grid: sites with <=3 alleles run in the small one, the rest in the general ones -- or, with
-    // many samples (launch_mcall), in mcall_kernel<5, 15, ...> as well, and the small one is not launched
-    if (P.small_too ? (nals <= 3 && NSUB == 25) : (nals <= 3) != (MAXA == 3)) return;
-
-    // record-loop prologue of vcfcall.c:1112-1115: with -v a REF-only record never reaches mcall()
+    if (!mcall_may_take(MAXA, NSUB, nals, P.small_too, grouped)) return false;
     if ((P.call_flag & BCFGPU_CALL_VARONLY) && (nals == 1 || (nals == 2 && unseen > 0))) {
         if (tid == 0) write_skipped(cs, 0);
-        return;
+        return false;
     }
-    const double *s_pl2p = P.pl2p;
-    __shared__ double s_p2[FAST ? 264 : 1];                   // 10^(-PL/10), PL = 0..255; [256] = 0: what a sample without data (or a slot past the genotypes) looks up; [257] = 1
-    if constexpr (FAST) {
-        // (the lane's four entries requested together: as a loop this was four round trips, one after the other)
-        const double t0 = P.pl2p[tid], t1 = P.pl2p[tid + WGS], t2 = P.pl2p[tid + 2 * WGS], t3 = P.pl2p[tid + 3 * WGS];
-        s_p2[tid] = t0; s_p2[tid + WGS] = t1; s_p2[tid + 2 * WGS] = t2; s_p2[tid + 3 * WGS] = t3;
-        if (tid < 8) s_p2[256 + tid] = tid == 1 ? 1.0 : 0.0;
-    }   // [257] = 1: the free slot of a sample without data (subset scan)
-    // the subset scan notes which samples carry data, four of them a byte (bit j: sample 4i+j), for the genotypes of a site that
-    // stays REF-only (below); 0x80: no group's scan came by (the planes are read then)
-    constexpr int NZ_MAX_S = 4096;
-    __shared__ __align__(4) uint8_t s_nz[FAST ? NZ_MAX_S / 4 : 4];
-    if constexpr (FAST) { if (S <= NZ_MAX_S) for (int i = tid; i < (S + 15) / 16; i += WGS) reinterpret_cast<uint32_t*>(s_nz)[i] = 0x80808080u; }
+    return true;
+}
 
-    // The 5-allele instantiations split the sites by the number of subsets to visit (LDS for the running products): more
-    // than 15 only when all five alleles have a non-zero frequency (5 + 10 + 10 subsets).  With sample groups the
-    // frequencies are sequential float32 sums over all samples (below): the split is then by the number of alleles alone,
-    // before those sums are formed -- the 25-subset instantiation takes every 5-allele site.
-    if (MAXA == 5 && ngrp > 1 && (nals == 5) != (NSUB == 25)) return;
-    // ---- allele-frequency set-up (mcall.c:1453-1535), sequential float32 ----
+// FAST: s_p2 = 10^(-PL/10), PL = 0..255; [256] = 0: what a sample without data (or a slot past the genotypes) looks up; [257] = 1:
+// the free slot of a sample without data (subset scan).  s_nz: the subset scan notes which samples carry data, four of them a
+// byte (bit j: sample 4i+j), for the genotypes of a site that stays REF-only; 0x80: no group's scan came by (the planes are read then)
+__device__ __forceinline__ void stage_pl_table(const McallParams &P, const int tid, const int S, double *s_p2, uint8_t *s_nz)
+{
+    // (the lane's four entries requested together: as a loop this was four round trips, one after the other)
+    const double t0 = P.pl2p[tid], t1 = P.pl2p[tid + WGS], t2 = P.pl2p[tid + 2 * WGS], t3 = P.pl2p[tid + 3 * WGS];
+    s_p2[tid] = t0; s_p2[tid + WGS] = t1; s_p2[tid + 2 * WGS] = t2; s_p2[tid + 3 * WGS] = t3;
+    if (tid < 8) s_p2[256 + tid] = tid == 1 ? 1.0 : 0.0;
+    if (S <= NZ_MAX_S) for (int i = tid; i < (S + 15) / 16; i += WGS) reinterpret_cast<uint32_t*>(s_nz)[i] = 0x80808080u;
+}
+
+// ---- allele-frequency set-up (mcall.c:1453-1535), sequential float32: the groups' sums, the -F AN,AC prior, normalisation.
+// Returns prior_fail: error("Incorrect AN,AC values") in the reference ----
+template <bool GRP, int N>
+__device__ __forceinline__ bool freq_setup(const McallParams &P, const Site &st, const int tid, CallShared<N> &sh)
+{
+    const int is = st.is, S = st.S, nals = st.nals, ngrp = st.ngrp;
+    float *s_gq = st.gq;
     if (tid == 0) {
         sh.als_new = 0; sh.early = 0; sh.prior_fail = 0;
         sh.max_qual = -HUGE_VAL; sh.ref_lk = -HUGE_VAL; sh.lk_sum = -HUGE_VAL;
@@ -511,7 +531,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
             while (nac < 4 && acv[nac] != VEND) nac++;
             if (an > 0 && nac == nals - 1) {
                 int gn = 0;
-                if (ngrp == 1) gn = S; else for (int s = 0; s < S; ++s) gn += (GRP_OF(s) == g);
+                if (ngrp == 1) gn = S; else for (int s = 0; s < S; ++s) gn += (grp_of(P, s, ngrp) == g);
                 int ac0 = an;
                 for (int i = 0; i < nals - 1; i++) {
                     if (acv[i] == VEND) break;
@@ -528,622 +548,681 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
         if (sum != 0.f) for (int i = 0; i < nals; i++) q[i] /= sum;
     }
     __syncthreads();
-    if (sh.prior_fail) {                  // error("Incorrect AN,AC values") in the reference
-        if (tid == 0) write_skipped(cs, -1);
-        return;
-    }
-    int *grp_als_tab = reinterpret_cast<int*>(s_gq + ngrp * 5);
-    // The 5-allele instantiations split the sites by the number of subsets to visit (LDS for the running products): more
-    // than 15 only when all five alleles have a non-zero frequency (5 + 10 + 10 subsets), in any group -- decided once
-    // per site, before the groups are walked, so that exactly one instantiation takes the site.
-    if (MAXA == 5 && ngrp == 1) {
-        bool five = false;
-        if (nals == 5)
-            for (int g = 0; g < ngrp; ++g) {
-                const float *q = s_gq + g * 5;
-                five = five || (q[0] != 0.f && q[1] != 0.f && q[2] != 0.f && q[3] != 0.f && q[4] != 0.f);
-            }
-        if (five != (NSUB == 25)) return;
-    }
+    return sh.prior_fail != 0;
+}
+// an ungrouped site whose five alleles all have a non-zero frequency: 5 + 10 + 10 subsets to visit
+__device__ __forceinline__ bool five_frequencies(const Site &st)
+{
+    const float *q = st.gq;
+    return st.nals == 5 && q[0] != 0.f && q[1] != 0.f && q[2] != 0.f && q[3] != 0.f && q[4] != 0.f;
+}
 
-    // ---- per group: mcall_find_best_alleles ----
-    // BATCH (the matrix-core scan with sample groups): what a group costs beside its scan -- the enumeration of its subsets, the
-    // logarithms of its row products, the maximum / log-sum-exp over its subsets -- is done for several groups at once, CPG
-    // lanes a group (a 64-lane wavefront holds GB = 64 / CPG groups), and the coefficient matrix of a group is formed in
-    // registers from the subset list instead of being staged through LDS: no workgroup barrier inside a batch but the two
-    // around its last step.  (One group after the other, each with its own set-up and reductions, was 1 450 of a site's
-    // instructions per group: profiles/r4_mcall_grp_probe.txt.)
-    constexpr bool BATCH = FAST && GRP;
-    const int CPG = ngrp == 1 ? 64 : (NSUB > 15 ? 32 : 16), GB = 64 / CPG;
-    __shared__ uint32_t s_sid[BATCH ? 64 : 1];            // [GB][CPG] a group's subsets: ia | ib << 8 | ic << 16 (0xff: absent)
-    __shared__ int s_nsub[BATCH ? 4 : 1], s_set[BATCH ? 4 : 1], s_rede2[BATCH ? 64 : 1], s_dipe[BATCH ? 4 : 1], s_rals[BATCH ? 4 : 1];
-    __shared__ double s_red2[BATCH ? 64 : 1], s_dipm[BATCH ? 4 : 1], s_rmax[BATCH ? 4 : 1], s_rsum[BATCH ? 4 : 1], s_rref[BATCH ? 4 : 1], s_rqual[BATCH ? 4 : 1];
-    for (int g = 0; g < ngrp; ++g) {
-        if constexpr (BATCH) {
-            if (g % GB == 0) {
-                // the subsets of the batch's groups: lane (group, candidate of the canonical enumeration), compacted per group
-                __syncthreads();
-                const int gl = tid / CPG, c = tid % CPG, gg = g + gl;
-                const float *qf = s_gq + (gg < ngrp ? gg : ngrp - 1) * 5;
-                const int npair = nals > 1 ? nals * (nals - 1) / 2 : 0;
-                const int ntrip = nals > 2 ? nals * (nals - 1) * (nals - 2) / 6 : 0;
-                int ia = 0xff, ib = 0xff, ic = 0xff;
-                bool valid = false;
-                if (c < nals) { ia = c; valid = true; }
-                else if (c < nals + npair) {
-                    const int cc = c - nals;
-                    ia = 1; while ((ia + 1) * ia / 2 <= cc) ia++;
-                    ib = cc - ia * (ia - 1) / 2;
-                    valid = qf[ia] != 0 && qf[ib] != 0;
-                } else if (c < nals + npair + ntrip) {
-                    int cc = c - nals - npair;
-                    ia = 2; while ((ia + 1) * ia * (ia - 1) / 6 <= cc) ia++;
-                    cc -= ia * (ia - 1) * (ia - 2) / 6;
-                    ib = 1; while ((ib + 1) * ib / 2 <= cc) ib++;
-                    ic = cc - ib * (ib - 1) / 2;
-                    valid = qf[ia] != 0 && qf[ib] != 0 && qf[ic] != 0;
-                }
-                valid = valid && gg < ngrp;
-                const unsigned long long bal = __ballot(valid);
-                const unsigned long long seg = CPG == 64 ? bal : (bal >> (gl * CPG)) & ((1ull << CPG) - 1);
-                if (valid) s_sid[gl * CPG + __popcll(seg & ((1ull << c) - 1))] = (uint32_t)ia | (uint32_t)ib << 8 | (uint32_t)ic << 16;
-                if (c == 0) s_nsub[gl] = __popcll(seg);
-                __syncthreads();
-            }
-        } else {
-        __syncthreads();
-        if (tid < 5) sh.qsum[tid] = s_gq[g * 5 + tid];
-        __syncthreads();
-        // the subsets that mcall.c:600-698 visits, in its order (singles, pairs, triples; alleles of zero frequency are
-        // skipped), with their frequency products: candidate c of the canonical enumeration is decoded by lane c and
-        // the surviving ones are compacted in order
-        {
-            const float *qf = sh.qsum;
-            const int npair = nals > 1 ? nals * (nals - 1) / 2 : 0;
-            const int ntrip = nals > 2 ? nals * (nals - 1) * (nals - 2) / 6 : 0;
-            int ia = -1, ib = -1, ic = -1;
-            bool valid = false;
-            if (tid < nals) { ia = tid; valid = true; }
-            else if (tid < nals + npair) {
-                const int c = tid - nals;
-                ia = 1; while ((ia + 1) * ia / 2 <= c) ia++;
-                ib = c - ia * (ia - 1) / 2;
-                valid = qf[ia] != 0 && qf[ib] != 0;
-            } else if (tid < nals + npair + ntrip) {
-                int c = tid - nals - npair;
-                ia = 2; while ((ia + 1) * ia * (ia - 1) / 6 <= c) ia++;
-                c -= ia * (ia - 1) * (ia - 2) / 6;
-                ib = 1; while ((ib + 1) * ib / 2 <= c) ib++;
-                ic = c - ib * (ib - 1) / 2;
-                valid = qf[ia] != 0 && qf[ib] != 0 && qf[ic] != 0;
-            }
-            const unsigned long long bal = __ballot(valid);
-            if (valid) {
-                Subset &t = sh.sub[__popcll(bal & ((1ull << tid) - 1))];
-                t.ia = ia; t.ib = ib; t.ic = ic;
-                t.iaa = (ia + 1) * (ia + 2) / 2 - 1;
-                t.ibb = t.icc = t.iab = t.iac = t.ibc = 0;
-                t.fa = t.fa2 = 1; t.fb = t.fc = t.fb2 = t.fc2 = t.fab = t.fac = t.fbc = 0;
-                if (ib >= 0 && ic < 0) {
-                    t.ibb = (ib + 1) * (ib + 2) / 2 - 1; t.iab = t.iaa - ia + ib;
-                    t.fa = (double)(qf[ia] / (qf[ia] + qf[ib])); t.fb = (double)(qf[ib] / (qf[ia] + qf[ib]));
-                    t.fa2 = t.fa * t.fa; t.fb2 = t.fb * t.fb; t.fab = 2 * t.fa * t.fb;
-                } else if (ic >= 0) {
-                    t.ibb = (ib + 1) * (ib + 2) / 2 - 1; t.icc = (ic + 1) * (ic + 2) / 2 - 1;
-                    t.iab = t.iaa - ia + ib; t.iac = t.iaa - ia + ic; t.ibc = t.ibb - ib + ic;
-                    const float den = qf[ia] + qf[ib] + qf[ic];
-                    t.fa = (double)(qf[ia] / den); t.fb = (double)(qf[ib] / den); t.fc = (double)(qf[ic] / den);
-                    t.fa2 = t.fa * t.fa; t.fb2 = t.fb * t.fb; t.fc2 = t.fc * t.fc;
-                    t.fab = 2 * t.fa * t.fb; t.fac = 2 * t.fa * t.fc; t.fbc = 2 * t.fb * t.fc;
-                }
-            }
-            if (tid == 0) sh.nsub = __popcll(bal);
+// ---- the subset enumeration ----
+// Candidate c of the canonical enumeration (singles, pairs, triples) -> its alleles, ABSENT where it has fewer; returns whether
+// mcall.c:600-698 visits it (alleles of zero frequency are skipped).
+template <int ABSENT>
+__device__ __forceinline__ bool subset_candidate(const int c, const int nals, const float *qf, int &ia, int &ib, int &ic)
+{
+    const int npair = nals > 1 ? nals * (nals - 1) / 2 : 0;
+    const int ntrip = nals > 2 ? nals * (nals - 1) * (nals - 2) / 6 : 0;
+    ia = ABSENT; ib = ABSENT; ic = ABSENT;
+    bool valid = false;
+    if (c < nals) { ia = c; valid = true; }
+    else if (c < nals + npair) {
+        const int cc = c - nals;
+        ia = 1; while ((ia + 1) * ia / 2 <= cc) ia++;
+        ib = cc - ia * (ia - 1) / 2;
+        valid = qf[ia] != 0 && qf[ib] != 0;
+    } else if (c < nals + npair + ntrip) {
+        int cc = c - nals - npair;
+        ia = 2; while ((ia + 1) * ia * (ia - 1) / 6 <= cc) ia++;
+        cc -= ia * (ia - 1) * (ia - 2) / 6;
+        ib = 1; while ((ib + 1) * ib / 2 <= cc) ib++;
+        ic = cc - ib * (ib - 1) / 2;
+        valid = qf[ia] != 0 && qf[ib] != 0 && qf[ic] != 0;
+    }
+    return valid;
+}
+// BATCH (the FAST instantiations with sample groups): what a group costs beside its scan -- the enumeration of its subsets, the
+// logarithms of its row products, the maximum / log-sum-exp over its subsets -- is done for several groups at once, CPG
+// lanes a group (a 64-lane wavefront holds GB = 64 / CPG groups), and the coefficient matrix of a group is formed in
+// registers from the subset list instead of being staged through LDS: no workgroup barrier inside a batch but the two
+// around its last step.  (One group after the other, each with its own set-up and reductions, was 1 450 of a site's
+// instructions per group: profiles/r4_mcall_grp_probe.txt.)
+// The subsets of the batch's groups g .. g + GB - 1: lane (group, candidate), compacted per group
+__device__ __forceinline__ void enumerate_batch(const Site &st, int tid, const int g, const int CPG, const BatchLds &bl)
+{
+    asm volatile("" : "+v"(tid));        // (as in sparse_scan: the lane's masks are formed here, per batch, not held in registers through the loop over the groups)
+    __syncthreads();
+    const int gl = tid / CPG, c = tid % CPG, gg = g + gl;
+    const float *qf = st.gq + (gg < st.ngrp ? gg : st.ngrp - 1) * 5;
+    int ia, ib, ic;
+    bool valid = subset_candidate<0xff>(c, st.nals, qf, ia, ib, ic);
+    valid = valid && gg < st.ngrp;
+    const unsigned long long bal = __ballot(valid);
+    const unsigned long long seg = CPG == 64 ? bal : (bal >> (gl * CPG)) & ((1ull << CPG) - 1);
+    if (valid) bl.sid[gl * CPG + __popcll(seg & ((1ull << c) - 1))] = (uint32_t)ia | (uint32_t)ib << 8 | (uint32_t)ic << 16;
+    if (c == 0) bl.nsub[gl] = __popcll(seg);
+    __syncthreads();
+}
+// One group: the subsets that mcall.c:600-698 visits, in its order, with their genotype indices and frequency products:
+// candidate c is decoded by lane c and the surviving ones are compacted in order
+template <int N>
+__device__ __forceinline__ void enumerate_group(const Site &st, const int tid, const int g, CallShared<N> &sh)
+{
+    __syncthreads();
+    if (tid < 5) sh.qsum[tid] = st.gq[g * 5 + tid];
+    __syncthreads();
+    const float *qf = sh.qsum;
+    int ia, ib, ic;
+    const bool valid = subset_candidate<-1>(tid, st.nals, qf, ia, ib, ic);
+    const unsigned long long bal = __ballot(valid);
+    if (valid) {
+        Subset &t = sh.sub[__popcll(bal & ((1ull << tid) - 1))];
+        t.ia = ia; t.ib = ib; t.ic = ic;
+        t.iaa = (ia + 1) * (ia + 2) / 2 - 1;
+        t.ibb = t.icc = t.iab = t.iac = t.ibc = 0;
+        t.fa = t.fa2 = 1; t.fb = t.fc = t.fb2 = t.fc2 = t.fab = t.fac = t.fbc = 0;
+        if (ib >= 0 && ic < 0) {
+            t.ibb = (ib + 1) * (ib + 2) / 2 - 1; t.iab = t.iaa - ia + ib;
+            t.fa = (double)(qf[ia] / (qf[ia] + qf[ib])); t.fb = (double)(qf[ib] / (qf[ia] + qf[ib]));
+            t.fa2 = t.fa * t.fa; t.fb2 = t.fb * t.fb; t.fab = 2 * t.fa * t.fb;
+        } else if (ic >= 0) {
+            t.ibb = (ib + 1) * (ib + 2) / 2 - 1; t.icc = (ic + 1) * (ic + 2) / 2 - 1;
+            t.iab = t.iaa - ia + ib; t.iac = t.iaa - ia + ic; t.ibc = t.ibb - ib + ic;
+            const float den = qf[ia] + qf[ib] + qf[ic];
+            t.fa = (double)(qf[ia] / den); t.fb = (double)(qf[ib] / den); t.fc = (double)(qf[ic] / den);
+            t.fa2 = t.fa * t.fa; t.fb2 = t.fb * t.fb; t.fc2 = t.fc * t.fc;
+            t.fab = 2 * t.fa * t.fb; t.fac = 2 * t.fa * t.fc; t.fbc = 2 * t.fb * t.fc;
         }
-        __syncthreads();
+    }
+    if (tid == 0) sh.nsub = __popcll(bal);
+    __syncthreads();
+}
+
+// ---- the three subset scans.  Each leaves a group's row products in `dst` and returns the lane's part of `setbits`: the rows
+// some sample entered ----
+// FAST: the u8-PL case of the fused pipeline (HAP: with a ploidy array; sample groups in both).  The subset scan of find_best_alleles is the
+// product (subset coefficients [rows] x genotypes [k]) * (genotypes [k] x samples [cols]); a row for each sample's
+// normalisation sum comes with it, whose product is divided out at the end.  NSUB <= 15: sparse_scan() above, a lane per sample;
+// NSUB = 25 (five alleles with a frequency): dense tiles on the f64 matrix cores (v_mfma_f64_16x16x4_f64), 16 samples per issue.
+template <int NZ, bool HAP, typename... A>
+__device__ __forceinline__ void sparse_scan_by_span(const bool narrow, A &&...a)
+{
+    // (a range of at most 128 samples -- a small group, few samples -- is scanned a sample a lane)
+    if (narrow) sparse_scan<NZ, HAP, 1>(a...);
+    else sparse_scan<NZ, HAP, 4>(a...);
+}
+// the scan a lane per sample: every site but those of the 25-subset instantiation
+template <bool HAP>
+__device__ __forceinline__ int scan_sparse(const McallParams &P, const Site &st, const int tid, const int g, const int nsub,
+                                           const double *s_p2, uint8_t *s_nz, const RowDst &dst)
+{
+    const int S = st.S, nals = st.nals, ngrp = st.ngrp;
+    const float *qf = st.gq + g * 5;
+    uint32_t nzm = 0;
+    #pragma unroll
+    for (int a = 0; a < 5; ++a) if (a < nals && qf[a] != 0.f) nzm |= 1u << a;
+    nzm = __builtin_amdgcn_readfirstlane(nzm);
+    const int nz = __popc(nzm);
+    uint32_t permw = 0;
+    {
+        int n = 0;
+        #pragma unroll
+        for (int a = 0; a < 5; ++a) if (a < nals && ((nzm >> a) & 1)) { permw |= (uint32_t)a << (4 * n); ++n; }
+        #pragma unroll
+        for (int a = 0; a < 5; ++a) if (a < nals && !((nzm >> a) & 1)) { permw |= (uint32_t)a << (4 * n); ++n; }
+    }
+    const uint8_t *plb = reinterpret_cast<const uint8_t*>(P.pl) + (size_t)st.is * BCFGPU_MAX_PL * (size_t)S;
+    int s_first, s_last;
+    group_sample_range(P, g, ngrp, S, 4, s_first, s_last);
+    double rm = 1.0, dm = 1.0; int re = 0, de = 0;
+    bool f_single = false, f_pt = false;
+    const bool note = S <= NZ_MAX_S;
+    const bool narrow = s_last - s_first <= 2 * WGS;
+    switch (nz) {
+    case 4:  sparse_scan_by_span<4, HAP>(narrow, P, plb, S, nals, g, ngrp, s_first, s_last, qf, permw, s_p2, s_nz, note, rm, re, dm, de, f_single, f_pt); break;
+    case 3:  sparse_scan_by_span<3, HAP>(narrow, P, plb, S, nals, g, ngrp, s_first, s_last, qf, permw, s_p2, s_nz, note, rm, re, dm, de, f_single, f_pt); break;
+    case 2:  sparse_scan_by_span<2, HAP>(narrow, P, plb, S, nals, g, ngrp, s_first, s_last, qf, permw, s_p2, s_nz, note, rm, re, dm, de, f_single, f_pt); break;
+    default: sparse_scan_by_span<1, HAP>(narrow, P, plb, S, nals, g, ngrp, s_first, s_last, qf, permw, s_p2, s_nz, note, rm, re, dm, de, f_single, f_pt); break;
+    }
+    // slot -> the row of the subset list: single allele x -> its own index, pairs and triples in visiting order, the sums last
+    const int np = nz * (nz - 1) / 2, nt = nz * (nz - 1) * (nz - 2) / 6;
+    const int slot = tid >> 2;
+    int row = -1;
+    if (slot < 5) { if (slot < nals) row = (int)((permw >> (4 * slot)) & 7); }
+    else if (slot < 5 + np + nt) row = nals + slot - 5;
+    else if (slot == 5 + np + nt) row = nsub;
+    if ((tid & 3) == 0 && row >= 0) { dst.m[row] = rm; dst.e[row] = re; }
+    if (HAP && tid == 0) { *dst.dip_m = dm; *dst.dip_e = de; }
+    // the rows some sample entered: the single alleles and the sums with any sample that has data, pairs and triples with
+    // one of ploidy 1 or 2 among them
+    const int single_rows = ((1 << nals) - 1) | (1 << nsub);
+    return (f_single ? single_rows : 0) | (f_pt ? ((1 << nsub) - 1) & ~((1 << nals) - 1) : 0);
+}
+
+// The lane's elements of the matrix-core scan's coefficient matrices, rows col (+ 16 t), genotypes 4 kk + kq.  BATCH: straight from
+// the subset list: genotype k = (x <= y) has f_x f_y (twice that when x != y) if both alleles are in the subset; the
+// frequencies inside the subset are float quotients, widened (mcall.c:629-630, 671-673); the haploid matrix has
+// f_x on the homozygous genotypes (mcall.c:643, 688); row nsub is the all-ones row of the normalisation sums
+template <int TILES, bool HAP>
+__device__ __forceinline__ void coef_from_subsets(const float *qf, const uint32_t *sid_g, const int nsub, const int col, const int (&gpk)[4],
+                                                  const uint32_t (&nodata)[4], double (&a)[TILES][4], double (&ah)[HAP ? TILES : 1][4])
+{
+    #pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+        const int row = t * 16 + col;
+        const uint32_t sid = row < nsub ? sid_g[row] : 0xffffffu;
+        const int ia = (int)(sid & 0xff), ib = (int)((sid >> 8) & 0xff), ic = (int)((sid >> 16) & 0xff);
+        double fa = 1.0, fb = 0.0, fc = 0.0;
+        if (row < nsub && ib != 0xff) {
+            if (ic == 0xff) { const float den = qf[ia] + qf[ib]; fa = (double)(qf[ia] / den); fb = (double)(qf[ib] / den); }
+            else { const float den = qf[ia] + qf[ib] + qf[ic]; fa = (double)(qf[ia] / den); fb = (double)(qf[ib] / den); fc = (double)(qf[ic] / den); }
         }
-        const int nsub = BATCH ? s_nsub[g % GB] : sh.nsub;
-        int setbits = 0;
-        if constexpr (FAST && NSUB <= 15) {
-            // ---- subset scan, a lane per sample (sparse_scan above): every site but those of the 25-subset instantiation ----
-            const float *qf = s_gq + g * 5;
-            uint32_t nzm = 0;
-            #pragma unroll
-            for (int a = 0; a < 5; ++a) if (a < nals && qf[a] != 0.f) nzm |= 1u << a;
-            nzm = __builtin_amdgcn_readfirstlane(nzm);
-            const int nz = __popc(nzm);
-            uint32_t permw = 0;
-            {
-                int n = 0;
-                #pragma unroll
-                for (int a = 0; a < 5; ++a) if (a < nals && ((nzm >> a) & 1)) { permw |= (uint32_t)a << (4 * n); ++n; }
-                #pragma unroll
-                for (int a = 0; a < 5; ++a) if (a < nals && !((nzm >> a) & 1)) { permw |= (uint32_t)a << (4 * n); ++n; }
-            }
-            const uint8_t *plb = reinterpret_cast<const uint8_t*>(P.pl) + (size_t)is * BCFGPU_MAX_PL * Ss;
-            // a group's samples lie in [first, last] (grp_range_kernel): consecutive for populations listed one after the
-            // other, and then the groups' scans together read every sample once
-            const int s_last = (ngrp > 1 && P.grp_rng) ? P.grp_rng[3 * g + 1] : S;
-            const int s_first = (ngrp > 1 && P.grp_rng) ? (min(P.grp_rng[3 * g], s_last) & ~3) : 0;
-            double rm = 1.0, dm = 1.0; int re = 0, de = 0;
-            bool f_single = false, f_pt = false;
-            const bool note = S <= NZ_MAX_S;
-            // (a range of at most 128 samples -- a small group, few samples -- is scanned a sample a lane)
-            const bool narrow = s_last - s_first <= 2 * WGS;
-            #define SCAN(NZ_) do { if (narrow) sparse_scan<NZ_, HAP, 1>(P, plb, S, nals, g, ngrp, s_first, s_last, qf, permw, s_p2, s_nz, note, rm, re, dm, de, f_single, f_pt); \
-                                   else sparse_scan<NZ_, HAP, 4>(P, plb, S, nals, g, ngrp, s_first, s_last, qf, permw, s_p2, s_nz, note, rm, re, dm, de, f_single, f_pt); } while (0)
-            switch (nz) {
-            case 4:  SCAN(4); break;
-            case 3:  SCAN(3); break;
-            case 2:  SCAN(2); break;
-            default: SCAN(1); break;
-            }
-            #undef SCAN
-            // slot -> the row of the subset list: single allele x -> its own index, pairs and triples in visiting order, the sums last
-            const int np = nz * (nz - 1) / 2, nt = nz * (nz - 1) * (nz - 2) / 6;
-            const int slot = tid >> 2;
-            int row = -1;
-            if (slot < 5) { if (slot < nals) row = (int)((permw >> (4 * slot)) & 7); }
-            else if (slot < 5 + np + nt) row = nals + slot - 5;
-            else if (slot == 5 + np + nt) row = nsub;
-            if ((tid & 3) == 0 && row >= 0) {
-                if constexpr (BATCH) { s_red2[(g % GB) * CPG + row] = rm; s_rede2[(g % GB) * CPG + row] = re; }
-                else { sh.red[row] = rm; sh.rede[row] = re; }      // log taken below, one row per lane
-            }
-            if (HAP && tid == 0) {
-                if constexpr (BATCH) { s_dipm[g % GB] = dm; s_dipe[g % GB] = de; }
-                else { sh.red[31] = dm; sh.rede[31] = de; }        // (at most 16 rows are in use)
-            }
-            if constexpr (!BATCH) {
-            __syncthreads();
-            if (tid <= nsub || (HAP && tid == 31)) sh.red[tid] = log(sh.red[tid]) + (double)sh.rede[tid] * 0.693147180559945309417232121458;
-            __syncthreads();
-            if (HAP && tid == 0) sh.red_dip = sh.red[31];
-            }
-            // the rows some sample entered: the single alleles and the sums with any sample that has data, pairs and triples with
-            // one of ploidy 1 or 2 among them
-            const int single_rows = ((1 << nals) - 1) | (1 << nsub);
-            setbits = (f_single ? single_rows : 0) | (f_pt ? ((1 << nsub) - 1) & ~((1 << nals) - 1) : 0);
-        } else if constexpr (FAST) {
-            // ---- subset scan on the matrix cores ----
-            // Rows = subsets (+ an all-ones row for the samples' normalisation sums), columns = samples, k = genotypes.
-            // Haploid samples use a second coefficient matrix (f_a P(aa) + f_b P(bb) [+ f_c P(cc)], mcall.c:643,688);
-            // samples of other groups, of ploidy 0 (pairs/triples only) or without data contribute nothing.
-            const int col = tid & 15, kq = tid >> 4;
-            // Slot k = 4 kk + kq of the products' inner dimension -> genotype: the homozygous genotypes first, then the heterozygous
-            // ones in index order, nothing past ngts.  The haploid matrix has coefficients on the homozygous genotypes only, so its
-            // product ends after the first nals slots, and the diploid one after ngts of the 16: a 4-allele site (10 genotypes)
-            // takes 3 + 1 matrix instructions per 16 samples instead of 4 + 4.
-            int gpk[4];
+        #pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const int k = gpk[kk] >= 0 ? gpk[kk] : 15;          // (genotype 15 = (0,5): an allele no subset holds)
+            const int y = (int)((0x5444443333222110ull >> (4 * k)) & 15), x = k - y * (y + 1) / 2;
+            const double fx = x == ia ? fa : x == ib ? fb : x == ic ? fc : 0.0, fy = y == ia ? fa : y == ib ? fb : y == ic ? fc : 0.0;
+            double av = 0.0, hv = 0.0;
+            if (row < nsub) { av = x == y ? fx * fx : 2 * fy * fx; hv = x == y ? fx : 0.0; }
+            else if (row == nsub) av = gpk[kk] >= 0 ? 1.0 : 0.0;
+            a[t][kk] = nodata[kk] == 257u ? 1.0 : av;
+            if (HAP) ah[t][kk] = hv;
+        }
+    }
+}
+// ... one group at a time: staged through LDS from the Subset list, s_coef = [TILES*16 rows][16 genotypes] (HAP: + the haploid rows)
+template <int TILES, bool HAP>
+__device__ __forceinline__ void coef_through_lds(double *s_coef, const Subset *sub, const int nsub, const int ngts, const int tid, const int col,
+                                                 const int (&gpk)[4], const uint32_t (&nodata)[4], double (&a)[TILES][4], double (&ah)[HAP ? TILES : 1][4])
+{
+    double *s_coefh = s_coef + TILES * 256;
+    for (int i = tid; i < TILES * 256 * (HAP ? 2 : 1); i += WGS) s_coef[i] = 0.0;
+    __syncthreads();
+    if (tid < nsub) {
+        const Subset &u = sub[tid];
+        double *row = s_coef + tid * 16;
+        if (u.ib < 0) row[u.iaa] = 1.0;
+        else {
+            row[u.iaa] = u.fa2; row[u.ibb] = u.fb2; row[u.iab] = u.fab;
+            if (u.ic >= 0) { row[u.icc] = u.fc2; row[u.iac] = u.fac; row[u.ibc] = u.fbc; }
+        }
+        if (HAP) {
+            double *rh = s_coefh + tid * 16;
+            rh[u.iaa] = u.fa;
+            if (u.ib >= 0) rh[u.ibb] = u.fb;
+            if (u.ic >= 0) rh[u.icc] = u.fc;
+        }
+    }
+    if (tid < ngts) s_coef[nsub * 16 + tid] = 1.0;                  // the sum row
+    __syncthreads();
+    #pragma unroll
+    for (int t = 0; t < TILES; ++t)
+        #pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            a[t][kk] = gpk[kk] >= 0 ? s_coef[(t * 16 + col) * 16 + gpk[kk]] : nodata[kk] == 257u ? 1.0 : 0.0;
+            if (HAP) ah[t][kk] = gpk[kk] >= 0 ? s_coefh[(t * 16 + col) * 16 + gpk[kk]] : 0.0;
+        }
+}
+// The scan on the matrix cores.  Rows = subsets (+ an all-ones row for the samples' normalisation sums), columns = samples,
+// k = genotypes.  Haploid samples use a second coefficient matrix (f_a P(aa) + f_b P(bb) [+ f_c P(cc)], mcall.c:643,688);
+// samples of other groups, of ploidy 0 (pairs/triples only) or without data contribute nothing.
+template <int TILES, bool HAP, bool BATCH>
+__device__ __forceinline__ int scan_matrix(const McallParams &P, const Site &st, const int tid, const int g, const int nsub, const uint32_t *sid_g,
+                                           const Subset *sub, double *s_coef, const double *s_p2, uint8_t *s_nz, const RowDst &dst)
+{
+    const int S = st.S, nals = st.nals, ngts = st.ngts, ngrp = st.ngrp;
+    const size_t Ss = (size_t)S;
+    int setbits = 0;
+    const int col = tid & 15, kq = tid >> 4;
+    // Slot k = 4 kk + kq of the products' inner dimension -> genotype: the homozygous genotypes first, then the heterozygous
+    // ones in index order, nothing past ngts.  The haploid matrix has coefficients on the homozygous genotypes only, so its
+    // product ends after the first nals slots, and the diploid one after ngts of the 16: a 4-allele site (10 genotypes)
+    // takes 3 + 1 matrix instructions per 16 samples instead of 4 + 4.
+    int gpk[4];
+    #pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        const int sl = 4 * kk + kq;
+        gpk[kk] = sl < nals ? (sl + 1) * (sl + 2) / 2 - 1 : sl < ngts ? (int)((0xDCBA876431ull >> (4 * (sl - nals))) & 15) : -1;
+    }
+    // Without a ploidy array, slot ngts -- the first one past the genotypes, always inside the last block of four the products
+    // visit (ngts is 1, 3, 6, 10 or 15) -- carries the coefficient 1 in every row and the value 1 for a sample that is not
+    // scanned (no data, another group), 0 for one that is: every product of such a sample is exactly 1, the products of the
+    // others are what they were (+ 0.0), and the running products take them all without a test.
+    uint32_t nodata[4];
+    #pragma unroll
+    for (int kk = 0; kk < 4; ++kk) nodata[kk] = (!HAP && 4 * kk + kq == ngts) ? 257u : 256u;
+    double a[TILES][4], ah[HAP ? TILES : 1][4];
+    if constexpr (BATCH) coef_from_subsets<TILES, HAP>(st.gq + g * 5, sid_g, nsub, col, gpk, nodata, a, ah);
+    else coef_through_lds<TILES, HAP>(s_coef, sub, nsub, ngts, tid, col, gpk, nodata, a, ah);
+    // this lane accumulates rows kq + 4r (+16t) over the sample columns col, col+16, ...
+    double man[TILES][4]; int ex[TILES][4];
+    #pragma unroll
+    for (int t = 0; t < TILES; ++t)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) { man[t][r] = 1.0; ex[t][r] = 0; }
+    double sdm = 1.0; int sde = 0;                                   // HAP: the sum row over ploidy-1/2 samples
+    int singles = 0;                                                // bit t*4+r: a row without ploidy term
+    #pragma unroll
+    for (int t = 0; t < TILES; ++t)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) { const int row = t * 16 + kq + 4 * r; if (row < nals || row == nsub) singles |= 1 << (t * 4 + r); }
+    const uint8_t *plb = reinterpret_cast<const uint8_t*>(P.pl) + (size_t)st.is * BCFGPU_MAX_PL * Ss;
+    // A lane takes 16 consecutive samples of a 256-sample block: the sixteen 4-byte loads of its four plane groups (and the
+    // ploidy / group words) are all issued before the first use, so a block costs one memory round trip -- with
+    // four wavefronts per SIMD the scan is bound by such round trips.  Word q of the block holds the samples
+    // sb+4q .. sb+4q+3; one matrix product covers the 16 lanes' samples sb+4q+j.
+    // (few samples: 4*nq consecutive samples per lane with nq = 2 or 1, so that the 16 lanes' columns stay filled)
+    int s_first, s_last;
+    group_sample_range(P, g, ngrp, S, 4, s_first, s_last);
+    const int span = s_last - s_first;
+    const int nq = span > 128 ? 4 : span > 64 ? 2 : 1;
+    for (int s0 = s_first; s0 < s_last; s0 += 64 * nq) {
+        const int sb0 = s0 + 4 * nq * col;
+        uint32_t wq[4][4], pwq[4], gmq[4];
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (q >= nq) break;
+            const int sb = sb0 + 4 * q, rem = S - sb;
+            uint32_t pw = 0x02020202u, gmask = 0xf;                 // ploidy bytes and group membership of the 4 samples
+            if (rem <= 0) gmask = 0;
+            else if (HAP || ngrp > 1) load_ploidy_group<HAP, false>(P, sb, rem, g, ngrp, pw, gmask);
+            pwq[q] = pw; gmq[q] = gmask;
+            // the plane of slot 4kk+kq, samples sb .. sb+3 as one word; samples past the end read as "no data"
             #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                const int sl = 4 * kk + kq;
-                gpk[kk] = sl < nals ? (sl + 1) * (sl + 2) / 2 - 1 : sl < ngts ? (int)((0xDCBA876431ull >> (4 * (sl - nals))) & 15) : -1;
+                const int k = gpk[kk];
+                uint32_t v = 0;
+                if (k >= 0 && rem > 0) {
+                    const uint8_t *src = plb + (size_t)k * Ss + sb;
+                    if (rem >= 4) __builtin_memcpy(&v, src, 4);
+                    else { v = src[0]; if (rem > 1) v |= (uint32_t)src[1] << 8; if (rem > 2) v |= (uint32_t)src[2] << 16; }
+                }
+                wq[q][kk] = v;
             }
-            // Without a ploidy array, slot ngts -- the first one past the genotypes, always inside the last block of four the products
-            // visit (ngts is 1, 3, 6, 10 or 15) -- carries the coefficient 1 in every row and the value 1 for a sample that is not
-            // scanned (no data, another group), 0 for one that is: every product of such a sample is exactly 1, the products of the
-            // others are what they were (+ 0.0), and the running products take them all without a test.
-            uint32_t nodata[4];
+        }
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t pw = pwq[q], gmask = gmq[q];
+            const uint32_t (&w)[4] = wq[q];
+            if (q >= nq) break;
+            if (ngrp > 1 && !__any(gmask != 0)) continue;              // no sample of this group in this word of the 16 lanes
+            // set_pdg: a sample whose PLs are all 0 (sum == n_gt) carries no data and is skipped (mcall.c:529-535)
+            uint32_t any = w[0] | w[1] | w[2] | w[3];
+            any |= __shfl_xor(any, 16);
+            any |= __shfl_xor(any, 32);
+            if (kq == 0 && S <= NZ_MAX_S && sb0 + 4 * q < S)
+                s_nz[(sb0 + 4 * q) >> 2] = (uint8_t)(((any & 0xffu) ? 1u : 0u) | ((any & 0xff00u) ? 2u : 0u) | ((any & 0xff0000u) ? 4u : 0u) | ((any & 0xff000000u) ? 8u : 0u));
             #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) nodata[kk] = (!HAP && 4 * kk + kq == ngts) ? 257u : 256u;
-            double a[TILES][4], ah[HAP ? TILES : 1][4];
-            if constexpr (BATCH) {
-                // the lane's elements of the coefficient matrices, rows col (+ 16 t), genotypes 4 kk + kq, straight from the subset
-                // list: genotype k = (x <= y) has f_x f_y (twice that when x != y) if both alleles are in the subset; the
-                // frequencies inside the subset are float quotients, widened (mcall.c:629-630, 671-673); the haploid matrix has
-                // f_x on the homozygous genotypes (mcall.c:643, 688); row nsub is the all-ones row of the normalisation sums
-                const float *qf = s_gq + g * 5;
+            for (int j = 0; j < 4; ++j) {
+                const bool has = ((any >> (8 * j)) & 0xff) != 0 && ((gmask >> j) & 1);
+                const int pd = (int)((pw >> (8 * j)) & 0xff);
+                if (!HAP && has) setbits = (1 << (TILES * 4)) - 1;       // (a scanned sample's products are all positive)
+                double b[4];
+                #pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+                    b[kk] = s_p2[has ? (gpk[kk] >= 0 ? (w[kk] >> (8 * j)) & 0xff : 256u) : nodata[kk]];    // (an unconditional look-up: no branch around the read; the next sample's look-ups requested a sample ahead: slower)
                 #pragma unroll
                 for (int t = 0; t < TILES; ++t) {
-                    const int row = t * 16 + col;
-                    const uint32_t sid = row < nsub ? s_sid[(g % GB) * CPG + row] : 0xffffffu;
-                    const int ia = (int)(sid & 0xff), ib = (int)((sid >> 8) & 0xff), ic = (int)((sid >> 16) & 0xff);
-                    double fa = 1.0, fb = 0.0, fc = 0.0;
-                    if (row < nsub && ib != 0xff) {
-                        if (ic == 0xff) { const float den = qf[ia] + qf[ib]; fa = (double)(qf[ia] / den); fb = (double)(qf[ib] / den); }
-                        else { const float den = qf[ia] + qf[ib] + qf[ic]; fa = (double)(qf[ia] / den); fb = (double)(qf[ib] / den); fc = (double)(qf[ic] / den); }
-                    }
+                    d4_t d = {0., 0., 0., 0.}, dh = {0., 0., 0., 0.};
                     #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        const int k = gpk[kk] >= 0 ? gpk[kk] : 15;          // (genotype 15 = (0,5): an allele no subset holds)
-                        const int y = (int)((0x5444443333222110ull >> (4 * k)) & 15), x = k - y * (y + 1) / 2;
-                        const double fx = x == ia ? fa : x == ib ? fb : x == ic ? fc : 0.0, fy = y == ia ? fa : y == ib ? fb : y == ic ? fc : 0.0;
-                        double av = 0.0, hv = 0.0;
-                        if (row < nsub) { av = x == y ? fx * fx : 2 * fy * fx; hv = x == y ? fx : 0.0; }
-                        else if (row == nsub) av = gpk[kk] >= 0 ? 1.0 : 0.0;
-                        a[t][kk] = nodata[kk] == 257u ? 1.0 : av;
-                        if (HAP) ah[t][kk] = hv;
-                    }
-                }
-            } else {
-            double *s_coef = reinterpret_cast<double*>(s_union);            // [TILES*16 rows][16 genotypes]
-            double *s_coefh = s_coef + TILES * 256;                         // HAP: the haploid rows
-            for (int i = tid; i < TILES * 256 * (HAP ? 2 : 1); i += WGS) s_coef[i] = 0.0;
-            __syncthreads();
-            if (tid < nsub) {
-                const Subset &u = sh.sub[tid];
-                double *row = s_coef + tid * 16;
-                if (u.ib < 0) row[u.iaa] = 1.0;
-                else {
-                    row[u.iaa] = u.fa2; row[u.ibb] = u.fb2; row[u.iab] = u.fab;
-                    if (u.ic >= 0) { row[u.icc] = u.fc2; row[u.iac] = u.fac; row[u.ibc] = u.fbc; }
-                }
-                if (HAP) {
-                    double *rh = s_coefh + tid * 16;
-                    rh[u.iaa] = u.fa;
-                    if (u.ib >= 0) rh[u.ibb] = u.fb;
-                    if (u.ic >= 0) rh[u.icc] = u.fc;
-                }
-            }
-            if (tid < ngts) s_coef[nsub * 16 + tid] = 1.0;                  // the sum row
-            __syncthreads();
-            #pragma unroll
-            for (int t = 0; t < TILES; ++t)
-                #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    a[t][kk] = gpk[kk] >= 0 ? s_coef[(t * 16 + col) * 16 + gpk[kk]] : nodata[kk] == 257u ? 1.0 : 0.0;
-                    if (HAP) ah[t][kk] = gpk[kk] >= 0 ? s_coefh[(t * 16 + col) * 16 + gpk[kk]] : 0.0;
-                }
-            }
-            // this lane accumulates rows kq + 4r (+16t) over the sample columns col, col+16, ...
-            double man[TILES][4]; int ex[TILES][4];
-            #pragma unroll
-            for (int t = 0; t < TILES; ++t)
-                #pragma unroll
-                for (int r = 0; r < 4; ++r) { man[t][r] = 1.0; ex[t][r] = 0; }
-            double sdm = 1.0; int sde = 0;                                   // HAP: the sum row over ploidy-1/2 samples
-            int singles = 0;                                                // bit t*4+r: a row without ploidy term
-            #pragma unroll
-            for (int t = 0; t < TILES; ++t)
-                #pragma unroll
-                for (int r = 0; r < 4; ++r) { const int row = t * 16 + kq + 4 * r; if (row < nals || row == nsub) singles |= 1 << (t * 4 + r); }
-            const uint8_t *plb = reinterpret_cast<const uint8_t*>(P.pl) + (size_t)is * BCFGPU_MAX_PL * Ss;
-            // A lane takes 16 consecutive samples of a 256-sample block: the sixteen 4-byte loads of its four plane groups (and the
-            // ploidy / group words) are all issued before the first use, so a block costs one memory round trip -- with
-            // four wavefronts per SIMD the scan is bound by such round trips.  Word q of the block holds the samples
-            // sb+4q .. sb+4q+3; one matrix product covers the 16 lanes' samples sb+4q+j.
-            // (few samples: 4*nq consecutive samples per lane with nq = 2 or 1, so that the 16 lanes' columns stay filled)
-            // a group's samples lie in [first, last] (grp_range_kernel): consecutive for populations listed one after the
-            // other, and then the groups' scans together read every sample once
-            const int s_last = (ngrp > 1 && P.grp_rng) ? P.grp_rng[3 * g + 1] : S;
-            const int s_first = (ngrp > 1 && P.grp_rng) ? (min(P.grp_rng[3 * g], s_last) & ~3) : 0;
-            const int span = s_last - s_first;
-            const int nq = span > 128 ? 4 : span > 64 ? 2 : 1;
-            for (int s0 = s_first; s0 < s_last; s0 += 64 * nq) {
-                const int sb0 = s0 + 4 * nq * col;
-                uint32_t wq[4][4], pwq[4], gmq[4];
-                #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (q >= nq) break;
-                    const int sb = sb0 + 4 * q, rem = S - sb;
-                    uint32_t pw = 0x02020202u, gmask = 0xf;                 // ploidy bytes and group membership of the 4 samples
-                    if (rem <= 0) gmask = 0;
-                    else if (HAP || ngrp > 1) {
-                        if (rem >= 4) {
-                            if (HAP) __builtin_memcpy(&pw, P.ploidy + sb, 4);
-                            if (ngrp > 1) {
-                                int gv[4];
-                                __builtin_memcpy(gv, P.grp + sb, 16);
-                                gmask = (gv[0] == g ? 1u : 0u) | (gv[1] == g ? 2u : 0u) | (gv[2] == g ? 4u : 0u) | (gv[3] == g ? 8u : 0u);
-                            }
-                        } else {
-                            #pragma unroll
-                            for (int j = 0; j < 4; ++j)
-                                if (j < rem) {
-                                    if (HAP) pw = (pw & ~(0xffu << (8 * j))) | (uint32_t)P.ploidy[sb + j] << (8 * j);
-                                    if (ngrp > 1 && GRP_OF(sb + j) != g) gmask &= ~(1u << j);
-                                }
-                        }
-                    }
-                    pwq[q] = pw; gmq[q] = gmask;
-                    // the plane of slot 4kk+kq, samples sb .. sb+3 as one word; samples past the end read as "no data"
-                    #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        const int k = gpk[kk];
-                        uint32_t v = 0;
-                        if (k >= 0 && rem > 0) {
-                            const uint8_t *src = plb + (size_t)k * Ss + sb;
-                            if (rem >= 4) __builtin_memcpy(&v, src, 4);
-                            else { v = src[0]; if (rem > 1) v |= (uint32_t)src[1] << 8; if (rem > 2) v |= (uint32_t)src[2] << 16; }
-                        }
-                        wq[q][kk] = v;
-                    }
-                }
-                #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                const uint32_t pw = pwq[q], gmask = gmq[q];
-                const uint32_t (&w)[4] = wq[q];
-                if (q >= nq) break;
-                if (ngrp > 1 && !__any(gmask != 0)) continue;              // no sample of this group in this word of the 16 lanes
-                // set_pdg: a sample whose PLs are all 0 (sum == n_gt) carries no data and is skipped (mcall.c:529-535)
-                uint32_t any = w[0] | w[1] | w[2] | w[3];
-                any |= __shfl_xor(any, 16);
-                any |= __shfl_xor(any, 32);
-                if (kq == 0 && S <= NZ_MAX_S && sb0 + 4 * q < S)
-                    s_nz[(sb0 + 4 * q) >> 2] = (uint8_t)(((any & 0xffu) ? 1u : 0u) | ((any & 0xff00u) ? 2u : 0u) | ((any & 0xff0000u) ? 4u : 0u) | ((any & 0xff000000u) ? 8u : 0u));
-                #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool has = ((any >> (8 * j)) & 0xff) != 0 && ((gmask >> j) & 1);
-                    const int pd = (int)((pw >> (8 * j)) & 0xff);
-                    if (!HAP && has) setbits = (1 << (TILES * 4)) - 1;       // (a scanned sample's products are all positive)
-                    double b[4];
-                    #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk)
-                        b[kk] = s_p2[has ? (gpk[kk] >= 0 ? (w[kk] >> (8 * j)) & 0xff : 256u) : nodata[kk]];    // (an unconditional look-up: no branch around the read; the next sample's look-ups requested a sample ahead: slower)
-                    #pragma unroll
-                    for (int t = 0; t < TILES; ++t) {
-                        d4_t d = {0., 0., 0., 0.}, dh = {0., 0., 0., 0.};
+                    for (int kk = 0; kk < 4; ++kk) if (4 * kk < ngts) d = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t][kk], b[kk], d, 0, 0, 0);
+                    if (HAP) {
                         #pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) if (4 * kk < ngts) d = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t][kk], b[kk], d, 0, 0, 0);
-                        if (HAP) {
-                            #pragma unroll
-                            for (int kk = 0; kk < 2; ++kk) if (4 * kk < nals) dh = __builtin_amdgcn_mfma_f64_16x16x4f64(ah[t][kk], b[kk], dh, 0, 0, 0);
-                        }
+                        for (int kk = 0; kk < 2; ++kk) if (4 * kk < nals) dh = __builtin_amdgcn_mfma_f64_16x16x4f64(ah[t][kk], b[kk], dh, 0, 0, 0);
+                    }
+                    #pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double v = d[r];
+                        if (HAP && !((singles >> (t * 4 + r)) & 1)) v = pd == 2 ? d[r] : pd == 1 ? dh[r] : 0.0;
+                        if constexpr (!HAP) man[t][r] *= v;
+                        else if (v != 0.0) { man[t][r] *= v; setbits |= 1 << (t * 4 + r); }
+                        if (HAP && t * 16 + kq + 4 * r == nsub && (pd == 1 || pd == 2) && d[r] != 0.0) sdm *= d[r];
+                    }
+                }
+                // (renormalised once per word of four samples: four factors are at least 1e-102 together, far from the range's end, and
+                // splitting off a power of two is exact whenever it is done; every other sample was 1 % slower, every eighth no faster)
+                if (j == 3) {
+                    #pragma unroll
+                    for (int t = 0; t < TILES; ++t)
                         #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            double v = d[r];
-                            if (HAP && !((singles >> (t * 4 + r)) & 1)) v = pd == 2 ? d[r] : pd == 1 ? dh[r] : 0.0;
-                            if constexpr (!HAP) man[t][r] *= v;
-                            else if (v != 0.0) { man[t][r] *= v; setbits |= 1 << (t * 4 + r); }
-                            if (HAP && t * 16 + kq + 4 * r == nsub && (pd == 1 || pd == 2) && d[r] != 0.0) sdm *= d[r];
-                        }
-                    }
-                    // (renormalised once per word of four samples: four factors are at least 1e-102 together, far from the range's end, and
-                    // splitting off a power of two is exact whenever it is done; every other sample was 1 % slower, every eighth no faster)
-                    if (j == 3) {
-                        #pragma unroll
-                        for (int t = 0; t < TILES; ++t)
-                            #pragma unroll
-                            for (int r = 0; r < 4; ++r) { ex[t][r] += frexp_exp(man[t][r]); man[t][r] = frexp_mant(man[t][r]); }
-                        if (HAP) { sde += frexp_exp(sdm); sdm = frexp_mant(sdm); }
-                    }
-                }
-                }
-            }
-            // product over the 16 sample columns of each row, then rows -> sh.red[]
-            int rowbits = 0;
-            #pragma unroll
-            for (int t = 0; t < TILES; ++t)
-                #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double m = man[t][r]; int e = ex[t][r]; int f = (setbits >> (t * 4 + r)) & 1;
-                    row16_product(m, e, f);
-                    const int row = t * 16 + kq + 4 * r;
-                    if (col == 0 && row <= nsub) {
-                        if constexpr (BATCH) { s_red2[(g % GB) * CPG + row] = m; s_rede2[(g % GB) * CPG + row] = e; }
-                        else { sh.red[row] = m; sh.rede[row] = e; }  // log taken below, one row per lane
-                        if (f) rowbits |= 1 << row;
-                    }
-                }
-            if (HAP) {
-                double m = sdm; int e = sde, f_ = 0;
-                row16_product(m, e, f_);
-                if (col == 0 && kq == (nsub & 3)) {
-                    if constexpr (BATCH) { s_dipm[g % GB] = m; s_dipe[g % GB] = e; }
-                    else { sh.red[31] = m; sh.rede[31] = e; }      // (at most 26 rows are in use)
-                }
-            }
-            if constexpr (!BATCH) {
-            __syncthreads();
-            if (tid <= nsub || (HAP && tid == 31)) sh.red[tid] = log(sh.red[tid]) + (double)sh.rede[tid] * 0.693147180559945309417232121458;
-            __syncthreads();
-            if (HAP && tid == 0) sh.red_dip = sh.red[31];
-            }
-            setbits = rowbits;
-        } else {
-        for (int t = 0; t < nsub; ++t) { s_man[t * WGS + tid] = 1.0; s_exp[t * WGS + tid] = 0; }
-        // (a group no sample belongs to keeps {INT_MAX, 0, 0}: an empty range, not a start that overflows when tid is added)
-        const int g_last = (ngrp > 1 && P.grp_rng) ? P.grp_rng[3 * g + 1] : S;
-        const int g_first = (ngrp > 1 && P.grp_rng) ? min(P.grp_rng[3 * g], g_last) : 0;
-        for (int s = g_first + tid; s < g_last; s += WGS) {
-            if (ngrp > 1 && GRP_OF(s) != g) continue;
-            int pl[NG]; double pdg[NG];
-            load_pl<NG>(P, is, s, ngts, pl);
-            const double psum = set_pdg_one<NG>(s_pl2p, pl, pdg, ngts, nals, unseen, s_fill + tid);
-            // normalised first, as set_pdg does (mcall.c:541): with PLs past ~3000 a term can be subnormal, and the reference's
-            // `if (val)` (mcall.c:644, 689) must see the same value -- a product of raw terms scaled afterwards can reach 0 on
-            // one side only, and then a row is -inf here and finite there
-            #pragma unroll
-            for (int k = 0; k < NG; ++k) s_pdg[k * WGS + tid] = psum != 0.0 ? pdg[k] / psum : 0.0;
-            const int ploidy = P.ploidy ? P.ploidy[s] : 2;
-            for (int t = 0; t < nsub; ++t) {
-                const Subset &u = sh.sub[t];
-                double val;
-                const double paa = s_pdg[u.iaa * WGS + tid];
-                if (u.ib < 0) val = paa;                                   // single allele: no ploidy term (mcall.c:607-611)
-                else {
-                    const double pbb = s_pdg[u.ibb * WGS + tid];
-                    if (u.ic < 0) {
-                        if (ploidy == 2) val = u.fa2 * paa + u.fb2 * pbb + u.fab * s_pdg[u.iab * WGS + tid];
-                        else if (ploidy == 1) val = u.fa * paa + u.fb * pbb;
-                        else val = 0;
-                    } else {
-                        const double pcc = s_pdg[u.icc * WGS + tid];
-                        if (ploidy == 2)
-                            val = u.fa2 * paa + u.fb2 * pbb + u.fc2 * pcc + u.fab * s_pdg[u.iab * WGS + tid]
-                                + u.fac * s_pdg[u.iac * WGS + tid] + u.fbc * s_pdg[u.ibc * WGS + tid];
-                        else if (ploidy == 1) val = u.fa * paa + u.fb * pbb + u.fc * pcc;
-                        else val = 0;
-                    }
-                }
-                if (val != 0.0) {
-                    // (val split before it is multiplied in: a subnormal factor would lose bits or round the product to 0)
-                    const double m = s_man[t * WGS + tid] * frexp_mant(val);
-                    s_man[t * WGS + tid] = frexp_mant(m);
-                    s_exp[t * WGS + tid] += frexp_exp(val) + frexp_exp(m);
-                    setbits |= 1 << t;
+                        for (int r = 0; r < 4; ++r) { ex[t][r] += frexp_exp(man[t][r]); man[t][r] = frexp_mant(man[t][r]); }
+                    if (HAP) { sde += frexp_exp(sdm); sdm = frexp_mant(sdm); }
                 }
             }
         }
+    }
+    // product over the 16 sample columns of each row, then rows -> dst
+    int rowbits = 0;
+    #pragma unroll
+    for (int t = 0; t < TILES; ++t)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double m = man[t][r]; int e = ex[t][r]; int f = (setbits >> (t * 4 + r)) & 1;
+            row16_product(m, e, f);
+            const int row = t * 16 + kq + 4 * r;
+            if (col == 0 && row <= nsub) {
+                dst.m[row] = m; dst.e[row] = e;
+                if (f) rowbits |= 1 << row;
+            }
+        }
+    if (HAP) {
+        double m = sdm; int e = sde, f_ = 0;
+        row16_product(m, e, f_);
+        if (col == 0 && kq == (nsub & 3)) { *dst.dip_m = m; *dst.dip_e = e; }
+    }
+    return rowbits;
+}
+// FAST, one group at a time: the logarithms of the row products the scan left in sh.red / sh.rede ([31]: the HAP product), one row per lane
+template <bool HAP, int N>
+__device__ __forceinline__ void rows_to_logs(CallShared<N> &sh, const int nsub, const int tid)
+{
+    __syncthreads();
+    if (tid <= nsub || (HAP && tid == 31)) sh.red[tid] = log_of_product(sh.red[tid], sh.rede[tid]);
+    __syncthreads();
+    if (HAP && tid == 0) sh.red_dip = sh.red[31];
+}
+
+// The general scan (missing PLs, int32 PLs of a VCF): a lane per sample, its P(D|G) in the lane's LDS column, per-lane running
+// products of the subset likelihoods kept as mantissa (f64) and exponent (i32): sum_s log(val_s) = log(prod_s val_s), so each
+// sample costs a multiply + frexp instead of a log().  Leaves the logarithms in red[].
+template <int NG>
+__device__ __forceinline__ int scan_general(const McallParams &P, const Site &st, const int tid, const int g, const int nsub, const Subset *sub,
+                                            double *s_man, int *s_exp, double *s_pdg, int *s_fill, double *red)
+{
+    const int ngrp = st.ngrp;
+    int setbits = 0;
+    for (int t = 0; t < nsub; ++t) { s_man[t * WGS + tid] = 1.0; s_exp[t * WGS + tid] = 0; }
+    int g_first, g_last;
+    group_sample_range(P, g, ngrp, st.S, 1, g_first, g_last);
+    for (int s = g_first + tid; s < g_last; s += WGS) {
+        if (ngrp > 1 && grp_of(P, s, ngrp) != g) continue;
+        int pl[NG]; double pdg[NG];
+        load_pl<NG>(P, st.is, s, st.ngts, pl);
+        const double psum = set_pdg_one<NG>(P.pl2p, pl, pdg, st.ngts, st.nals, st.unseen, s_fill + tid);
+        // normalised first, as set_pdg does (mcall.c:541): with PLs past ~3000 a term can be subnormal, and the reference's
+        // `if (val)` (mcall.c:644, 689) must see the same value -- a product of raw terms scaled afterwards can reach 0 on
+        // one side only, and then a row is -inf here and finite there
+        #pragma unroll
+        for (int k = 0; k < NG; ++k) s_pdg[k * WGS + tid] = psum != 0.0 ? pdg[k] / psum : 0.0;
+        const int ploidy = P.ploidy ? P.ploidy[s] : 2;
         for (int t = 0; t < nsub; ++t) {
-            // wave product of the mantissas (renormalised at every step) and sum of the exponents
-            double m = s_man[t * WGS + tid]; int e = s_exp[t * WGS + tid];
-            #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double mm = m * __shfl_xor(m, o);
-                e += __shfl_xor(e, o) + frexp_exp(mm);
-                m = frexp_mant(mm);
-            }
-            if (tid == 0) sh.red[t] = log(m) + (double)e * 0.693147180559945309417232121458;
-        }
-        }
-        setbits = wor(setbits);
-        if constexpr (BATCH) {
-            if (tid == 0) s_set[g % GB] = setbits;
-            if (g % GB != GB - 1 && g != ngrp - 1) continue;             // the batch goes on: its groups are finished together
-            // ---- the batch's groups side by side, CPG lanes each: logarithms of the row products, UPDATE_MAX_LKs over the
-            // visited subsets (mcall.c:582-585, 600-698; the first maximum in visiting order wins), one log-sum-exp for lk_sum ----
-            __syncthreads();
-            const int g0 = g - g % GB, gl = tid / CPG, c = tid % CPG;
-            const bool live = g0 + gl <= g;
-            const int ns = live ? s_nsub[gl] : 0;
-            const double LN2 = 0.693147180559945309417232121458;
-            double lg = 0.0, dip = 0.0;
-            if (live && c <= ns) lg = log(s_red2[gl * CPG + c]) + (double)s_rede2[gl * CPG + c] * LN2;
-            if (HAP && live) dip = log(s_dipm[gl]) + (double)s_dipe[gl] * LN2;
-            const double rsum = __shfl(lg, gl * CPG + ns);               // the row of the normalisation sums
-            const int set = live ? s_set[gl] : 0;
-            const double theta = P.theta;
-            double lk_tot = -HUGE_VAL, lk_add = -HUGE_VAL, v = 0.0;
-            int als = 0;
-            if (live && c < ns) {
-                const uint32_t sid = s_sid[gl * CPG + c];
-                const int ia = (int)(sid & 0xff), ib = (int)((sid >> 8) & 0xff), ic = (int)((sid >> 16) & 0xff);
-                // divide out the product of the normalisation sums of the samples that contributed to this row
-                v = lg - ((HAP && ib != 0xff) ? dip : rsum);
-                als = 1 << ia;
-                if (ia != 0) v += theta;
-                if (ib != 0xff) { als |= 1 << ib; if (ib != 0) v += theta; }
-                if (ic != 0xff) { als |= 1 << ic; if (ic != 0) v += theta; }
-                if ((set >> c) & 1) { lk_tot = v; if (als != 1) lk_add = v; }
-            }
-            const double refc = __shfl(v, gl * CPG);                     // subset 0 is the REF-only one
-            double m = lk_tot; int mi = c;
-            double ma = lk_add;
-            for (int o = CPG >> 1; o > 0; o >>= 1) {
-                const double om = __shfl_xor(m, o); const int oi = __shfl_xor(mi, o);
-                if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-                const double oa = __shfl_xor(ma, o);
-                ma = oa > ma ? oa : ma;
-            }
-            int max_als_b = __shfl(als, gl * CPG + mi);
-            if (m == -HUGE_VAL) max_als_b = 0;
-            double e = lk_add != -HUGE_VAL ? exp(lk_add - ma) : 0.0;
-            for (int o = CPG >> 1; o > 0; o >>= 1) e += __shfl_xor(e, o);
-            const double lk_sum_b = ma != -HUGE_VAL ? ma + log(e) : -HUGE_VAL;
-            if (live && c == 0) {
-                s_rmax[gl] = m; s_rsum[gl] = lk_sum_b; s_rref[gl] = refc; s_rals[gl] = max_als_b;
-                s_rqual[gl] = m != -HUGE_VAL ? -4.343 * (refc - lse2(lk_sum_b, refc)) : 0.0;
-            }
-            __syncthreads();
-            if (tid == 0) {                                              // in group order, as the reference walks them (mcall.c:1546-1560)
-                for (int b = 0; b <= g - g0; ++b) {
-                    const int max_als2 = s_rals[b];
-                    int n = 0;
-                    for (int i = 0; i < nals; i++) if (max_als2 & 1 << i) n++;
-                    sh.als_new |= max_als2;
-                    if (s_rmax[b] != -HUGE_VAL && sh.max_qual < s_rqual[b]) { sh.max_qual = s_rqual[b]; sh.lk_sum = s_rsum[b]; sh.ref_lk = s_rref[b]; }
-                    grp_als_tab[(g0 + b) * 2] = max_als2;
-                    grp_als_tab[(g0 + b) * 2 + 1] = n;
+            const Subset &u = sub[t];
+            double val;
+            const double paa = s_pdg[u.iaa * WGS + tid];
+            if (u.ib < 0) val = paa;                                   // single allele: no ploidy term (mcall.c:607-611)
+            else {
+                const double pbb = s_pdg[u.ibb * WGS + tid];
+                if (u.ic < 0) {
+                    if (ploidy == 2) val = u.fa2 * paa + u.fb2 * pbb + u.fab * s_pdg[u.iab * WGS + tid];
+                    else if (ploidy == 1) val = u.fa * paa + u.fb * pbb;
+                    else val = 0;
+                } else {
+                    const double pcc = s_pdg[u.icc * WGS + tid];
+                    if (ploidy == 2)
+                        val = u.fa2 * paa + u.fb2 * pbb + u.fc2 * pcc + u.fab * s_pdg[u.iab * WGS + tid]
+                            + u.fac * s_pdg[u.iac * WGS + tid] + u.fbc * s_pdg[u.ibc * WGS + tid];
+                    else if (ploidy == 1) val = u.fa * paa + u.fb * pbb + u.fc * pcc;
+                    else val = 0;
                 }
             }
-            continue;
-        }
-        if (tid == 0) sh.redset = setbits;
-        __syncthreads();
-        // UPDATE_MAX_LKs over the visited subsets (mcall.c:582-585, 600-698), lane t = subset t: the first maximum in
-        // visiting order wins, and lk_sum (which only feeds QUAL) is one log-sum-exp instead of a chain of pairwise ones
-        int max_als = 0;
-        double ref_lk, max_lk, lk_sum;
-        {
-            const int set = sh.redset;
-            const double theta = P.theta;
-            double lk_tot = -HUGE_VAL, lk_add = -HUGE_VAL;
-            int als = 0;
-            if (tid < nsub) {
-                const Subset &u = sh.sub[tid];
-                double v = sh.red[tid];
-                // divide out the product of the normalisation sums of the samples that contributed to this row
-                if (FAST) v -= (HAP && u.ib >= 0) ? sh.red_dip : sh.red[nsub];
-                als = 1 << u.ia;
-                if (u.ib < 0) { if (u.ia != 0) v += theta; }
-                else {
-                    als |= 1 << u.ib;
-                    if (u.ia != 0) v += theta;
-                    if (u.ib != 0) v += theta;
-                    if (u.ic >= 0) { als |= 1 << u.ic; if (u.ic != 0) v += theta; }
-                }
-                if (tid == 0) sh.ref_cur = v;               // subset 0 is the REF-only one
-                if ((set >> tid) & 1) { lk_tot = v; if (als != 1) lk_add = v; }
+            if (val != 0.0) {
+                // (val split before it is multiplied in: a subnormal factor would lose bits or round the product to 0)
+                const double m = s_man[t * WGS + tid] * frexp_mant(val);
+                s_man[t * WGS + tid] = frexp_mant(m);
+                s_exp[t * WGS + tid] += frexp_exp(val) + frexp_exp(m);
+                setbits |= 1 << t;
             }
-            double m = lk_tot; int mi = tid;
-            double ma = lk_add;
-            #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double om = __shfl_xor(m, o); const int oi = __shfl_xor(mi, o);
-                if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-                const double oa = __shfl_xor(ma, o);
-                ma = oa > ma ? oa : ma;
-            }
-            max_lk = m;
-            max_als = __shfl(als, mi);
-            if (m == -HUGE_VAL) max_als = 0;
-            double e = lk_add != -HUGE_VAL ? exp(lk_add - ma) : 0.0;
-            e = wsum(e);
-            lk_sum = ma != -HUGE_VAL ? ma + log(e) : -HUGE_VAL;
-            __syncthreads();
-            ref_lk = sh.ref_cur;
-        }
-        if (tid == 0) {
-            int n = 0;
-            for (int i = 0; i < nals; i++) if (max_als & 1 << i) n++;
-            sh.als_new |= max_als;
-            if (max_lk != -HUGE_VAL) {
-                const double qual = -4.343 * (ref_lk - lse2(lk_sum, ref_lk));
-                if (sh.max_qual < qual) { sh.max_qual = qual; sh.lk_sum = lk_sum; sh.ref_lk = ref_lk; }
-            }
-            grp_als_tab[g * 2] = max_als;
-            grp_als_tab[g * 2 + 1] = n;
         }
     }
-    __syncthreads();
+    for (int t = 0; t < nsub; ++t) {
+        // wave product of the mantissas (renormalised at every step) and sum of the exponents
+        double m = s_man[t * WGS + tid]; int e = s_exp[t * WGS + tid];
+        #pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double mm = m * __shfl_xor(m, o);
+            e += __shfl_xor(e, o) + frexp_exp(mm);
+            m = frexp_mant(mm);
+        }
+        if (tid == 0) red[t] = log_of_product(m, e);
+    }
+    return setbits;
+}
 
-    // ---- allele trimming, output set-up (mcall.c:1563-1577) ----
-    if (tid == 0) {
-        if (!(sh.als_new & 1)) sh.als_new |= 1;
-        sh.is_variant = sh.als_new == 1 ? 0 : 1;
-        if ((P.call_flag & BCFGPU_CALL_VARONLY) && !sh.is_variant) sh.early = 1;
-        int nn = 0;
-        for (int i = 0; i < nals; i++) {
-            if (i > 0 && i == unseen) continue;
-            if (P.call_flag & BCFGPU_CALL_KEEPALT) sh.als_new |= 1 << i;
-            if (sh.als_new & (1 << i)) nn++;
-        }
-        sh.nals_new = nn;
-        int nout = 0;
-        for (int i = 0; i < nals; i++) sh.als_map[i] = (sh.als_new & (1 << i)) ? nout++ : -1;
-        int k = 0, l = 0;
-        for (int i = 0; i < nals; i++)
-            for (int j = 0; j <= i; j++) {
-                if ((sh.als_new & (1 << i)) && (sh.als_new & (1 << j))) sh.pl_map[k++] = l;
-                l++;
-            }
+// ---- the best subset of a group: UPDATE_MAX_LKs over the visited subsets (mcall.c:582-585, 600-698) ----
+// a subset's allele set, and its log-likelihood with theta added for every ALT allele
+template <int ABSENT>
+__device__ __forceinline__ double subset_prior(double v, const int ia, const int ib, const int ic, const double theta, int &als)
+{
+    als = 1 << ia;
+    if (ia != 0) v += theta;
+    if (ib != ABSENT) { als |= 1 << ib; if (ib != 0) v += theta; }
+    if (ic != ABSENT) { als |= 1 << ic; if (ic != 0) v += theta; }
+    return v;
+}
+// The core, a lane per subset: the group's subsets sit in the `width` lanes (a power of two) from lane `base` on, this lane
+// being the c-th; v / als as subset_prior() left them, `visited`: a sample entered the subset's row.  The first maximum in
+// visiting order wins, and lk_sum (which only feeds QUAL) is one log-sum-exp over the subsets with an ALT allele instead of a
+// chain of pairwise ones.
+__device__ __forceinline__ void update_max_lks(const int width, const int base, const int c, const bool visited, const double v, const int als,
+                                               double &max_lk, int &max_als, double &lk_sum)
+{
+    double lk_tot = -HUGE_VAL, lk_add = -HUGE_VAL;
+    if (visited) { lk_tot = v; if (als != 1) lk_add = v; }
+    double m = lk_tot; int mi = c;
+    double ma = lk_add;
+    for (int o = width >> 1; o > 0; o >>= 1) {
+        const double om = __shfl_xor(m, o); const int oi = __shfl_xor(mi, o);
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+        const double oa = __shfl_xor(ma, o);
+        ma = oa > ma ? oa : ma;
+    }
+    max_lk = m;
+    max_als = __shfl(als, base + mi);
+    if (m == -HUGE_VAL) max_als = 0;
+    double e = lk_add != -HUGE_VAL ? exp(lk_add - ma) : 0.0;
+    for (int o = width >> 1; o > 0; o >>= 1) e += __shfl_xor(e, o);
+    lk_sum = ma != -HUGE_VAL ? ma + log(e) : -HUGE_VAL;
+}
+__device__ __forceinline__ double group_qual(const double max_lk, const double lk_sum, const double ref_lk)
+{
+    return max_lk != -HUGE_VAL ? -4.343 * (ref_lk - lse2(lk_sum, ref_lk)) : 0.0;
+}
+// a group's result folded into the site's, by one lane, in group order as the reference walks them (mcall.c:1546-1560)
+template <int N>
+__device__ __forceinline__ void fold_group(CallShared<N> &sh, const Site &st, const int g, const int max_als, const double max_lk, const double qual,
+                                           const double lk_sum, const double ref_lk)
+{
+    int n = 0;
+    for (int i = 0; i < st.nals; i++) if (max_als & 1 << i) n++;
+    sh.als_new |= max_als;
+    if (max_lk != -HUGE_VAL && sh.max_qual < qual) { sh.max_qual = qual; sh.lk_sum = lk_sum; sh.ref_lk = ref_lk; }
+    st.grp_als[g * 2] = max_als;
+    st.grp_als[g * 2 + 1] = n;
+}
+// one group, lane t = subset t
+template <bool FAST, bool HAP, int N>
+__device__ __forceinline__ void best_subset(const McallParams &P, const Site &st, const int tid, const int g, const int nsub, const int setbits, CallShared<N> &sh)
+{
+    if (tid == 0) sh.redset = setbits;
+    __syncthreads();
+    const int set = sh.redset;
+    double v = 0.0;
+    int als = 0;
+    bool visited = false;
+    if (tid < nsub) {
+        const Subset &u = sh.sub[tid];
+        v = sh.red[tid];
+        // divide out the product of the normalisation sums of the samples that contributed to this row
+        if (FAST) v -= (HAP && u.ib >= 0) ? sh.red_dip : sh.red[nsub];
+        v = subset_prior<-1>(v, u.ia, u.ib, u.ic, P.theta, als);
+        if (tid == 0) sh.ref_cur = v;               // subset 0 is the REF-only one
+        visited = (set >> tid) & 1;
+    }
+    double max_lk, lk_sum;
+    int max_als;
+    update_max_lks(WGS, 0, tid, visited, v, als, max_lk, max_als, lk_sum);
+    __syncthreads();
+    const double ref_lk = sh.ref_cur;
+    if (tid == 0) fold_group(sh, st, g, max_als, max_lk, group_qual(max_lk, lk_sum, ref_lk), lk_sum, ref_lk);
+}
+// Group g's scan is noted; when g is the last of its batch, the batch's groups are finished together, side by side, CPG lanes
+// each: logarithms of the row products, then as above
+template <bool HAP, int N>
+__device__ __forceinline__ void best_subsets_batch(const McallParams &P, const Site &st, const int tid, const int g, const int setbits, const int CPG,
+                                                   const int GB, const BatchLds &bl, CallShared<N> &sh)
+{
+    if (tid == 0) bl.set[g % GB] = setbits;
+    if (g % GB != GB - 1 && g != st.ngrp - 1) return;             // the batch goes on
+    __syncthreads();
+    const int g0 = g - g % GB, gl = tid / CPG, c = tid % CPG;
+    const bool live = g0 + gl <= g;
+    const int ns = live ? bl.nsub[gl] : 0;
+    double lg = 0.0, dip = 0.0;
+    if (live && c <= ns) lg = log_of_product(bl.red[gl * CPG + c], bl.rede[gl * CPG + c]);
+    if (HAP && live) dip = log_of_product(bl.dipm[gl], bl.dipe[gl]);
+    const double rsum = __shfl(lg, gl * CPG + ns);               // the row of the normalisation sums
+    const int set = live ? bl.set[gl] : 0;
+    double v = 0.0;
+    int als = 0;
+    bool visited = false;
+    if (live && c < ns) {
+        const uint32_t sid = bl.sid[gl * CPG + c];
+        const int ia = (int)(sid & 0xff), ib = (int)((sid >> 8) & 0xff), ic = (int)((sid >> 16) & 0xff);
+        // divide out the product of the normalisation sums of the samples that contributed to this row
+        v = lg - ((HAP && ib != 0xff) ? dip : rsum);
+        v = subset_prior<0xff>(v, ia, ib, ic, P.theta, als);
+        visited = (set >> c) & 1;
+    }
+    const double refc = __shfl(v, gl * CPG);                     // subset 0 is the REF-only one
+    double m, lk_sum_b;
+    int max_als_b;
+    update_max_lks(CPG, gl * CPG, c, visited, v, als, m, max_als_b, lk_sum_b);
+    if (live && c == 0) {
+        bl.rmax[gl] = m; bl.rsum[gl] = lk_sum_b; bl.rref[gl] = refc; bl.rals[gl] = max_als_b;
+        bl.rqual[gl] = group_qual(m, lk_sum_b, refc);
     }
     __syncthreads();
-    if (sh.early) {
-        if (tid == 0) write_skipped(cs, 0);
-        return;
+    if (tid == 0)
+        for (int b = 0; b <= g - g0; ++b) fold_group(sh, st, g0 + b, bl.rals[b], bl.rmax[b], bl.rqual[b], bl.rsum[b], bl.rref[b]);
+}
+
+// ---- allele trimming, output set-up (mcall.c:1563-1577; init_allele_trimming_maps :547-570), by one lane ----
+template <int N>
+__device__ __forceinline__ void trim_alleles(const McallParams &P, const Site &st, CallShared<N> &sh)
+{
+    const int nals = st.nals;
+    if (!(sh.als_new & 1)) sh.als_new |= 1;
+    sh.is_variant = sh.als_new == 1 ? 0 : 1;
+    if ((P.call_flag & BCFGPU_CALL_VARONLY) && !sh.is_variant) sh.early = 1;
+    int nn = 0;
+    for (int i = 0; i < nals; i++) {
+        if (i > 0 && i == st.unseen) continue;
+        if (P.call_flag & BCFGPU_CALL_KEEPALT) sh.als_new |= 1 << i;
+        if (sh.als_new & (1 << i)) nn++;
     }
-    const int als_new = sh.als_new, nals_new = sh.nals_new, is_variant = sh.is_variant;
+    sh.nals_new = nn;
+    int nout = 0;
+    for (int i = 0; i < nals; i++) sh.als_map[i] = (sh.als_new & (1 << i)) ? nout++ : -1;
+    int k = 0, l = 0;
+    for (int i = 0; i < nals; i++)
+        for (int j = 0; j <= i; j++) {
+            if ((sh.als_new & (1 << i)) && (sh.als_new & (1 << j))) sh.pl_map[k++] = l;
+            l++;
+        }
+}
+
+// ---- genotypes (mcall_set_ref_genotypes / mcall_call_genotypes) + PL trimming ----
+// A site that stays REF-only (most of them) needs of its samples only "any data at all?" (mcall_set_ref_genotypes,
+// mcall.c:529-541): four samples a lane and a 4-byte store per GT plane, from the subset scan's notes or (sample groups)
+// from a 4-byte load per PL plane -- four trips to memory for 1000 samples where the general loop below makes sixteen.
+// FAST only; false: the planes do not allow it, nothing was written.
+template <int NG, bool HAP>
+__device__ __forceinline__ bool ref_only_genotypes(const McallParams &P, const Site &st, const int tid, const uint8_t *plb2, const uint8_t *s_nz, int (&ac_loc)[5])
+{
+    const int S = st.S;
+    const size_t Ss = (size_t)S;
+    int8_t *gt0 = P.out.gt + (size_t)st.is * 2 * Ss;
+    const bool ok = !(S & 3) && !(((uintptr_t)plb2 | (uintptr_t)gt0) & 3);
+    if (ok) {
+        for (int s4 = tid * 4; s4 < S; s4 += WGS * 4) {
+            uint32_t any = 0;
+            const uint32_t nib = S <= NZ_MAX_S ? s_nz[s4 >> 2] : 0x80u;
+            if (!(nib & 0x80u)) {                            // the scan's note: no PL is read again
+                any = (nib & 1u) | (nib & 2u) << 7 | (nib & 4u) << 14 | (nib & 8u) << 21;
+            } else {
+                #pragma unroll
+                for (int k = 0; k < NG; ++k)
+                    if (k < st.ngts) any |= *reinterpret_cast<const uint32_t*>(plb2 + (size_t)k * Ss + s4);
+            }
+            uint32_t w = 0, w1 = 0, pw = 0x02020202u;
+            if (HAP && P.ploidy) __builtin_memcpy(&pw, P.ploidy + s4, 4);
+            #pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t pd = (pw >> (8 * b)) & 0xFFu;
+                const bool called = ((any >> (8 * b)) & 0xFFu) && pd;
+                if (called) ac_loc[0] += (int)pd;
+                const uint32_t g0 = called ? 0u : (uint32_t)(uint8_t)BCFGPU_GT_MISSING;
+                w |= g0 << (8 * b);
+                w1 |= (pd == 2 ? g0 : (uint32_t)(uint8_t)BCFGPU_GT_VECTOR_END) << (8 * b);
+            }
+            *reinterpret_cast<uint32_t*>(gt0 + s4) = w;
+            *reinterpret_cast<uint32_t*>(gt0 + Ss + s4) = w1;
+        }
+    }
+    return ok;
+}
+// GQ and GP of the lane's sample from its genotype likelihoods gps[k * WGS] (mcall.c:842-885); returns GQ
+__device__ __forceinline__ int sample_gq_gp(const McallParams &P, float *gps, const int ploidy, const int gnals, const int ngts_new)
+{
+    int nmax;
+    if (P.ploidy) nmax = ploidy == 2 ? ngts_new : (ploidy == 1 ? gnals : 0);
+    else nmax = ngts_new;
+    double mx = gps[0];
+    if (mx < 0 || nmax == 0) {
+        if (P.output_tags & BCFGPU_CALL_FMT_GP) {
+            for (int k = 0; k < nmax; ++k) gps[k * WGS] = 0;
+            if (nmax == 0) { gps[0] = __uint_as_float(0x7F800001u); nmax = 1; }
+            if (nmax < ngts_new) gps[nmax * WGS] = __uint_as_float(0x7F800002u);
+        }
+        return 0;
+    }
+    double sum = mx;
+    for (int k = 1; k < nmax; ++k) { const double v = gps[k * WGS]; if (mx < v) mx = v; sum += v; }
+    mx = -4.34294 * log(1 - mx / sum);
+    if (P.output_tags & BCFGPU_CALL_FMT_GP) {
+        for (int k = 0; k < nmax; ++k) gps[k * WGS] = (float)(gps[k * WGS] / sum);
+        for (int k = nmax; k < ngts_new; ++k) gps[k * WGS] = __uint_as_float(0x7F800002u);
+    }
+    return mx <= 127 ? (int)mx : 127;
+}
+// the sample's PLs of the alleles that stay (mcall.c:1158-1194); plc_at(i): its PL of genotype i
+template <typename F>
+__device__ __forceinline__ void store_trimmed_pls(int32_t *dst, const size_t Ss, const int ploidy, const int nals_new, const int ngts_new, const int *pl_map, F plc_at)
+{
+    if (ploidy == 2) {
+        for (int k = 0; k < ngts_new; ++k) dst[(size_t)k * Ss] = plc_at(pl_map[k]);
+    } else if (ploidy == 1) {
+        int k;
+        for (k = 0; k < nals_new; ++k) dst[(size_t)k * Ss] = plc_at(pl_map[(k + 1) * (k + 2) / 2 - 1]);
+        if (k < ngts_new) dst[(size_t)k * Ss] = VEND;
+    } else {
+        dst[0] = MISSING;
+        dst[Ss] = VEND;
+    }
+}
+// the general loop, a lane per sample: GT, and at a variant site GQ / GP and the trimmed PLs
+template <int NG, bool FAST, bool HAP, int N>
+__device__ __forceinline__ void call_genotypes(const McallParams &P, const Site &st, const int tid, CallShared<N> &sh, const GtLds &L, const uint8_t *plb2,
+                                               const int is_variant, const int nals_new, const bool ref_only, int (&ac_loc)[5])
+{
+    const int is = st.is, S = st.S, nals = st.nals, ngts = st.ngts, ngrp = st.ngrp;
+    const size_t Ss = (size_t)S;
     const int ngts_new = nals_new * (nals_new + 1) / 2;
-    const bool ref_only = (als_new == 1);
     const bool want_gqgp = (P.output_tags & (BCFGPU_CALL_FMT_GQ | BCFGPU_CALL_FMT_GP)) != 0;
-
-    // ---- genotypes (mcall_set_ref_genotypes / mcall_call_genotypes) + PL trimming ----
-    int ac_loc[5] = {0, 0, 0, 0, 0};
     const int ogt = P.out_n_gt_max;
-    {
-    const uint8_t *plb2 = reinterpret_cast<const uint8_t*>(P.pl) + (size_t)is * BCFGPU_MAX_PL * Ss;
+    float *s_gps = L.gps;
     // FAST: the PL bytes of the lane's next sample are requested before the current one is worked on (the loop is a
     // chain of memory round trips otherwise: 16 of them for 1000 samples)
     uint32_t pl_nx[FAST ? NG : 1];
@@ -1153,42 +1232,8 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
             for (int k = 0; k < NG; ++k) pl_nx[k] = (k < ngts && s < S) ? (uint32_t)plb2[(size_t)k * Ss + s] : 0u;
         }
     };
-    // A site that stays REF-only (most of them) needs of its samples only "any data at all?" (mcall_set_ref_genotypes,
-    // mcall.c:529-541): four samples a lane and a 4-byte store per GT plane, from the subset scan's notes or (sample groups)
-    // from a 4-byte load per PL plane -- four trips to memory for 1000 samples where the general loop below makes sixteen
-    bool gt_done = false;
-    if constexpr (FAST) {
-        int8_t *gt0 = P.out.gt + (size_t)is * 2 * Ss;
-        if (!gt_done && !is_variant && ref_only && !(S & 3) && !(((uintptr_t)plb2 | (uintptr_t)gt0) & 3)) {
-            for (int s4 = tid * 4; s4 < S; s4 += WGS * 4) {
-                uint32_t any = 0;
-                const uint32_t nib = S <= NZ_MAX_S ? s_nz[s4 >> 2] : 0x80u;
-                if (!(nib & 0x80u)) {                            // the scan's note: no PL is read again
-                    any = (nib & 1u) | (nib & 2u) << 7 | (nib & 4u) << 14 | (nib & 8u) << 21;
-                } else {
-                    #pragma unroll
-                    for (int k = 0; k < NG; ++k)
-                        if (k < ngts) any |= *reinterpret_cast<const uint32_t*>(plb2 + (size_t)k * Ss + s4);
-                }
-                uint32_t w = 0, w1 = 0, pw = 0x02020202u;
-                if (HAP && P.ploidy) __builtin_memcpy(&pw, P.ploidy + s4, 4);
-                #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const uint32_t pd = (pw >> (8 * b)) & 0xFFu;
-                    const bool called = ((any >> (8 * b)) & 0xFFu) && pd;
-                    if (called) ac_loc[0] += (int)pd;
-                    const uint32_t g0 = called ? 0u : (uint32_t)(uint8_t)BCFGPU_GT_MISSING;
-                    w |= g0 << (8 * b);
-                    w1 |= (pd == 2 ? g0 : (uint32_t)(uint8_t)BCFGPU_GT_VECTOR_END) << (8 * b);
-                }
-                *reinterpret_cast<uint32_t*>(gt0 + s4) = w;
-                *reinterpret_cast<uint32_t*>(gt0 + Ss + s4) = w1;
-            }
-            gt_done = true;
-        }
-    }
-    if (!gt_done) fetch_pl(tid);
-    for (int s = tid; s < (gt_done ? 0 : S); s += WGS) {
+    fetch_pl(tid);
+    for (int s = tid; s < S; s += WGS) {
         const int ploidy = (FAST && !HAP) ? 2 : (P.ploidy ? P.ploidy[s] : 2);    // FAST without HAP is launched only without a ploidy array
         // P(D|G) = raw/psum is formed lazily below, with the same division the reference performs (bit-exact genotypes)
         double psum = 0;
@@ -1201,8 +1246,8 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
             for (int k = 0; k < NG; ++k) {
                 if (k < ngts) {
                     const uint32_t v = pl_nx[k];
-                    s_plb[k * WGS + tid] = (uint8_t)v;
-                    psum += s_p2[v];
+                    L.plb[k * WGS + tid] = (uint8_t)v;
+                    psum += L.p2[v];
                     anynz |= v;
                 }
                 if (want_gqgp) s_gps[k * WGS + tid] = 0.f;
@@ -1212,26 +1257,26 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
         } else {
             int pl[NG]; double pdg[NG];
             load_pl<NG>(P, is, s, ngts, pl);
-            psum = set_pdg_one<NG>(s_pl2p, pl, pdg, ngts, nals, unseen, s_fill + tid);
+            psum = set_pdg_one<NG>(P.pl2p, pl, pdg, ngts, nals, st.unseen, L.fill + tid);
             #pragma unroll
             for (int k = 0; k < NG; ++k) {
                 if (k < ngts && pdg[k] != 0.0) allzero = false;
-                s_pdg[k * WGS + tid] = pdg[k]; s_plc[k * WGS + tid] = pl[k];
+                L.pdg[k * WGS + tid] = pdg[k]; L.plc[k * WGS + tid] = pl[k];
                 if (want_gqgp) s_gps[k * WGS + tid] = 0.f;
             }
             if (psum == 0.0) allzero = true;
         }
-        auto pdg_at = [&](int i) -> double { if constexpr (FAST) return s_p2[s_plb[i * WGS + tid]]; else return s_pdg[i * WGS + tid]; };
-        auto plc_at = [&](int i) -> int { if constexpr (FAST) return (int)s_plb[i * WGS + tid]; else return s_plc[i * WGS + tid]; };
+        auto pdg_at = [&](int i) -> double { if constexpr (FAST) return L.p2[L.plb[i * WGS + tid]]; else return L.pdg[i * WGS + tid]; };
+        auto plc_at = [&](int i) -> int { if constexpr (FAST) return (int)L.plb[i * WGS + tid]; else return L.plc[i * WGS + tid]; };
         int g0, g1, gq = 0, gnals = 0;
         if (!is_variant) {
             if (allzero || !ploidy) { g0 = BCFGPU_GT_MISSING; g1 = ploidy == 2 ? BCFGPU_GT_MISSING : BCFGPU_GT_VECTOR_END; }
             else { g0 = 0; g1 = ploidy == 2 ? 0 : BCFGPU_GT_VECTOR_END; ac_loc[0] += ploidy; }
         } else {
-            const int g = ngrp > 1 ? GRP_OF(s) : 0;
-            const int gals = grp_als_tab[g * 2];
-            gnals = grp_als_tab[g * 2 + 1];
-            const float *gq5 = s_gq + g * 5;
+            const int g = ngrp > 1 ? grp_of(P, s, ngrp) : 0;
+            const int gals = st.grp_als[g * 2];
+            gnals = st.grp_als[g * 2 + 1];
+            const float *gq5 = st.gq + g * 5;
             if (!ploidy) { g0 = BCFGPU_GT_MISSING; g1 = BCFGPU_GT_VECTOR_END; s_gps[tid] = -1; }
             else if (allzero) { g0 = BCFGPU_GT_MISSING; g1 = ploidy == 2 ? BCFGPU_GT_MISSING : BCFGPU_GT_VECTOR_END; s_gps[tid] = -1; }
             else {
@@ -1265,30 +1310,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
                 #pragma unroll
                 for (int k = 0; k < 5; ++k) { if (g0 == k) ac_loc[k]++; if (g1 == k) ac_loc[k]++; }
             }
-            if (want_gqgp) {
-                // mcall.c:842-885
-                int nmax;
-                if (P.ploidy) nmax = ploidy == 2 ? ngts_new : (ploidy == 1 ? gnals : 0);
-                else nmax = ngts_new;
-                double mx = s_gps[tid];
-                if (mx < 0 || nmax == 0) {
-                    if (P.output_tags & BCFGPU_CALL_FMT_GP) {
-                        for (int k = 0; k < nmax; ++k) s_gps[k * WGS + tid] = 0;
-                        if (nmax == 0) { s_gps[tid] = __uint_as_float(0x7F800001u); nmax = 1; }
-                        if (nmax < ngts_new) s_gps[nmax * WGS + tid] = __uint_as_float(0x7F800002u);
-                    }
-                    gq = 0;
-                } else {
-                    double sum = mx;
-                    for (int k = 1; k < nmax; ++k) { const double v = s_gps[k * WGS + tid]; if (mx < v) mx = v; sum += v; }
-                    mx = -4.34294 * log(1 - mx / sum);
-                    gq = mx <= 127 ? (int)mx : 127;
-                    if (P.output_tags & BCFGPU_CALL_FMT_GP) {
-                        for (int k = 0; k < nmax; ++k) s_gps[k * WGS + tid] = (float)(s_gps[k * WGS + tid] / sum);
-                        for (int k = nmax; k < ngts_new; ++k) s_gps[k * WGS + tid] = __uint_as_float(0x7F800002u);
-                    }
-                }
-            }
+            if (want_gqgp) gq = sample_gq_gp(P, s_gps + tid, ploidy, gnals, ngts_new);
         }
         P.out.gt[((size_t)is * 2 + 0) * Ss + s] = (int8_t)g0;
         P.out.gt[((size_t)is * 2 + 1) * Ss + s] = (int8_t)g1;
@@ -1297,48 +1319,124 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(!FAST ? 1 :
             if ((P.output_tags & BCFGPU_CALL_FMT_GP) && P.out.gp)
                 for (int k = 0; k < ngts_new; ++k) P.out.gp[((size_t)is * ogt + k) * Ss + s] = s_gps[k * WGS + tid];
         }
-        // trimmed PLs (mcall.c:1158-1194)
-        if (!ref_only && P.out.pl) {
-            int32_t *dst = P.out.pl + (size_t)is * ogt * Ss + s;
-            if (ploidy == 2) {
-                for (int k = 0; k < ngts_new; ++k) dst[(size_t)k * Ss] = plc_at(sh.pl_map[k]);
-            } else if (ploidy == 1) {
-                int k;
-                for (k = 0; k < nals_new; ++k) dst[(size_t)k * Ss] = plc_at(sh.pl_map[(k + 1) * (k + 2) / 2 - 1]);
-                if (k < ngts_new) dst[(size_t)k * Ss] = VEND;
-            } else {
-                dst[0] = MISSING;
-                dst[Ss] = VEND;
-            }
-        }
+        if (!ref_only && P.out.pl) store_trimmed_pls(P.out.pl + (size_t)is * ogt * Ss + s, Ss, ploidy, nals_new, ngts_new, sh.pl_map, plc_at);
     }
+}
+
+// ---- the site record (mcall.c:1617-1618, 1631-1650: QUAL, AC / AN), by one lane ----
+template <int N>
+__device__ __forceinline__ void write_site_record(const McallParams &P, const Site &st, const CallShared<N> &sh, bcfgpu_call_site *cs,
+                                                  const int is_variant, const int nals_new, const int als_new, const bool ref_only)
+{
+    int nAC = 0;
+    if (is_variant) for (int i = 1; i < nals_new; i++) nAC += sh.ac[i];
+    if (is_variant && !nAC && (P.call_flag & BCFGPU_CALL_VARONLY)) { write_skipped(cs, 0); return; }
+    float qual = 0; int qmiss = 0;
+    if (nAC) qual = (float)sh.max_qual;
+    else {
+        if (sh.lk_sum != -HUGE_VAL) qual = (float)(-4.343 * (sh.lk_sum - lse2(sh.lk_sum, sh.ref_lk)));
+        else if (sh.ac[0]) qual = P.theta != 0 ? (float)(-4.343 * P.theta) : 0.f;
+        else qmiss = 1;
     }
+    cs->qual = qual; cs->qual_missing = qmiss;
+    for (int i = 0; i < 5; ++i) cs->ac[i] = i < nals_new ? sh.ac[i] : 0;
+    cs->an = nAC + sh.ac[0];
+    cs->nals_new = nals_new; cs->als_new = als_new;
+    for (int i = 0; i < 5; ++i) cs->als_map[i] = i < st.nals ? sh.als_map[i] : -1;
+    cs->ret = nals_new;
+    cs->pl_dropped = ref_only ? 1 : 0;
+    cs->has_i16 = 0; cs->mq = 0; cs->pv4_tested = 0;
+    for (int i = 0; i < 4; ++i) { cs->dp4[i] = 0; cs->pv4[i] = 0.f; }
+}
+
+// wavefronts per SIMD an instantiation is compiled for; the general ones (`general`: the lower and the upper bound) take what they get
+constexpr int mcall_waves(int nsub, bool fast, bool hap, bool grp, int general)
+{
+    return !fast ? general : (hap || grp) && nsub > 15 ? 3 : hap ? MCALL_WAVES_HAP : grp ? MCALL_WAVES_GRP : MCALL_WAVES;
+}
+
+// One workgroup of one wavefront per site; instantiation (MAXA, NSUB) works on the sites mcall_route.h gives it.  FAST: u8 PLs of
+// the fused pipeline, HAP: with a ploidy array, GRP: with sample groups (GRP = false is launched only for a single group).
+template <int MAXA, int NSUB, bool FAST, bool HAP, bool GRP>
+__global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(mcall_waves(NSUB, FAST, HAP, GRP, 1), mcall_waves(NSUB, FAST, HAP, GRP, 8))))
+void mcall_kernel(const McallParams P)
+{
+    constexpr int NG = MAXA * (MAXA + 1) / 2;
+    constexpr int TILES = NSUB >= 16 ? 2 : 1;     // 16-row tiles of the coefficient matrix (subsets + the sum row)
+    constexpr bool BATCH = FAST && GRP;           // the groups are worked on in batches (enumerate_batch)
+    extern __shared__ __align__(16) unsigned char dsm[];      // [n_grp][5] group qsum, then [n_grp][2] best allele sets
+    __shared__ CallShared<BATCH ? 1 : NSUB> sh;                // (the batched groups keep their subsets in s_sid)
+    __shared__ double s_pdg[FAST ? 1 : NG * WGS];   // the lane's current sample: raw P(D|G) (not yet divided by its sum)
+    // pass 1 (the subset scan): general: per-lane running products, mantissas and exponents; FAST: the coefficient matrix
+    // pass 2 (genotypes): the lane's current sample: general: PLs (i32) and genotype posteriors; FAST: PL bytes (u8) and posteriors (f32)
+    constexpr int U1 = FAST ? TILES * 16 * 16 * 8 * (HAP ? 2 : 1) : NSUB * WGS * 12, U2 = FAST ? NG * WGS * 5 : NG * WGS * 8,
+                  UB = U1 > U2 ? U1 : U2;
+    __shared__ __align__(8) unsigned char s_union[UB];
+    __shared__ double s_p2[FAST ? 264 : 1];
+    __shared__ __align__(4) uint8_t s_nz[FAST ? NZ_MAX_S / 4 : 4];
+    __shared__ uint32_t s_sid[BATCH ? 64 : 1];
+    __shared__ int s_nsub[BATCH ? 4 : 1], s_set[BATCH ? 4 : 1], s_rede2[BATCH ? 64 : 1], s_dipe[BATCH ? 4 : 1], s_rals[BATCH ? 4 : 1];
+    __shared__ double s_red2[BATCH ? 64 : 1], s_dipm[BATCH ? 4 : 1], s_rmax[BATCH ? 4 : 1], s_rsum[BATCH ? 4 : 1], s_rref[BATCH ? 4 : 1], s_rqual[BATCH ? 4 : 1];
+    const BatchLds bl = {s_sid, s_nsub, s_set, s_rede2, s_dipe, s_rals, s_red2, s_dipm, s_rmax, s_rsum, s_rref, s_rqual};
+    const GtLds gl = {s_p2, s_union + NG * WGS * 4, reinterpret_cast<float*>(s_union + (FAST ? 0 : NG * WGS * 4)), s_pdg,
+                      reinterpret_cast<int*>(s_union), reinterpret_cast<int*>(s_pdg)};   // (fill: used before s_pdg is written)
+
+    const int tid = threadIdx.x;
+    Site st;
+    st.is = blockIdx.x; st.S = P.n_smpl;
+    st.ngrp = GRP ? (P.n_grp > 1 ? P.n_grp : 1) : 1;
+    st.gq = reinterpret_cast<float*>(dsm); st.grp_als = reinterpret_cast<int*>(st.gq + st.ngrp * 5);
+    bcfgpu_call_site *cs = &P.out.site[st.is];
+    const int ngrp = st.ngrp;
+
+    if (!site_header<MAXA, NSUB>(P, st.is, tid, ngrp > 1, st.nals, st.unseen)) return;
+    st.ngts = st.nals * (st.nals + 1) / 2;
+    if constexpr (FAST) stage_pl_table(P, tid, st.S, s_p2, s_nz);
+    if (freq_setup<GRP>(P, st, tid, sh)) {
+        if (tid == 0) write_skipped(cs, -1);
+        return;
+    }
+    // (decided once per site, before the groups are walked, so that exactly one instantiation takes the site)
+    if (!mcall_takes_by_freq(MAXA, NSUB, ngrp > 1, ngrp == 1 && five_frequencies(st))) return;
+
+    // ---- per group: mcall_find_best_alleles ----
+    const int CPG = ngrp == 1 ? 64 : (NSUB > 15 ? 32 : 16), GB = 64 / CPG;
+    for (int g = 0; g < ngrp; ++g) {
+        if constexpr (!BATCH) enumerate_group(st, tid, g, sh);
+        else if (g % GB == 0) enumerate_batch(st, tid, g, CPG, bl);
+        const int nsub = BATCH ? s_nsub[g % GB] : sh.nsub;
+        const int gb = BATCH ? (g % GB) * CPG : 0;
+        const RowDst dst = BATCH ? RowDst{s_red2 + gb, s_rede2 + gb, s_dipm + g % GB, s_dipe + g % GB} : RowDst{sh.red, sh.rede, sh.red + 31, sh.rede + 31};
+        int setbits;
+        if constexpr (FAST && NSUB <= 15) setbits = scan_sparse<HAP>(P, st, tid, g, nsub, s_p2, s_nz, dst);
+        else if constexpr (FAST) setbits = scan_matrix<TILES, HAP, BATCH>(P, st, tid, g, nsub, s_sid + gb, sh.sub, reinterpret_cast<double*>(s_union), s_p2, s_nz, dst);
+        else setbits = scan_general<NG>(P, st, tid, g, nsub, sh.sub, reinterpret_cast<double*>(s_union), reinterpret_cast<int*>(s_union + NSUB * WGS * 8), s_pdg, gl.fill, sh.red);
+        if constexpr (FAST && !BATCH) rows_to_logs<HAP>(sh, nsub, tid);
+        setbits = wor(setbits);
+        if constexpr (!BATCH) best_subset<FAST, HAP>(P, st, tid, g, nsub, setbits, sh);
+        else best_subsets_batch<HAP>(P, st, tid, g, setbits, CPG, GB, bl, sh);
+    }
+    __syncthreads();
+
+    if (tid == 0) trim_alleles(P, st, sh);
+    __syncthreads();
+    if (sh.early) {
+        if (tid == 0) write_skipped(cs, 0);
+        return;
+    }
+    const int als_new = sh.als_new, nals_new = sh.nals_new, is_variant = sh.is_variant;
+    const bool ref_only = (als_new == 1);
+
+    int ac_loc[5] = {0, 0, 0, 0, 0};
+    const uint8_t *plb2 = reinterpret_cast<const uint8_t*>(P.pl) + (size_t)st.is * BCFGPU_MAX_PL * (size_t)st.S;
+    bool gt_done = false;
+    if constexpr (FAST) gt_done = !is_variant && ref_only && ref_only_genotypes<NG, HAP>(P, st, tid, plb2, s_nz, ac_loc);
+    if (!gt_done) call_genotypes<NG, FAST, HAP>(P, st, tid, sh, gl, plb2, is_variant, nals_new, ref_only, ac_loc);
     // AC totals
     #pragma unroll
     for (int k = 0; k < 5; ++k) { const int v = wsumi(ac_loc[k]); if (tid == 0) sh.ac[k] = v; }
     __syncthreads();
-
-    if (tid == 0) {
-        int nAC = 0;
-        if (is_variant) for (int i = 1; i < nals_new; i++) nAC += sh.ac[i];
-        if (is_variant && !nAC && (P.call_flag & BCFGPU_CALL_VARONLY)) { write_skipped(cs, 0); return; }
-        float qual = 0; int qmiss = 0;
-        if (nAC) qual = (float)sh.max_qual;
-        else {
-            if (sh.lk_sum != -HUGE_VAL) qual = (float)(-4.343 * (sh.lk_sum - lse2(sh.lk_sum, sh.ref_lk)));
-            else if (sh.ac[0]) qual = P.theta != 0 ? (float)(-4.343 * P.theta) : 0.f;
-            else qmiss = 1;
-        }
-        cs->qual = qual; cs->qual_missing = qmiss;
-        for (int i = 0; i < 5; ++i) cs->ac[i] = i < nals_new ? sh.ac[i] : 0;
-        cs->an = nAC + sh.ac[0];
-        cs->nals_new = nals_new; cs->als_new = als_new;
-        for (int i = 0; i < 5; ++i) cs->als_map[i] = i < nals ? sh.als_map[i] : -1;
-        cs->ret = nals_new;
-        cs->pl_dropped = ref_only ? 1 : 0;
-        cs->has_i16 = 0; cs->mq = 0; cs->pv4_tested = 0;
-        for (int i = 0; i < 4; ++i) { cs->dp4[i] = 0; cs->pv4[i] = 0.f; }
-    }
+    if (tid == 0) write_site_record(P, st, sh, cs, is_variant, nals_new, als_new, ref_only);
 }
 
 // (A workgroup of four wavefronts per site -- all 256 lanes normalising a round of 1024 samples, the groups dealt to the
@@ -1409,7 +1507,7 @@ __global__ __launch_bounds__(WGS) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                 }
             }
             #pragma unroll
-            for (int j = 0; j < 4; ++j) gnx[j] = j < rem ? GRP_OF(s + j) : 0;
+            for (int j = 0; j < 4; ++j) gnx[j] = j < rem ? grp_of(P, s + j, ngrp) : 0;
         };
         auto fetch_ad = [&](int base) __attribute__((always_inline)) { fetch_at(base + 4 * tid); };
         // Groups that are runs of consecutive samples (the usual -G file): lane (group, allele) keeps its group's running sum and
@@ -1628,12 +1726,18 @@ __global__ void grp_check_kernel(const int32_t *grp, int n_smpl, int n_grp, int 
     } else { atomicMin(&rng[3 * g], s); atomicMax(&rng[3 * g + 1], s + 1); atomicAdd(&rng[3 * g + 2], 1); }
 }
 
+// the three instantiations that share the grid (mcall_route.h), those that the rule launches
+template <bool FAST, bool HAP, bool GRP>
+static void launch_mcall3(const McallParams &p, size_t lds, hipStream_t s)
+{
+    if (mcall_launched(3, p.small_too)) hipLaunchKernelGGL((mcall_kernel<3, 7, FAST, HAP, GRP>), dim3(p.n_sites), dim3(WGS), lds, s, p);
+    if (mcall_launched(5, p.small_too)) hipLaunchKernelGGL((mcall_kernel<5, 15, FAST, HAP, GRP>), dim3(p.n_sites), dim3(WGS), lds, s, p);
+    if (mcall_launched(5, p.small_too)) hipLaunchKernelGGL((mcall_kernel<5, 25, FAST, HAP, GRP>), dim3(p.n_sites), dim3(WGS), lds, s, p);
+}
+
 void launch_mcall(const McallParams &p_in, hipStream_t s)
 {
     if (p_in.n_sites == 0) return;
-    #ifndef MCALL_SMALL_TOO_SAMPLES
-    #define MCALL_SMALL_TOO_SAMPLES 256
-    #endif
     McallParams p = p_in;
     p.small_too = (p.pl_is_u8 && p.n_smpl >= MCALL_SMALL_TOO_SAMPLES) ? 1 : 0;        // (below; the fused pipeline's launches only)
     const int ngrp = p.n_grp > 1 ? p.n_grp : 1;
@@ -1646,20 +1750,15 @@ void launch_mcall(const McallParams &p_in, hipStream_t s)
     // Each instantiation is launched over all sites and a workgroup leaves at once when the site is another's: 25-45 us a launch of
     // 32 768 workgroups.  With many samples nearly every site shows four or five alleles (sequencing errors alone), so the small
     // instantiation is not launched then and the few sites it would take run in the 15-subset one (same arithmetic, longer loops).
-    #define MCALL_LAUNCH3(FAST_, HAP_, GRP_) do { \
-        if (!p.small_too) hipLaunchKernelGGL((mcall_kernel<3, 7, FAST_, HAP_, GRP_>), dim3(p.n_sites), dim3(WGS), lds, s, p); \
-        hipLaunchKernelGGL((mcall_kernel<5, 15, FAST_, HAP_, GRP_>), dim3(p.n_sites), dim3(WGS), lds, s, p); \
-        hipLaunchKernelGGL((mcall_kernel<5, 25, FAST_, HAP_, GRP_>), dim3(p.n_sites), dim3(WGS), lds, s, p); } while (0)
     if (p.pl_is_u8) {
         // u8 PLs (the fused pipeline): the lane-per-sample subset scan (matrix cores for 25 subsets); the haploid forms only with a ploidy
         // array, the group handling only with more than one group
-        if (p.ploidy) MCALL_LAUNCH3(true, true, true);
-        else if (ngrp > 1) MCALL_LAUNCH3(true, false, true);
-        else MCALL_LAUNCH3(true, false, false);
+        if (p.ploidy) launch_mcall3<true, true, true>(p, lds, s);
+        else if (ngrp > 1) launch_mcall3<true, false, true>(p, lds, s);
+        else launch_mcall3<true, false, false>(p, lds, s);
     } else {
-        MCALL_LAUNCH3(false, false, true);
+        launch_mcall3<false, false, true>(p, lds, s);
     }
-    #undef MCALL_LAUNCH3
     if (p.msite || p.i16) hipLaunchKernelGGL(i16_kernel, dim3((p.n_sites + 15) / 16), dim3(64), 0, s, p);
 }
 

@@ -976,7 +976,6 @@ __global__ __launch_bounds__(256) void baq_ref4_kernel(const char *ref, size_t n
 
 using namespace bcfgpu;
 
-#define BQ_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
 
 // the scratch class: BAQ_WIDE_LANES reads a wavefront; the working rows in LDS when two rows of the class's widest band fit (bands
 // to about 200), else every cell through the scratch matrices
@@ -1020,12 +1019,12 @@ static int baq_core(const char *who, bcfgpu_ctx *ctx, hipStream_t stream, const 
     if (!Q.jobs0 || !Q.jobs1 || !Q.jobs2 || !Q.jobs3 || !Q.counts || !d_state || !d_q || !d_tmp) return nomem();
     const int init[8] = {0, 0, 1, 1, INT32_MAX, 0, 0, 0};
     int counts[8];
-    BQ_CHK(hipMemcpyAsync(Q.counts, init, sizeof init, hipMemcpyHostToDevice, stream));
+    BCFGPU_CHK(hipMemcpyAsync(Q.counts, init, sizeof init, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(baq_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, Q);
-    BQ_CHK(hipMemcpyAsync(counts, Q.counts, sizeof counts, hipMemcpyDeviceToHost, stream));
-    BQ_CHK(hipMemcpyAsync(d_qo, D.qual, nbase, hipMemcpyDeviceToDevice, stream));     // reads without a job keep their qualities
-    BQ_CHK(hipMemsetAsync(d_zo, 0, nbase, stream));
-    BQ_CHK(hipStreamSynchronize(stream));
+    BCFGPU_CHK(hipMemcpyAsync(counts, Q.counts, sizeof counts, hipMemcpyDeviceToHost, stream));
+    BCFGPU_CHK(hipMemcpyAsync(d_qo, D.qual, nbase, hipMemcpyDeviceToDevice, stream));     // reads without a job keep their qualities
+    BCFGPU_CHK(hipMemsetAsync(d_zo, 0, nbase, stream));
+    BCFGPU_CHK(hipStreamSynchronize(stream));
     // the reference slice the windows touch, as 0..4 codes
     const int lo = counts[4] == INT32_MAX ? 0 : counts[4], hi = std::max(counts[5], lo);
     char *d_refc = (char*)bcfgpu_internal_ws(ctx, WS_PBAQ_REF, (size_t)(hi - lo) + 64);
@@ -1036,7 +1035,7 @@ static int baq_core(const char *who, bcfgpu_ctx *ctx, hipStream_t stream, const 
         char *h_ref = (char*)bcfgpu_internal_pinned(ctx, PIN_PBAQ_REF, (size_t)(hi - lo));
         if (!h_ref) return bcfgpu_set_error(BCFGPU_E_NOMEM, who, "host staging");
         std::memcpy(h_ref, ref + lo, (size_t)(hi - lo));
-        BQ_CHK(hipMemcpyAsync(d_refc, h_ref, (size_t)(hi - lo), hipMemcpyHostToDevice, stream));
+        BCFGPU_CHK(hipMemcpyAsync(d_refc, h_ref, (size_t)(hi - lo), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(baq_ref4_kernel, dim3((unsigned)(((size_t)(hi - lo) + 255) / 256)), dim3(256), 0, stream, d_refc, (size_t)(hi - lo), d_ref4);
     }
     BaqParams P{};
@@ -1059,7 +1058,7 @@ static int baq_core(const char *who, bcfgpu_ctx *ctx, hipStream_t stream, const 
         if (!jobs2) return nomem();
         hipLaunchKernelGGL(baq_sort_wide_kernel, dim3(1), dim3(1024), 0, stream, Q.jobs2, counts[6], jobs2);
     }
-    BQ_CHK(hipEventRecord(sev[0], stream));
+    BCFGPU_CHK(hipEventRecord(sev[0], stream));
     static const WsSlot slotF[4] = { WS_PBAQ_F0, WS_PBAQ_F1, WS_PBAQ_F2, WS_PBAQ_F3 }, slotS[4] = { WS_PBAQ_S0, WS_PBAQ_S1, WS_PBAQ_S2, WS_PBAQ_S3 },
                         slotW[4] = { WS_PBAQ_W0, WS_PBAQ_W1, WS_PBAQ_W2, WS_PBAQ_W3 };
     bool used_side[4] = { false, false, false, false };
@@ -1069,7 +1068,7 @@ static int baq_core(const char *who, bcfgpu_ctx *ctx, hipStream_t stream, const 
         if (!nj) continue;
         const bool reg = c < 2;
         hipStream_t st = c == 0 ? stream : side[c - 1];
-        if (c) { BQ_CHK(hipStreamWaitEvent(st, sev[0], 0)); used_side[c] = true; }
+        if (c) { BCFGPU_CHK(hipStreamWaitEvent(st, sev[0], 0)); used_side[c] = true; }
         P.ncell = reg ? 2 * (2 * (c ? BAQ_BWM2 : BAQ_BWM) + 3) : 3 * (2 * (c == 3 ? BAQ_BWM3 : counts[2]) + 1) + 6;       // doubles per matrix row
         const size_t per_mat = (size_t)(reg ? BAQ_ROWS_KEPT(P.max_lq) : P.max_lq + 2) * P.ncell * sizeof(double);  // one matrix of one read (register-row classes: the odd rows)
         const size_t per_job = reg ? per_mat : 2 * per_mat;
@@ -1097,10 +1096,10 @@ static int baq_core(const char *who, bcfgpu_ctx *ctx, hipStream_t stream, const 
             else             e = launch_baq_wide<0>(P, st);
             if (e != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, who, "hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize)");
         }
-        BQ_CHK(hipGetLastError());
+        BCFGPU_CHK(hipGetLastError());
     }
     for (int c = 1; c < 4; ++c)
-        if (used_side[c]) { BQ_CHK(hipEventRecord(sev[c], side[c - 1])); BQ_CHK(hipStreamWaitEvent(stream, sev[c], 0)); }
+        if (used_side[c]) { BCFGPU_CHK(hipEventRecord(sev[c], side[c - 1])); BCFGPU_CHK(hipStreamWaitEvent(stream, sev[c], 0)); }
     return BCFGPU_OK;
 }
 
@@ -1152,8 +1151,8 @@ extern "C" int bcfgpu_pool_baq(bcfgpu_ctx *ctx, const char *ref, int32_t ref_len
     if (!d_qo || !d_zo || !d_has_zq || !d_ret) return bcfgpu_set_error(BCFGPU_E_NOMEM, who, "device workspace");
     if (const int rc = baq_core(who, ctx, stream, d_q2p, D, ref, ref_len, flag, d_qo, d_zo, d_has_zq, d_ret)) return rc;
     if (ret) {
-        BQ_CHK(hipMemcpyAsync(ret, d_ret, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-        BQ_CHK(hipStreamSynchronize(stream));
+        BCFGPU_CHK(hipMemcpyAsync(ret, d_ret, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+        BCFGPU_CHK(hipStreamSynchronize(stream));
     }
     D.qual = d_qo; D.qual_slot = qo_slot; D.zq = d_zo; D.r_has_zq = d_has_zq;
     return BCFGPU_OK;

@@ -1,7 +1,9 @@
 // ctx.h -- the context's internal interface, for the stages in their own translation units: the workspace slots and the
-// accessors of bcfgpu_ctx.  Defined in api.hip, except pool_view_upload and bcfgpu_internal_pool_extent (pileup.hip) and
-// bcfgpu_internal_gap_core (gap_prep.hip).  C++ linkage: none of it is part of the C-ABI of include/bcfgpu.h.
+// accessors of bcfgpu_ctx.  Defined in api.hip, except the read pool's functions (pool.hip), scan_exclusive and enc_offsets
+// (gather.hip) and bcfgpu_internal_gap_core (gap_prep.hip).  C++ linkage: none of it is part of the C-ABI of include/bcfgpu.h.
 #pragma once
+#include <thread>
+#include <vector>
 #include "kernels.h"
 
 namespace bcfgpu {
@@ -20,7 +22,7 @@ enum WsSlot : int {
     // bcfgpu_baq: what baq_core writes for it (bcfgpu_pool_baq hands the core the pool's kept slots instead): scratch for one call
     WS_BAQ_QUAL_OUT = 14, WS_BAQ_ZQ_OUT = 15, WS_BAQ_HAS_ZQ = 8,
 
-    // the read pool (pileup.hip pool_upload_impl).  Kept: DevPool, read by the pool stages below and bcfgpu_pool_pileup
+    // the read pool (pool.hip pool_upload_impl).  Kept: DevPool, read by the pool stages below and bcfgpu_pool_pileup
     WS_POOL_CIG = 27, WS_POOL_SEQ16 = 28, WS_POOL_QUAL = 29,
     WS_POOL_R_POS = 104, WS_POOL_R_LQ = 105, WS_POOL_R_FLAG = 106, WS_POOL_R_NCIG = 107, WS_POOL_R_CIG_OFF = 108,
     WS_POOL_R_SEQ_OFF = 109, WS_POOL_R_MAPQ = 110,
@@ -156,7 +158,7 @@ PileupParams *bcfgpu_internal_pileup_state(bcfgpu_ctx *c);      // the parameter
 void bcfgpu_internal_pool_replaced(bcfgpu_ctx *c);
 void bcfgpu_internal_pileup_built(bcfgpu_ctx *c, const PileupParams &P);
 bool bcfgpu_internal_pileup_pool_gone(const bcfgpu_ctx *c);
-// The staged read pool (bcfgpu_pool_stage / bcfgpu_pool_adopt, pileup.hip): the pool has two sets of its kept slots, the
+// The staged read pool (bcfgpu_pool_stage / bcfgpu_pool_adopt, pool.hip): the pool has two sets of its kept slots, the
 // context's pool in one and the pool a stage brings up in the other; adopting is a change of roles.
 struct PoolStage {
     int set = 0;                        // the set DevPool points into: 0 = WS_POOL_*, 1 = WS_POOL_B_*
@@ -179,9 +181,15 @@ PoolStage *bcfgpu_internal_pool_stage(bcfgpu_ctx *c, bool with_stream);
 void bcfgpu_internal_drop_plan(bcfgpu_ctx *c, WsSlot recs);
 int bcfgpu_set_error(int code, const char *what);               // bcfgpu_last_error() becomes `what`; returns `code`
 int bcfgpu_set_error(int code, const char *name, const char *what);     // ... becomes "`name`: `what`"
+// a HIP call of an entry point: on an error, BCFGPU_E_HIP with the call's text, and the entry returns
+#define BCFGPU_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
+// d[0 .. n) becomes its exclusive sum, queued on st; the scan's temporary storage is workspace `slot`.  Returns 0, BCFGPU_E_HIP or
+// BCFGPU_E_NOMEM (no error text is set).  The one instance of the device-wide exclusive scan in the library (gather.hip), for the
+// element types in use: uint32_t / int32_t counts and 64-bit sizes.
+template <class T> int scan_exclusive(bcfgpu_ctx *ctx, hipStream_t st, WsSlot slot, T *d, int n);
 
-// ---- a bcfgpu_reads in HBM (pileup.hip) ----
-// One slot per array.  The context's pool lies in one of two sets of kept slots (POOL_SET, pileup.hip); the host-pointer forms of
+// ---- a bcfgpu_reads in HBM (pool.hip) ----
+// One slot per array.  The context's pool lies in one of two sets of kept slots (POOL_SET, pool.hip); the host-pointer forms of
 // the read stages upload their reads to POOL_VIEW, scratch for one call, and run the pool forms' cores on that view.
 struct PoolSlots { WsSlot cig, seq16, qual, r_pos, r_lq, r_flag, r_ncig, r_cig_off, r_seq_off, r_mapq, zq, r_has_zq; };
 constexpr PoolSlots POOL_VIEW = {WS_VIEW_CIG, WS_VIEW_SEQ16, WS_VIEW_QUAL, WS_VIEW_R_POS, WS_VIEW_R_LQ, WS_VIEW_R_FLAG, WS_VIEW_R_NCIG,
@@ -196,6 +204,18 @@ int pool_view_upload(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, c
                      const PoolSlots &ps, hipStream_t stream, DevPool *D);
 // [lowest start, highest end) of D's reads, kept in D once computed
 int bcfgpu_internal_pool_extent(bcfgpu_ctx *ctx, DevPool &D, int *lo, int *hi);
+// bcfgpu_pool_upload without its wait: `rd` / `pk` become the context's read pool, copies and kernels queued on the context's stream
+// (bcfgpu_pileup[_packed] go on to the pileup and wait there, with the counts)
+int pool_upload_impl(const char *who, bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bcfgpu_packed *pk, const uint8_t *r_mapq);
+// host threads for a pass over n reads (at most 16, BCFGPU_HOST_THREADS), and fn(t) on each of them
+int host_threads(int n);
+template <class F> void on_threads(int nthr, F &&fn)
+{
+    std::vector<std::thread> thr;
+    for (int t = 1; t < nthr; ++t) thr.emplace_back(fn, t);
+    fn(0);
+    for (auto &th : thr) th.join();
+}
 // The size pass of an encoder entry `name` behind its size kernel (gather.hip): d_off[0 .. n_off) holds the blocks' sizes and a
 // last 0 and becomes their exclusive sum, the offsets; *n_bytes = their total, d_off[n_off - 1].  The stream is synchronised.
 // n_off == 1 (nothing to encode, no size kernel): the one offset is set to 0.  Returns 0 -- the caller goes on to its write

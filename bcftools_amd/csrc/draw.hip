@@ -129,7 +129,6 @@ __global__ __launch_bounds__(64) void draw_shuffle_kernel(const DrawShuffleParam
 
 using namespace bcfgpu;
 
-#define DR_CHK(call) do { if ((call) != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
 
 extern "C" int bcfgpu_errmod_plan_visit(bcfgpu_ctx *ctx, const bcfgpu_tile *snp, const uint8_t *snp_visit, const bcfgpu_tile *indel, const int32_t *indel_cols,
                                         const int32_t *indel_ret);
@@ -158,24 +157,24 @@ extern "C" int bcfgpu_errmod_plan_visit(bcfgpu_ctx *ctx, const bcfgpu_tile *snp,
         const size_t words = (size_t)((n_reads[t] + 31) / 32);
         bits[t] = (uint32_t*)bcfgpu_internal_ws(ctx, t ? WS_DRAW_BITS_INDEL : WS_DRAW_BITS_SNP, words * 4 + 64);
         if (!bits[t]) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
-        DR_CHK(hipMemsetAsync(bits[t], 0, words * 4, stream));
+        BCFGPU_CHK(hipMemsetAsync(bits[t], 0, words * 4, stream));
     }
     DrawEnt *d_ent = (DrawEnt*)bcfgpu_internal_ws(ctx, WS_DRAW_ENT, (size_t)cap * sizeof(DrawEnt) + 64);
     unsigned long long *d_ctr = (unsigned long long*)bcfgpu_internal_ws(ctx, WS_DRAW_CTR, 64);
     if (!d_ent || !d_ctr) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
-    DR_CHK(hipMemsetAsync(d_ctr, 0, 64, stream));
+    BCFGPU_CHK(hipMemsetAsync(d_ctr, 0, 64, stream));
     int32_t *d_cols = nullptr, *d_ret = nullptr;
     if (indel && indel->n_sites) {
         d_cols = (int32_t*)bcfgpu_internal_ws(ctx, WS_DRAW_COLS, (size_t)indel->n_sites * 8 + 64);
         if (!d_cols) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
-        DR_CHK(hipMemcpyAsync(d_cols, indel_cols, (size_t)indel->n_sites * 4, hipMemcpyHostToDevice, stream));
-        if (indel_ret) { d_ret = d_cols + indel->n_sites; DR_CHK(hipMemcpyAsync(d_ret, indel_ret, (size_t)indel->n_sites * 4, hipMemcpyHostToDevice, stream)); }
+        BCFGPU_CHK(hipMemcpyAsync(d_cols, indel_cols, (size_t)indel->n_sites * 4, hipMemcpyHostToDevice, stream));
+        if (indel_ret) { d_ret = d_cols + indel->n_sites; BCFGPU_CHK(hipMemcpyAsync(d_ret, indel_ret, (size_t)indel->n_sites * 4, hipMemcpyHostToDevice, stream)); }
     }
     uint8_t *d_visit = nullptr;
     if (snp && snp_visit && snp->n_sites) {
         d_visit = (uint8_t*)bcfgpu_internal_ws(ctx, WS_DRAW_VISIT, (size_t)snp->n_sites + 64);
         if (!d_visit) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
-        DR_CHK(hipMemcpyAsync(d_visit, snp_visit, (size_t)snp->n_sites, hipMemcpyHostToDevice, stream));
+        BCFGPU_CHK(hipMemcpyAsync(d_visit, snp_visit, (size_t)snp->n_sites, hipMemcpyHostToDevice, stream));
     }
     for (int t = 0; t < 2; ++t) {
         if (!tiles[t] || !tiles[t]->n_sites || !n_reads[t]) continue;
@@ -187,14 +186,14 @@ extern "C" int bcfgpu_errmod_plan_visit(bcfgpu_ctx *ctx, const bcfgpu_tile *snp,
         hipLaunchKernelGGL(draw_scan_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, stream, Q);
     }
     unsigned long long ctr[2] = {0, 0};
-    DR_CHK(hipMemcpyAsync(ctr, d_ctr, 16, hipMemcpyDeviceToHost, stream));
-    DR_CHK(hipStreamSynchronize(stream));
+    BCFGPU_CHK(hipMemcpyAsync(ctr, d_ctr, 16, hipMemcpyDeviceToHost, stream));
+    BCFGPU_CHK(hipStreamSynchronize(stream));
     const uint32_t n_ent = (uint32_t)std::min<unsigned long long>(ctr[0] & 0xffffffffull, cap);
     for (int t = 0; t < 2; ++t) if (tiles[t]) { D.rd[t] = tiles[t]->rd; D.n_reads[t] = n_reads[t]; D.bits[t] = bits[t]; }
     if (n_ent == 0) return BCFGPU_OK;
     // visit order and the draws before every cell: the list is short (a cell in it holds more than 255 reads), ranked on the host
     std::vector<DrawEnt> ent(n_ent);
-    DR_CHK(hipMemcpy(ent.data(), d_ent, (size_t)n_ent * sizeof(DrawEnt), hipMemcpyDeviceToHost));
+    BCFGPU_CHK(hipMemcpy(ent.data(), d_ent, (size_t)n_ent * sizeof(DrawEnt), hipMemcpyDeviceToHost));
     std::sort(ent.begin(), ent.end(), [](const DrawEnt &a, const DrawEnt &b) { return a.key < b.key; });
     std::vector<unsigned long long> idx_off(n_ent);
     unsigned long long draws = 0, usable = 0;
@@ -202,15 +201,15 @@ extern "C" int bcfgpu_errmod_plan_visit(bcfgpu_ctx *ctx, const bcfgpu_tile *snp,
     unsigned long long *d_ioff = (unsigned long long*)bcfgpu_internal_ws(ctx, WS_DRAW_IDX_OFF, (size_t)n_ent * 8 + 64);
     uint32_t *d_idx = (uint32_t*)bcfgpu_internal_ws(ctx, WS_DRAW_IDX, (size_t)usable * 4 + 64);
     if (!d_ioff || !d_idx) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_errmod_plan: device workspace");
-    DR_CHK(hipMemcpyAsync(d_ent, ent.data(), (size_t)n_ent * sizeof(DrawEnt), hipMemcpyHostToDevice, stream));
-    DR_CHK(hipMemcpyAsync(d_ioff, idx_off.data(), (size_t)n_ent * 8, hipMemcpyHostToDevice, stream));
+    BCFGPU_CHK(hipMemcpyAsync(d_ent, ent.data(), (size_t)n_ent * sizeof(DrawEnt), hipMemcpyHostToDevice, stream));
+    BCFGPU_CHK(hipMemcpyAsync(d_ioff, idx_off.data(), (size_t)n_ent * 8, hipMemcpyHostToDevice, stream));
     DrawShuffleParams H{};
     H.n_ent = (int)n_ent; H.min_baseQ = cfg->min_baseQ < 0 ? 0 : cfg->min_baseQ; H.ent = d_ent;
     H.rd[0] = snp ? snp->rd : nullptr; H.rd[1] = indel ? indel->rd : nullptr; H.bits[0] = bits[0]; H.bits[1] = bits[1];
     H.idx_off = d_ioff; H.idx = d_idx; H.x0 = D.x;
     hipLaunchKernelGGL(draw_shuffle_kernel, dim3((n_ent + 63) / 64), dim3(64), 0, stream, H);
-    DR_CHK(hipGetLastError());
-    DR_CHK(hipStreamSynchronize(stream));                     // (ent / idx_off are this call's host vectors)
+    BCFGPU_CHK(hipGetLastError());
+    BCFGPU_CHK(hipStreamSynchronize(stream));                     // (ent / idx_off are this call's host vectors)
     D.x = rand48_jump(D.x, draws);
     D.n_planned = n_ent;
     return BCFGPU_OK;

@@ -614,7 +614,6 @@ __global__ __launch_bounds__(256) void gap_fin_aux_kernel(const GapSite *sites, 
 
 // =====================================================================================================================
 // host: transfers and launch sequencing only
-#define GP_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, #call); } while (0)
 #define WS(slot, bytes) bcfgpu_internal_ws(ctx, slot, (bytes) + 64)      /* 64 bytes of padding on every workspace of the stage */
 
 // The stage on arrays that are already in HBM (`g`: device pointers throughout; n_ent pileup entries).  d_aux [n_ent]
@@ -644,16 +643,16 @@ int bcfgpu::bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_e
     int32_t *o_ireg = (int32_t*)(d_small + so_ireg), *o_msup = (int32_t*)(d_small + so_msup);
     float *o_mfrac = (float*)(d_small + so_mfrac);
     GapTotals *d_tot = (GapTotals*)(d_small + so_tot);
-    GP_CHK(hipMemsetAsync(d_small, 0, so_bytes, st));
-    if (n_ent) GP_CHK(hipMemsetAsync(d_aux, 0, n_ent * 4, st));
+    BCFGPU_CHK(hipMemsetAsync(d_small, 0, so_bytes, st));
+    if (n_ent) BCFGPU_CHK(hipMemsetAsync(d_aux, 0, n_ent * 4, st));
 
     // ---- typing ----
     if (nr) hipLaunchKernelGGL(gap_read_info_kernel, dim3((nr + 255) / 256), dim3(256), 0, st, g, d_rinfo);
     hipLaunchKernelGGL(gap_type_kernel, dim3(ns), dim3(256), 0, st, g, d_sites, d_rinfo, o_ret, o_types, o_msup, o_mfrac);
     hipLaunchKernelGGL(gap_scan_kernel, dim3(1), dim3(256), 0, st, d_sites, ns, n, d_tot);
     GapTotals tot{};
-    GP_CHK(hipMemcpyAsync(h_small, d_tot, sizeof(GapTotals), hipMemcpyDeviceToHost, st));
-    GP_CHK(hipStreamSynchronize(st));                           // sizes of the next stage's buffers
+    BCFGPU_CHK(hipMemcpyAsync(h_small, d_tot, sizeof(GapTotals), hipMemcpyDeviceToHost, st));
+    BCFGPU_CHK(hipStreamSynchronize(st));                           // sizes of the next stage's buffers
     memcpy(&tot, h_small, sizeof tot);
     gs.prepare_ms += ms_since(t_begin);
     if (tot.n_jobs >> 31 || tot.ref2_bytes >> 32 || tot.qpack8 >> 32)
@@ -680,16 +679,16 @@ int bcfgpu::bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_e
         int32_t *d_sumq = (int32_t*)WS(WS_GAP_SUMQ, (size_t)ns * 64 * 4);
         uint8_t *d_otype = (uint8_t*)WS(WS_GAP_OTYPE, (size_t)ns * 64);
         size_t sort_bytes = 0;
-        GP_CHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_k0, d_k1, d_v0, d_v1, (int)nj, 0, 17, st));
+        BCFGPU_CHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_k0, d_k1, d_v0, d_v1, (int)nj, 0, 17, st));
         void *d_sort = WS(WS_GAP_SORT_TMP, sort_bytes);
         if (out->inscns) d_oinscns = (int8_t*)WS(WS_GAP_OUT_INSCNS, (size_t)ns * 4 * inscns_cap);
         if (!d_inscnt || !d_inscns || !d_ref2 || !d_s1 || !d_s2 || !d_wide || !d_ent || !d_qpack || !d_pjob || !d_k0 || !d_v0 || !d_k1 || !d_v1 ||
             !d_list2 || !d_queue || !d_emt || !d_sort || !d_sumq || !d_otype || (out->inscns && !d_oinscns))
             return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep: device workspace");
-        if (tot.ins_bytes) { GP_CHK(hipMemsetAsync(d_inscnt, 0, (size_t)tot.ins_bytes * 5 * 4, st)); GP_CHK(hipMemsetAsync(d_inscns, 0, (size_t)tot.ins_bytes, st)); }
-        GP_CHK(hipMemsetAsync(d_s1, 0, nj * 4, st)); GP_CHK(hipMemsetAsync(d_s2, 0, nj * 4, st));
-        GP_CHK(hipMemsetAsync(d_sumq, 0, (size_t)ns * 64 * 4, st));
-        if (d_oinscns) GP_CHK(hipMemsetAsync(d_oinscns, 0, (size_t)ns * 4 * inscns_cap, st));
+        if (tot.ins_bytes) { BCFGPU_CHK(hipMemsetAsync(d_inscnt, 0, (size_t)tot.ins_bytes * 5 * 4, st)); BCFGPU_CHK(hipMemsetAsync(d_inscns, 0, (size_t)tot.ins_bytes, st)); }
+        BCFGPU_CHK(hipMemsetAsync(d_s1, 0, nj * 4, st)); BCFGPU_CHK(hipMemsetAsync(d_s2, 0, nj * 4, st));
+        BCFGPU_CHK(hipMemsetAsync(d_sumq, 0, (size_t)ns * 64 * 4, st));
+        if (d_oinscns) BCFGPU_CHK(hipMemsetAsync(d_oinscns, 0, (size_t)ns * 4 * inscns_cap, st));
         if (tot.ins_bytes && n_ent) hipLaunchKernelGGL(gap_inscnt_kernel, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, st, g, d_sites, (int)n_ent, d_inscnt);
         hipLaunchKernelGGL(gap_inscns_kernel, dim3(ns), dim3(64), 0, st, g, d_sites, d_inscnt, d_inscns);
         hipLaunchKernelGGL(gap_cons_kernel, dim3((unsigned)((size_t)ns * n)), dim3(GAP_CONS_THREADS), (size_t)tot.max_L * 5 + 16, st, g, d_sites, d_inscns, d_ref2);
@@ -706,16 +705,16 @@ int bcfgpu::bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_e
         hipEventCreate(&e0); hipEventCreate(&e1);
         hipEventRecord(e0, st);
         launch_probaln_jobs(p, st);
-        GP_CHK(hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_k0, d_k1, d_v0, d_v1, (int)nj, 0, 17, st));
+        BCFGPU_CHK(hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_k0, d_k1, d_v0, d_v1, (int)nj, 0, 17, st));
         launch_probaln_bounds(p, st);
         {
             hipStream_t *side = nullptr; hipEvent_t *sev = nullptr;
             if (bcfgpu_internal_side(ctx, &side, &sev) || launch_probaln_exact(p, st, bcfgpu_internal_n_cu(ctx), side, sev))
                 return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_gap_prep: side streams");
         }
-        GP_CHK(hipMemcpyAsync(h_small, d_tot, sizeof(GapTotals), hipMemcpyDeviceToHost, st));
-        GP_CHK(hipMemcpyAsync(h_small + sizeof(GapTotals), d_queue, sizeof(ProbalnQueue), hipMemcpyDeviceToHost, st));
-        GP_CHK(hipStreamSynchronize(st));                       // how many jobs need the wide-band version, and how wide
+        BCFGPU_CHK(hipMemcpyAsync(h_small, d_tot, sizeof(GapTotals), hipMemcpyDeviceToHost, st));
+        BCFGPU_CHK(hipMemcpyAsync(h_small + sizeof(GapTotals), d_queue, sizeof(ProbalnQueue), hipMemcpyDeviceToHost, st));
+        BCFGPU_CHK(hipStreamSynchronize(st));                       // how many jobs need the wide-band version, and how wide
         memcpy(&tot, h_small, sizeof tot);
         {   // jobs by band width (statistics): the register classes, the five groups of the LDS class, sixteen-a-wavefront, scratch
             ProbalnQueue hq;
@@ -747,17 +746,17 @@ int bcfgpu::bcfgpu_internal_gap_core(bcfgpu_ctx *ctx, const GapIn &g, size_t n_e
             hipLaunchKernelGGL(gap_fin_types_kernel, dim3(ns), dim3(64), 0, st, d_sites, d_sumq, d_inscns, o_types, d_oinscns, inscns_cap, o_maxins, o_ireg, d_otype);
             hipLaunchKernelGGL(gap_fin_aux_kernel, fgrid, dim3(256), 0, st, d_sites, d_otype, d_aux, o_ret);
         }
-        GP_CHK(hipGetLastError());
-        GP_CHK(hipMemcpyAsync(h_small, d_small, so_bytes, hipMemcpyDeviceToHost, st));
-        if (out->inscns) GP_CHK(hipMemcpyAsync(out->inscns, d_oinscns, (size_t)ns * 4 * inscns_cap, hipMemcpyDeviceToHost, st));
-        GP_CHK(hipStreamSynchronize(st));
+        BCFGPU_CHK(hipGetLastError());
+        BCFGPU_CHK(hipMemcpyAsync(h_small, d_small, so_bytes, hipMemcpyDeviceToHost, st));
+        if (out->inscns) BCFGPU_CHK(hipMemcpyAsync(out->inscns, d_oinscns, (size_t)ns * 4 * inscns_cap, hipMemcpyDeviceToHost, st));
+        BCFGPU_CHK(hipStreamSynchronize(st));
         hipEventElapsedTime(&gs.kernel_ms, e0, e1);
         hipEventDestroy(e0); hipEventDestroy(e1);
         memcpy(&tot, h_small + so_tot, sizeof tot);
         gs.n_passes = tot.n_passes; gs.dp_cells = tot.dp_cells;
     } else {
-        GP_CHK(hipMemcpyAsync(h_small, d_small, so_bytes, hipMemcpyDeviceToHost, st));
-        GP_CHK(hipStreamSynchronize(st));
+        BCFGPU_CHK(hipMemcpyAsync(h_small, d_small, so_bytes, hipMemcpyDeviceToHost, st));
+        BCFGPU_CHK(hipStreamSynchronize(st));
         if (out->inscns) memset(out->inscns, 0, (size_t)ns * 4 * inscns_cap);
     }
     const auto t_fin = std::chrono::steady_clock::now();
@@ -807,7 +806,7 @@ extern "C" int bcfgpu_gap_prep(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bc
     uint32_t *d_aux = (uint32_t*)WS(WS_GAP_AUX, n_ent * 4);
     if (!d_pos || !d_soff || !d_pread || !d_pqpos || !d_pindel || !d_ref || !d_aux)
         return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gap_prep: device workspace");
-    #define UP(dst, src, bytes) GP_CHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st))
+    #define UP(dst, src, bytes) BCFGPU_CHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st))
     UP(d_pos, in->pos, (size_t)ns * 4); UP(d_soff, in->smpl_off, ((size_t)ns * n + 1) * 4);
     if (n_ent) { UP(d_pread, in->p_read, n_ent * 4); UP(d_pqpos, in->p_qpos, n_ent * 4); UP(d_pindel, in->p_indel, n_ent * 4); }
     UP(d_ref, in->ref + ref_lo, (size_t)(ref_hi - ref_lo));
@@ -821,12 +820,11 @@ extern "C" int bcfgpu_gap_prep(bcfgpu_ctx *ctx, const bcfgpu_reads *rd, const bc
     if (rc) return rc;
     const auto t_dl = std::chrono::steady_clock::now();
     if (n_ent) {
-        GP_CHK(hipMemcpyAsync(out->p_aux, d_aux, n_ent * 4, hipMemcpyDeviceToHost, st));
-        GP_CHK(hipStreamSynchronize(st));
+        BCFGPU_CHK(hipMemcpyAsync(out->p_aux, d_aux, n_ent * 4, hipMemcpyDeviceToHost, st));
+        BCFGPU_CHK(hipStreamSynchronize(st));
     }
     gs.finalize_ms += ms_since(t_dl);
     gs.total_ms = ms_since(t_begin);
     return BCFGPU_OK;
 }
-#undef GP_CHK
 #undef WS

@@ -79,9 +79,8 @@ __global__ __launch_bounds__(256) void compact_copy_kernel(const bcfgpu_call_sit
     if ((uint32_t)tid < bytes - end) dst[end + tid] = 0;                            // 0-15 bytes up to the next record
 }
 
-// d[0 .. n) becomes its exclusive sum, queued on st; the scan's temporary storage is workspace `slot`.  0, BCFGPU_E_HIP or
-// BCFGPU_E_NOMEM.  The one instance of the device scan over 64-bit sizes in the library.
-static int scan_sizes(bcfgpu_ctx *ctx, hipStream_t st, WsSlot slot, unsigned long long *d, int n)
+// (ctx.h) the one instance of the device-wide exclusive scan in the library, instantiated for the element types in use
+template <class T> int scan_exclusive(bcfgpu_ctx *ctx, hipStream_t st, WsSlot slot, T *d, int n)
 {
     size_t tmp = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d, d, n, st) != hipSuccess) return BCFGPU_E_HIP;
@@ -89,6 +88,9 @@ static int scan_sizes(bcfgpu_ctx *ctx, hipStream_t st, WsSlot slot, unsigned lon
     if (!d_tmp) return BCFGPU_E_NOMEM;
     return hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, d, d, n, st) != hipSuccess ? BCFGPU_E_HIP : 0;
 }
+template int scan_exclusive<uint32_t>(bcfgpu_ctx*, hipStream_t, WsSlot, uint32_t*, int);
+template int scan_exclusive<int32_t>(bcfgpu_ctx*, hipStream_t, WsSlot, int32_t*, int);
+template int scan_exclusive<unsigned long long>(bcfgpu_ctx*, hipStream_t, WsSlot, unsigned long long*, int);
 
 int enc_offsets(bcfgpu_ctx *ctx, hipStream_t st, const char *name, uint64_t *d_off, int n_off, uint64_t cap_bytes, uint64_t *n_bytes)
 {
@@ -99,7 +101,7 @@ int enc_offsets(bcfgpu_ctx *ctx, hipStream_t st, const char *name, uint64_t *d_o
     }
     uint64_t *h_total = (uint64_t*)bcfgpu_internal_pinned(ctx, PIN_ENC_TOTAL, sizeof(uint64_t));
     if (!h_total) return bcfgpu_set_error(BCFGPU_E_NOMEM, name, "workspace");
-    const int rc = scan_sizes(ctx, st, WS_COMPACT_ENC_SCAN_TMP, reinterpret_cast<unsigned long long*>(d_off), n_off);
+    const int rc = scan_exclusive(ctx, st, WS_COMPACT_ENC_SCAN_TMP, reinterpret_cast<unsigned long long*>(d_off), n_off);
     if (rc) return bcfgpu_set_error(rc, name, rc == BCFGPU_E_HIP ? "scan" : "workspace");
     if (hipMemcpyAsync(h_total, d_off + n_off - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return bcfgpu_set_error(BCFGPU_E_HIP, name, "size pass");
@@ -125,7 +127,7 @@ extern "C" int bcfgpu_compact_calls_async(bcfgpu_ctx *ctx, int32_t n_sites, int3
     if (!d_size) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_compact_calls_async: device workspace");
     hipLaunchKernelGGL(compact_size_kernel, dim3((n_sites + 256) / 256), dim3(256), 0, st, cout->site, n_sites, S, variants_only, d_size,
                        reinterpret_cast<unsigned long long*>(d_counts));
-    const int rc = scan_sizes(ctx, st, WS_COMPACT_SCAN_TMP, d_size, n_sites + 1);
+    const int rc = scan_exclusive(ctx, st, WS_COMPACT_SCAN_TMP, d_size, n_sites + 1);
     if (rc) return bcfgpu_set_error(rc, rc == BCFGPU_E_HIP ? "scan" : "bcfgpu_compact_calls_async: device workspace");
     hipLaunchKernelGGL(compact_copy_kernel, dim3(n_sites), dim3(256), 0, st, cout->site, msite, cout->gt, cout->pl, n_gt_planes, S, n_sites, site0,
                        variants_only, d_size, (unsigned char*)d_buf, (unsigned long long)cap_bytes, reinterpret_cast<unsigned long long*>(d_counts));

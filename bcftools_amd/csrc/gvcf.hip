@@ -130,7 +130,6 @@ __global__ __launch_bounds__(64) void gvcf_reduce_kernel(const GvcfParams P, int
 
 using namespace bcfgpu;
 
-#define GV_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bcfgpu_set_error(BCFGPU_E_HIP, hipGetErrorString(e_)); } while (0)
 
 extern "C" int bcfgpu_gvcf_blocks(bcfgpu_ctx *ctx, const bcfgpu_gvcf_in *in, const bcfgpu_gvcf_out *out, int32_t *n_blocks)
 {
@@ -154,24 +153,24 @@ extern "C" int bcfgpu_gvcf_blocks(bcfgpu_ctx *ctx, const bcfgpu_gvcf_in *in, con
     P.ref_only = in->ref_only; P.dp32 = in->dp; P.end = in->end;
     P.blk = out->blk; P.min_dp = out->min_dp; P.block = out->block; P.dp_out = out->dp; P.pl_out = out->pl;
     size_t tmp_bytes = 0;
-    GV_CHK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, (int32_t*)nullptr, (int32_t*)nullptr, n, stream));
+    BCFGPU_CHK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, (int32_t*)nullptr, (int32_t*)nullptr, n, stream));
     int32_t *w = (int32_t*)bcfgpu_internal_ws(ctx, WS_GVCF_SCAN, (size_t)n * 3 * sizeof(int32_t));
     void *d_tmp = bcfgpu_internal_ws(ctx, WS_GVCF_SCAN_TMP, tmp_bytes + 16);
     if (!w || !d_tmp) return bcfgpu_set_error(BCFGPU_E_NOMEM, "bcfgpu_gvcf_blocks: workspace");
     P.range = w; P.head = w + n; P.scan = w + 2 * (size_t)n;
     hipLaunchKernelGGL(gvcf_site_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, P);
     hipLaunchKernelGGL(gvcf_head_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, P);
-    GV_CHK(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, P.head, P.scan, n, stream));
+    BCFGPU_CHK(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, P.head, P.scan, n, stream));
     hipLaunchKernelGGL(gvcf_block_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, P);
     int32_t nb = 0;
-    GV_CHK(hipMemcpyAsync(&nb, P.scan + (n - 1), sizeof nb, hipMemcpyDeviceToHost, stream));
-    GV_CHK(hipStreamSynchronize(stream));
+    BCFGPU_CHK(hipMemcpyAsync(&nb, P.scan + (n - 1), sizeof nb, hipMemcpyDeviceToHost, stream));
+    BCFGPU_CHK(hipStreamSynchronize(stream));
     if (nb < 0 || nb > n) return bcfgpu_set_error(BCFGPU_E_HIP, "bcfgpu_gvcf_blocks: block count out of range");
     if (nb) {
         const int chunks = (P.n_smpl + 63) / 64;
         hipLaunchKernelGGL(gvcf_reduce_kernel, dim3((unsigned)nb * chunks), dim3(64), 0, stream, P, chunks);
     }
-    GV_CHK(hipGetLastError());
+    BCFGPU_CHK(hipGetLastError());
     *n_blocks = nb;
     return BCFGPU_OK;
 }

@@ -133,7 +133,7 @@ struct McallParams {
     int small_too;                  // mcall_kernel<5, 15, ...> also takes the sites of at most three alleles (launch_mcall)
 };
 
-// ---- the read pool of a region kept in HBM (bcfgpu_pool_upload; pileup.hip, baq.hip, overlap.hip, capmapq.hip) ----
+// ---- the read pool of a region kept in HBM (bcfgpu_pool_upload; pool.hip, pileup.hip, baq.hip, overlap.hip, capmapq.hip) ----
 // The caller's per-read arrays as they were handed over, the pools one byte per base; the stages replace `qual` / `r_mapq`
 // in place or swing the pointer to a buffer of their own.
 struct DevPool {

@@ -68,13 +68,10 @@ def test_cigar_classes(gpu_ctx_factory, want_epos, packed):
 
 
 # ---- 2. entries ----
-def test_entries_of_the_classes(gpu_ctx_factory):
-    """bcfgpu_pileup_entries (entry_of_read, the CIGAR walk stated a second time): every column with an indel and ten without."""
-    ctx, (want, w_n, w_indel, entries) = _run(gpu_ctx_factory, "classes")
+def _assert_entries(ctx, ref, cols):
+    """bcfgpu_pileup_entries of columns `cols` of the pileup on ctx against the reference's; returns (read, qpos, indel)."""
+    want, w_n, _, entries = ref
     S = want.n_smpl
-    plain = np.nonzero((w_indel == 0) & (w_n > 0))[0]
-    cols = np.sort(np.concatenate([np.nonzero(w_indel)[0], plain[:: max(1, len(plain) // 10)][:10]])).astype(np.int32)
-    assert (w_indel[cols] == 0).sum() == 10 and w_indel[cols].sum() == w_indel.sum() > 5
     cap = int(w_n[cols].sum())
     so = np.zeros(len(cols) * S + 1, np.int32)
     pr, pq, pi = (np.zeros(cap, np.int32) for _ in range(3))
@@ -86,7 +83,40 @@ def test_entries_of_the_classes(gpu_ctx_factory):
     flat = [t for c in cols for t in entries[int(c)]]
     for k, (got, name) in enumerate(((pr, "read"), (pq, "qpos"), (pi, "indel"))):
         np.testing.assert_array_equal(got, np.array([t[k] for t in flat], np.int32), err_msg=name)
+    return pr, pq, pi
+
+
+def test_entries_of_the_classes(gpu_ctx_factory):
+    """bcfgpu_pileup_entries (resolve_cigar, the fill pass's walk, from a wavefront per cell): every column with an indel and ten without."""
+    ctx, ref = _run(gpu_ctx_factory, "classes")
+    _, w_n, w_indel, _ = ref
+    plain = np.nonzero((w_indel == 0) & (w_n > 0))[0]
+    cols = np.sort(np.concatenate([np.nonzero(w_indel)[0], plain[:: max(1, len(plain) // 10)][:10]])).astype(np.int32)
+    assert (w_indel[cols] == 0).sum() == 10 and w_indel[cols].sum() == w_indel.sum() > 5
+    _, _, pi = _assert_entries(ctx, ref, cols)
     assert {2, 3, 4, -1, -2} <= set(pi.tolist())
+
+
+@pytest.mark.parametrize("name", ["classes", "shape_17x17", "shape_33x16"])
+def test_entries_of_every_column(gpu_ctx_factory, name):
+    """The entries' query offset and indel in every column that has entries -- one entry per record of the tile, in the tile's
+    order -- so that the columns inside a deletion and inside a reference skip, those of soft-clipped reads, the last base before
+    pads and an insertion, before consecutive insertions and before a deletion are all among them; two tiles of fewer than 64
+    columns that cross the 16-column edge of the fill pass's workgroups beside the classes."""
+    ctx, ref = _run(gpu_ctx_factory, name)
+    want, w_n, _, _ = ref
+    pr, pq, pi = _assert_entries(ctx, ref, np.nonzero(w_n > 0)[0].astype(np.int32))
+    assert len(pr) == len(want.rd) > 0
+    if name == "classes":
+        pool = G.cases()[name].pool
+        for flag in (abi.RD_DEL, abi.RD_SKIP, abi.RD_SCLIP):
+            assert (want.rd & flag).any()
+        assert ((want.rd & abi.RD_SCLIP) != 0)[pq > 0].any()                   # a soft clip before the entry's base
+        by_class = {}
+        for r, d in zip(pr.tolist(), pi.tolist()):
+            by_class.setdefault(pool[r].name, set()).add(d)
+        assert 3 in by_class["M_P_I_P_I_M"] and 4 in by_class["M_I_I_M"] and -2 in by_class["M_P_D_M"] and -2 in by_class["M_D"]
+        assert by_class["M_N_M"] == {0} and by_class["M_N"] == {0}
 
 
 # ---- 3. window and ties ----

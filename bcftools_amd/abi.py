@@ -225,6 +225,15 @@ class VcfRewrite(C.Structure):
 VCF_REWRITE = [("off", "<u8"), ("r_mask", "<u8"), ("len", "<u4"), ("pl_idx", "<i4"), ("n_fmt", "<i2"), ("nals", "<i2"), ("flags", "<i4")]
 
 
+class VcfKey(C.Structure):
+    """bcfgpu_vcf_key: one integer pass-through FORMAT key of one record of VCF text input, a job of bcfgpu_call_parse_keys_vcf (32 bytes)."""
+    _fields_ = [("site", C.c_int32), ("key_id", C.c_int32), ("idx", C.c_int32), ("nals", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+VCF_KEY = [("site", "<i4"), ("key_id", "<i4"), ("idx", "<i4"), ("nals", "<i4"), ("flags", "<i4"), ("reserved", "<i4", (3,))]
+
+
 class Timing(C.Structure):
     _fields_ = [("glfgen_ms", C.c_float), ("combine_ms", C.c_float),
                 ("mcall_ms", C.c_float), ("total_ms", C.c_float)]
@@ -307,6 +316,9 @@ PROTOTYPES = {
                                          C.c_uint64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_call_rewrite_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.POINTER(VcfRewrite), C.c_int32, C.c_void_p,
                                           C.c_uint64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bcfgpu_call_parse_keys_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(VcfKey), C.c_int32, C.POINTER(VcfVec), C.c_int32, C.c_void_p, C.c_uint64,
+                                             C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                             C.c_void_p]),
     "bcfgpu_comm_init_all":(C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]),
     "bcfgpu_comm_destroy": (None, [C.c_void_p]),
     "bcfgpu_gather_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),

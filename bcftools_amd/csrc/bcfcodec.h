@@ -1,5 +1,5 @@
 // bcfcodec.h -- what the device codecs of the records' per-sample bytes have in common (bcfenc.hip, vcfenc.hip, bcfcallenc.hip,
-// bcfkeys.hip, bcfdec.hip, vcfcallenc.hip, vcfdec.hip, vcfcallrw.hip): the line-wise copy between global memory and the LDS stage, the BCF2 block
+// bcfkeys.hip, bcfdec.hip, vcfcallenc.hip, vcfdec.hip, vcfcallrw.hip, vcfkeys.hip): the line-wise copy between global memory and the LDS stage, the BCF2 block
 // header and typed-value rules (bcf_enc_vint / bcf_dec_int of htslib vcf.c; here host/vcfio.c enc_int1 / enc_size / enc_vint /
 // dec_int), the workgroup maximum of the size kernels, decimal text written and read, the reading of a pass-through key from the
 // input's bytes, and the FORMAT keys of an mpileup record.  Device and host-inline code only.
@@ -154,7 +154,7 @@ __device__ __forceinline__ int text_value(unsigned char *p, int32_t v)
 // one GT entry: an allele index as its digit, anything else '.'
 __device__ __forceinline__ unsigned char gt_char(int g) { return g >= 0 && g <= 9 ? (unsigned char)('0' + g) : (unsigned char)'.'; }
 
-// ---- reading text (vcfdec.hip, vcfcallrw.hip) ----
+// ---- reading text (vcfdec.hip, vcfcallrw.hip, vcfkeys.hip) ----
 constexpr uint32_t VDEC_NO_ERROR = 0xffffffffu;                 // an error word of the indexing pass nobody has touched; else the smallest site at fault
 // bit i of the result: byte i of the 16-byte line w is c (the exact zero-byte test on w ^ cccc, then the four high bits of a word
 // gathered by one multiplication whose partial products meet on no bit)

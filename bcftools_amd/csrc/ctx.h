@@ -99,13 +99,19 @@ enum WsSlot : int {
     // bcfgpu_call_rewrite_vcf (vcfcallrw.hip): the uploaded copies of the records' runs (as the indexing kernel reads them), of the
     // records and of the sample map, the offsets of the columns of one chunk of sites (bounded as bcfgpu_call_decode_vcf's), the error word
     WS_COMPACT_VCFRW_VEC = 182, WS_COMPACT_VCFRW_REC = 183, WS_COMPACT_VCFRW_COL = 184, WS_COMPACT_VCFRW_START = 185, WS_COMPACT_VCFRW_ERR = 186,
+    // bcfgpu_call_parse_keys_vcf (vcfkeys.hip): the uploaded copies of the key jobs (each with its run's place among the indexed runs)
+    // and of the sample map, one packed word a job (the block's integer type and width), one status byte a job, the runs of the sites
+    // that have a job with a record (as the indexing kernel reads them), the offsets of the columns of one chunk of them (bounded as
+    // bcfgpu_call_decode_vcf's), the error word
+    WS_COMPACT_VCFKEY_JOBS = 187, WS_COMPACT_VCFKEY_COL = 188, WS_COMPACT_VCFKEY_WORD = 189, WS_COMPACT_VCFKEY_STATUS = 190,
+    WS_COMPACT_VCFKEY_RUNS = 191, WS_COMPACT_VCFKEY_START = 192, WS_COMPACT_VCFKEY_ERR = 193,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_COMPACT_VCFRW_ERR + 1       // one past the highest slot
+    WS_COUNT = WS_COMPACT_VCFKEY_ERR + 1      // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names
@@ -130,7 +136,8 @@ enum PinnedSlot : int {
     PIN_ENC_TOTAL = 7,                  // enc_offsets: the size of all blocks of an encoder entry (each synchronises before it returns)
     PIN_VCFDEC_ERR = 8,                 // bcfgpu_call_decode_vcf: the error words of its two passes (it synchronises before it reads them)
     PIN_VCFRW_ERR = 9,                  // bcfgpu_call_rewrite_vcf: the error word of its indexing pass (it synchronises before it reads it)
-    PINNED_COUNT = PIN_VCFRW_ERR + 1        // one past the highest slot
+    PIN_VCFKEY_ERR = 10,                // bcfgpu_call_parse_keys_vcf: the error word of its indexing pass (it synchronises before it reads it)
+    PINNED_COUNT = PIN_VCFKEY_ERR + 1       // one past the highest slot
 };
 
 // workspace / pinned host buffer `slot` of at least `bytes` (contents undefined); nullptr when the allocation fails

@@ -588,6 +588,50 @@ class Context:
             self.release(bufs)
         return data, offs
 
+    def parse_keys_vcf(self, text, keys, run, n_smpl_in, site, col=None, emit=None, cap_bytes=None):
+        """bcfgpu_call_parse_keys_vcf: the integer pass-through FORMAT keys of call records of VCF text input as BCF2 key blocks.  text:
+        the input records' sample columns (bytes or np.uint8) and site: the call's site records (a host array of abi.CallSite layout),
+        both uploaded here; keys: the jobs, an array of abi.VCF_KEY; run: one (off, len) a site, an array of abi.VCF_VEC; col: the input
+        column of each called sample, or None; emit: host u8 [n_sites] or None; cap_bytes: the buffer's size (None: asked from the
+        size pass first).  Returns (bytes as np.uint8, offsets as np.uint64 [n_keys + 1], status as np.uint8 [n_keys]); BcfGpuError
+        with code E_RANGE, .needed = the size and .status when cap_bytes is too small."""
+        text = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+        k = np.ascontiguousarray(keys, dtype=abi.VCF_KEY)
+        r = np.ascontiguousarray(run, dtype=abi.VCF_VEC)
+        site = np.ascontiguousarray(site)
+        assert len(r) == len(site)
+        c = None if col is None else np.ascontiguousarray(col, np.int32)
+        assert c is None or len(c) == self.cfg.n_smpl
+        status = np.zeros(len(k) + 1, np.uint8)
+        off, n = self.buf(8 * (len(k) + 1)), C.c_uint64(0)
+        bufs = [off, self.to_device(text), self.to_device(site.view(np.uint8).reshape(-1))]
+        d_emit = None
+        if emit is not None:
+            bufs.append(self.to_device(np.ascontiguousarray(emit, dtype=np.uint8)))
+            d_emit = bufs[-1].ptr
+        args = (len(k), k.ctypes.data_as(C.POINTER(abi.VcfKey)), len(r), r.ctypes.data_as(C.POINTER(abi.VcfVec)), n_smpl_in,
+                bufs[1].ptr if text.nbytes else None, text.nbytes, None if c is None else c.ctypes.data_as(C.POINTER(C.c_int32)), bufs[2].ptr, d_emit)
+        try:
+            if cap_bytes is None:
+                rc = self.L.bcfgpu_call_parse_keys_vcf(self.h, *args, None, 0, off.ptr, C.byref(n), status.ctypes.data)
+                if rc not in (0, abi.E_RANGE):
+                    check(rc)
+                cap_bytes = n.value
+            out = self.buf(cap_bytes)
+            bufs.append(out)
+            rc = self.L.bcfgpu_call_parse_keys_vcf(self.h, *args, out.ptr, cap_bytes, off.ptr, C.byref(n), status.ctypes.data)
+            if rc:
+                e = BcfGpuError(rc, self.L.bcfgpu_last_error().decode())
+                e.needed, e.status = n.value, status[:len(k)].copy()
+                raise e
+            data, offs = np.zeros(n.value, np.uint8), np.zeros(len(k) + 1, np.uint64)
+            if n.value:
+                out.download(data)
+            off.download(offs)
+        finally:
+            self.release(bufs)
+        return data, offs, status[:len(k)].copy()
+
     def timing(self, on=True):
         check(self.L.bcfgpu_timing_enable(self.h, 1 if on else 0))
 

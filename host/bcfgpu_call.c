@@ -32,8 +32,16 @@
  *              the decode and bcfgpu_call_remap_bcf makes those keys' blocks of the written records there -- the -S sample choice,
  *              the Number=R values following als_map, width and type chosen anew -- one size call and one write call over all of
  *              them.  The host splices them in their keys' places; Float and String keys and GP stay on the host
- *              (vio_encode_keys), and a record without any of those forms no sample text at all.  In any other run the option does
- *              nothing.  The same output either way.
+ *              (vio_encode_keys), and a record without any of those forms no sample text at all.
+ *              With --device-parse and --device-records both in effect (text in, BCF out) the same for VCF text input: the columns'
+ *              text stays in HBM after the decode and bcfgpu_call_parse_keys_vcf makes the blocks there from every written record's
+ *              own columns -- a job for each key of the FORMAT column that the header declares Type=Integer, that is not PL, not
+ *              named GT and stands among the first 64 keys; token by token, the exact integer grammar, the -S sample choice, the
+ *              Number=R values following als_map, width and type chosen anew.  A key one of whose values the grammar refuses (an
+ *              empty value, `12x`, a blank, a number past int32: strtol makes something of each) or that is wider than 255 values
+ *              comes back flagged and is the host's again, with Float and String keys and GP: the host's text of a record holds only
+ *              those keys' tokens, and a record with integer keys alone and no GP has no column copied or split.
+ *              In any other run the option does nothing.  The same output either way.
  *          --device-text: with -O v|z and --device-input in effect, the sample columns of the written records are not formed on the
  *              host either: the input records' bytes stay in HBM after the decode and bcfgpu_call_encode_vcf formats every such
  *              record's columns there -- GT, the input's keys in their order with the trimmed PL in PL's place (nothing when PL is
@@ -75,7 +83,8 @@
  * with --device-parse: line = the first nine columns, the sample columns' text (from the ninth tab on) = ilen bytes at ioff */
 typedef struct { char *line; char **fld; int nfld; char **als; int nals, unseen, pl_idx, ad_idx; uint8_t *ploidy;
                  size_t ioff, ilen; int n_fmt, nkeys; vio_indiv_key *keys;
-                 int *kjob; } rec_t;            /* --device-keys, a written record: key i's job of bcfgpu_call_remap_bcf, or -1 (the host's) */
+                 int *kjob, nkjob; } rec_t;     /* --device-keys, a written record: key i's job of bcfgpu_call_remap_bcf (text input: of
+                                                 * bcfgpu_call_parse_keys_vcf), or -1 (the host's); nkjob entries, one a FORMAT key */
 
 typedef struct { char chrom[256]; int from, to, ploidy; char sex[64]; } preg_t;
 
@@ -430,7 +439,7 @@ typedef struct { int32_t *nals, *unseen, *pl, *ad, *pan, *pac; float *qs, *i16; 
 typedef struct {                                                /* the planes in HBM, and what came down of the results */
     bcfgpu_ctx *ctx;
     int32_t *d_nals, *d_unseen, *d_plin, *d_ad, *d_grp, *d_pan, *d_pac; float *d_qs, *d_i16;
-    void *d_indiv;                                              /* --device-keys, --device-text: kept until the pass-through keys / the columns are made */
+    void *d_indiv;                                              /* --device-keys, --device-text: the input's bytes or text, kept until the pass-through keys / the columns are made */
     void *d_site, *d_gt, *d_pl, *d_ploidy, *d_gq, *d_gp;
     bcfgpu_call_site *cs; int8_t *gt; int32_t *opl, *gq; float *gp;
 } dev_t;
@@ -521,7 +530,8 @@ static int parse_options(int argc, char **argv, opt_t *o)
     if (o->gv_n && o->varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (o->gv_n && cals) DIE("-g with -C alleles is not supported\n");
     if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-parse] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"
-        "       --device-text acts with -O v|z where --device-input (BCF in) or --device-parse (VCF text in) is in effect\n"); return 2; }
+        "       --device-text acts with -O v|z where --device-input (BCF in) or --device-parse (VCF text in) is in effect\n"
+        "       --device-keys acts with -O u|b where --device-records and --device-input (BCF in) or --device-parse (VCF text in) are in effect\n"); return 2; }
     o->in_path = argv[1]; return 0;
 }
 static void load_ploidy(opt_t *o, ploidy_t *P)
@@ -575,7 +585,7 @@ static vio_file *open_input(opt_t *o, vio_hdr **hdr)
     o->dev_in = o->dev_in && vio_is_bcf(fin) && !cals && !o->gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
     o->dev_parse = o->dev_parse && !vio_is_bcf(fin) && !cals && !o->gv_n;   /* the same two, for the same reasons, on text input */
     o->dev_rec = o->dev_rec && (o->out_mode == 'u' || o->out_mode == 'b') && !o->gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
-    o->dev_keys = o->dev_keys && o->dev_in && o->dev_rec;      /* the input's bytes in HBM and key blocks to splice: both ends on the device */
+    o->dev_keys = o->dev_keys && (o->dev_in || o->dev_parse) && o->dev_rec;      /* the input's bytes or text in HBM and key blocks to splice: both ends on the device */
     o->dev_text = o->dev_text && (o->dev_in || o->dev_parse) && (o->out_mode == 'v' || o->out_mode == 'z');   /* the input's bytes or text in HBM, text records to write */
     return fin;
 }
@@ -695,7 +705,7 @@ static void read_records(const opt_t *o, const ploidy_t *P, const smap_t *M, vio
         }
         r->line = smp ? strndup(use, (size_t)(smp - use)) : strdup(use);
         r->fld = split(r->line, '\t', &r->nfld);
-        r->keys = NULL; r->nkeys = 0; r->kjob = NULL;
+        r->keys = NULL; r->nkeys = 0; r->kjob = NULL; r->nkjob = 0;
         if (smp) {                                               /* the columns join the byte buffer as they are */
             const size_t l_smp = strlen(smp);
             if (R->ibuf_l + l_smp > R->ibuf_m) { R->ibuf_m = (R->ibuf_l + l_smp) * 2 + (1 << 20); R->ibuf = realloc(R->ibuf, R->ibuf_m); if (!R->ibuf) DIE("out of memory\n"); }
@@ -887,7 +897,7 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
             CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); D->d_ad = dp;
             decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_ad, cmap, namax, D->d_ad);
         }
-        if (!o->dev_text) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
+        if (!o->dev_keys && !o->dev_text) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
     } else {
         D->d_plin = dev_upload(ctx, H->pl, (size_t)n * ngmax * S * 4);
         if (H->ad) D->d_ad = dev_upload(ctx, H->ad, (size_t)n * namax * S * 4);
@@ -983,13 +993,63 @@ static int remap_call(void *arg, void *d_buf, uint64_t cap, uint64_t *d_off, uin
     const remap_arg *a = arg;
     return bcfgpu_call_remap_bcf(a->ctx, a->n_job, a->job, a->S_in, a->d_indiv, a->l_indiv, a->cmap, a->d_site, a->n, a->d_emit, d_buf, cap, d_off, need);
 }
-static void encode_key_blocks(const opt_t *o, const smap_t *M, recs_t *R, dev_t *D, const vio_hdr *hdr, blocks_t *B)
+/* the same on text input (--device-parse): the jobs come from the record's FORMAT column, the blocks from the columns' text where
+ * --device-parse left it.  A job the device flags (a value outside the exact integer grammar, a key wider than 255 values) goes back to
+ * the host: its block has zero length and the text route makes the key */
+typedef struct { bcfgpu_ctx *ctx; int32_t n_job; const bcfgpu_vcf_key *job; int n; const bcfgpu_vcf_vec *run; int S_in; const void *d_text; size_t l_text; const int32_t *cmap;
+                 const void *d_site, *d_emit; uint8_t *status; } parse_keys_arg;
+static int parse_keys_call(void *arg, void *d_buf, uint64_t cap, uint64_t *d_off, uint64_t *need)
 {
+    const parse_keys_arg *a = arg;
+    return bcfgpu_call_parse_keys_vcf(a->ctx, a->n_job, a->job, a->n, a->run, a->S_in, a->d_text, a->l_text, a->cmap, a->d_site, a->d_emit, d_buf, cap, d_off, need, a->status);
+}
+static void parse_key_blocks(const opt_t *o, const smap_t *M, recs_t *R, const hplanes_t *H, dev_t *D, const vio_hdr *hdr, blocks_t *B)
+{
+    size_t cap_job = 0; bcfgpu_vcf_key *job = NULL;
+    for (int k = 0; k < R->n; ++k) {
+        rec_t *r = &R->rec[k];
+        if (!B->emit[k]) continue;
+        int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
+        r->kjob = malloc((size_t)nk * sizeof *r->kjob); r->nkjob = nk;
+        for (int i = 0; i < nk; ++i) {
+            r->kjob[i] = -1;
+            if (i == r->pl_idx || i >= BCFGPU_VCF_REWRITE_MAX_KEYS || !strcmp(keys[i], "GT")) continue;
+            const int id = vio_hdr_fmt_id(hdr, keys[i]);
+            if (id < 0 || vio_hdr_fmt_type(hdr, id) != VIO_TYPE_INT) continue;
+            if ((size_t)B->n_pjob == cap_job) { cap_job = cap_job ? 2 * cap_job : 4096; job = realloc(job, cap_job * sizeof *job); if (!job) DIE("out of memory\n"); }
+            bcfgpu_vcf_key *j = &job[B->n_pjob];
+            memset(j, 0, sizeof *j);
+            j->site = k; j->key_id = id; j->idx = i; j->nals = r->nals;
+            j->flags = is_numberR(fmtR, n_fmtR, keys[i], strlen(keys[i]));
+            r->kjob[i] = (int)B->n_pjob++;
+        }
+        free(keys); free(fmt);
+    }
+    if (B->n_pjob > INT32_MAX - 1) DIE("too many pass-through keys for one call\n");
+    if (B->n_pjob) {
+        uint8_t *status = calloc((size_t)B->n_pjob, 1);
+        parse_keys_arg a = { D->ctx, (int32_t)B->n_pjob, job, R->n, H->txt_pl, M->S_in, D->d_indiv, R->ibuf_l, o->smpl_file ? (const int32_t *)M->col : NULL, D->d_site, B->d_emit, status };
+        encode_two_pass(D->ctx, parse_keys_call, &a, "bcfgpu_call_parse_keys_vcf", (size_t)B->n_pjob + 1, &B->pblk, &B->poff);
+        long n_flagged = 0;
+        for (long j = 0; j < B->n_pjob; ++j) n_flagged += status[j] != 0;
+        for (int k = 0; n_flagged && k < R->n; ++k) {              /* the flagged jobs are the host's again */
+            rec_t *r = &R->rec[k];
+            for (int i = 0; r->kjob && i < r->nkjob; ++i) if (r->kjob[i] >= 0 && status[r->kjob[i]]) r->kjob[i] = -1;
+        }
+        B->n_pjob -= n_flagged;                                  /* (write_record counts them under the host's) */
+        free(status);
+    } else B->poff = calloc(1, 8);
+    free(job);
+    CHECK(bcfgpu_free(D->ctx, D->d_indiv)); D->d_indiv = NULL;
+}
+static void encode_key_blocks(const opt_t *o, const smap_t *M, recs_t *R, const hplanes_t *H, dev_t *D, const vio_hdr *hdr, blocks_t *B)
+{
+    if (o->dev_parse) { parse_key_blocks(o, M, R, H, D, hdr, B); return; }
     size_t cap_job = 0; bcfgpu_bcf_key *job = NULL;
     for (int k = 0; k < R->n; ++k) {
         rec_t *r = &R->rec[k];
         if (!B->emit[k]) continue;
-        r->kjob = malloc((size_t)(r->nkeys ? r->nkeys : 1) * sizeof *r->kjob);
+        r->kjob = malloc((size_t)(r->nkeys ? r->nkeys : 1) * sizeof *r->kjob); r->nkjob = r->nkeys;
         for (int i = 0; i < r->nkeys; ++i) {
             const vio_indiv_key *q = &r->keys[i];
             r->kjob[i] = -1;
@@ -1357,7 +1417,7 @@ static void write_record(writer_t *W, int k, int gv_min_dp)
     fmt_t F; char *fmt = strdup(r->fld[8]); F.keys = split(fmt, ':', &F.nk);
     F.called = nn > 1 && c->ret > 0;                           /* mcall_call_genotypes ran: GP and GQ exist (mcall.c:1618-1623) */
     /* --device-records: GT, PL and GQ are blocks already; the sample text holds the other keys alone (host_keys of them) */
-    F.kjob = o->dev_keys && r->kjob && F.nk == r->nkeys ? r->kjob : NULL;     /* the keys whose blocks the device made */
+    F.kjob = o->dev_keys && r->kjob && F.nk == r->nkjob ? r->kjob : NULL;     /* the keys whose blocks the device made */
     F.host_keys = dev_rec ? F.nk - 1 + (F.called && D->gp) : 0;
     for (int i = 0; F.kjob && i < F.nk; ++i) F.host_keys -= F.kjob[i] >= 0;
     const int text_ready = o->dev_text && W->B->toff[k + 1] > W->B->toff[k];     /* --device-text: the sample columns came from the device */
@@ -1438,7 +1498,7 @@ int main(int argc, char **argv)
     if (o.dev_rec) {
         const double te = now_s();
         encode_call_blocks(&o, &R, &D, hdr, &B);
-        if (o.dev_keys) encode_key_blocks(&o, &M, &R, &D, hdr, &B);
+        if (o.dev_keys) encode_key_blocks(&o, &M, &R, &H, &D, hdr, &B);
         free(B.emit);
         t_enc = now_s() - te;                                    /* a device stage: counted there, not under writing */
     }

@@ -47,7 +47,7 @@ int  vio_write_record_int(vio_file *f, const vio_hdr *h, const char *head, int n
 int  vio_hdr_fmt_id(const vio_hdr *h, const char *id);
 /* The Type the header declares for the FORMAT key at dictionary index `dict` (vio_indiv_key.dict, vio_hdr_fmt_id): VIO_TYPE_*, or -1
  * when the index is outside the dictionary or no FORMAT line declares the key.  What a writer needs to know before it takes a key's
- * stored integers for integers (bcfgpu_call_remap_bcf). */
+ * stored integers for integers (bcfgpu_call_remap_bcf), or parses a key's text as integers (bcfgpu_call_parse_keys_vcf). */
 enum { VIO_TYPE_FLAG = 0, VIO_TYPE_INT = 1, VIO_TYPE_FLOAT = 2, VIO_TYPE_STR = 3 };
 int  vio_hdr_fmt_type(const vio_hdr *h, int dict);
 /* A BCF record whose per-sample part is encoded already (bcfgpu_mplp_encode_bcf): `head` as for vio_write_record_int -- the shared part
@@ -63,7 +63,8 @@ int  vio_write_record_text(vio_file *f, const vio_hdr *h, const char *head, cons
  * Every key's block -- typed key id, descriptor, values, exactly the bytes vio_write_line puts into a record's per-sample part for that
  * key -- is appended to *out (a malloc'ed buffer that grows, *cap its size; overwritten from its start); key_end[k] = the bytes of
  * *out up to and including key k's block (room for 64).  The number of keys, or -1.  A writer that has other keys' blocks ready
- * (bcfgpu_call_encode_bcf) puts these between them and hands the whole to vio_write_record_indiv. */
+ * (bcfgpu_call_encode_bcf; bcfgpu_call_remap_bcf or, on text input, bcfgpu_call_parse_keys_vcf for the integer keys it passes through)
+ * puts these between them and hands the whole to vio_write_record_indiv: `fmt` and `samples` then hold only the keys left to the host. */
 int  vio_encode_keys(const vio_hdr *h, const char *fmt, const char *samples, int n_sample, char **out, size_t *cap, size_t *key_end);
 vio_file *vio_open_read(const char *path);                      /* path "-" = stdin; VCF, bgzipped VCF or BCF2, detected */
 vio_hdr *vio_read_hdr(vio_file *f);

@@ -40,6 +40,8 @@
  *                                           caller's GT / PL / GQ and the pass-through keys interleaved in FORMAT order
  *    bcfgpu_call_rewrite_vcf             <- the same for VCF text input: the written records' sample columns rewritten token by token
  *                                           from the input columns' text, around GT, the trimmed PL and GQ
+ *    bcfgpu_call_parse_keys_vcf          <- what bcfgpu_call_remap_bcf stands for, on VCF text input: the integer pass-through keys' BCF2 blocks
+ *                                           parsed from the input columns' text (vcf_parse_format behind the same writer)
  *
  *  Memory model: all bulk arrays are *device* pointers (HBM).  Hosts that do
  *  not link HIP use bcfgpu_malloc/free/memcpy_*.  Kernels are enqueued on the
@@ -947,6 +949,63 @@ int  bcfgpu_call_rewrite_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_gt_max,
                              const bcfgpu_vcf_rewrite *rec /* HOST [n_sites] */, int32_t n_smpl_in,
                              const void *d_text, uint64_t n_text_bytes, const int32_t *col,
                              const uint8_t *d_emit, void *d_buf, uint64_t cap_bytes, uint64_t *d_off, uint64_t *n_bytes);
+
+/* The pass-through keys where the input is VCF text and the output BCF (vcfkeys.hip): the integer FORMAT keys of the input records other
+ * than PL as the BCF2 key blocks of the written records -- the blocks of bcfgpu_call_remap_bcf, made from the input records' own sample
+ * columns, the text bcfgpu_call_decode_vcf parsed, still in HBM.  One job a key and record; the blocks are complete in themselves (typed
+ * key id, descriptor, values) and have an offset each.  The rule is the text route's, byte for byte: print_sample_text / print_numberR of
+ * host/bcfgpu_call.c, then split_samples / encode_fmt_key / int_val / enc_vint of host/vcfio.c.  For job j with k = keys[j].site,
+ * nn = d_site[k].nals_new and map = d_site[k].als_map, called sample s reads input column c = col ? col[s] : s:
+ *     token    the column is cut at ':'; token idx is the key's text; a column with fewer than idx + 1 tokens (a whole-column '.'
+ *              included) has the token '.'
+ *     values   the token is cut at ',': commas + 1 values; '.' is `missing`, [+-]?[0-9]+ inside int32 its value (leading zeros allowed;
+ *              the decimal text of the two int32 sentinels is stored as it stands and neither cuts nor shortens the vector)
+ *     remap    when flags & 1 and nn != nals and the token was present (idx < the column's tokens) and holds exactly nals values:
+ *              [v[0]] when nn == 1, else nn values `missing` with out[map[i]] = v[i] for every i < nals with map[i] >= 0.  Every other
+ *              vector stays as it is
+ *     width    the longest output vector over the called samples; shorter ones are padded with `end of vector`
+ *     type     as bcfgpu_call_remap_bcf chooses it, over the output values that are no sentinel: int8 for -120 .. 127, int16 for
+ *              -32760 .. 32767, else int32; an all-sentinel key is int8; a value on a dropped allele does not count
+ *     block    as bcfgpu_call_remap_bcf: the typed key id, the descriptor (width >= 15: the long form), the values sample-major
+ *     status   HOST [n_keys], out.  0: the block was made, or the site has no record (zero length).  1: a value of token idx of a called
+ *              sample's column is neither '.' nor [+-]?[0-9]+ inside int32 (an empty value counts; every value of the token is checked,
+ *              whether or not the remap keeps it).  2: the output width passes BCFGPU_BCF_KEY_MAX_WIDTH.  A flagged job has zero length:
+ *              its caller makes that key on the host, which keeps the output equal to the text route's where strtol would accept `12x`,
+ *              `+ 5` or a number past int32.  The columns of input samples that are not called are not examined
+ *   keys     HOST [n_keys], in the order of the blocks, their sites non-decreasing
+ *   run      HOST [n_sites]: off and len as for bcfgpu_call_decode_vcf (the tab in front of input sample 0's column, the bytes from there
+ *            to the end of the last column); idx is not read.  Every run's bounds are checked; only the runs of sites that have a job
+ *            with a record are indexed and read
+ *   d_text, n_text_bytes, n_smpl_in, col   as for bcfgpu_call_decode_vcf
+ *   d_site   DEVICE [n_sites]: the site records of bcfgpu_mcall (nals_new and als_map are read)
+ *   d_emit   DEVICE [n_sites], 0 = the site has no record: its keys' blocks have zero length; NULL = every site has one
+ *   d_buf    DEVICE, cap_bytes: the blocks back to back in the order of keys[]
+ *   d_off    DEVICE [n_keys + 1], 8-byte aligned: d_off[j] = the start of block j, d_off[n_keys] = the size of all.  Set whether or not
+ *            the blocks fit
+ *   n_bytes  HOST, out: the size of all blocks
+ * When the blocks do not fit cap_bytes nothing is written to d_buf, *n_bytes is the size needed and the call returns BCFGPU_E_RANGE
+ * (cap_bytes = 0 asks for the size); status is filled by the size pass, so it is valid after either call.  BCFGPU_E_ARG, checked on the
+ * host before anything runs: NULL pointers, sites that decrease, a site outside [0, n_sites), a negative key id, idx outside
+ * 0 .. BCFGPU_VCF_REWRITE_MAX_KEYS-1, nals outside 1 .. 5 with flags & 1, non-zero reserved, a col entry outside [0, n_smpl_in), more
+ * called samples than input samples without a map; and -- found by the indexing pass of bcfgpu_call_decode_vcf before anything is
+ * written -- an indexed run whose first byte is no tab or whose tab count is not n_smpl_in.  BCFGPU_E_RANGE when off + len passes
+ * n_text_bytes or len passes 1 GiB.  No sample's column is bounded by the LDS stage: a column longer than it is read from global memory by
+ * its own lane.  The columns' offsets are a workspace bounded as bcfgpu_call_decode_vcf's: the kernels run over chunks of that many
+ * sites.  n_keys == 0 is valid.  Runs on the context's stream and synchronises it. */
+typedef struct {            /* one integer pass-through key of one record; 32 bytes */
+    int32_t site;           /* index into run / d_site / d_emit */
+    int32_t key_id;         /* the key's index in the writer's header dictionary */
+    int32_t idx;            /* the key's place among the input record's FORMAT keys, 0 .. BCFGPU_VCF_REWRITE_MAX_KEYS-1 */
+    int32_t nals;           /* alleles of the input record */
+    int32_t flags;          /* bit 0: the header declares the key Number=R */
+    int32_t reserved[3];    /* 0 */
+} bcfgpu_vcf_key;
+int  bcfgpu_call_parse_keys_vcf(bcfgpu_ctx *ctx, int32_t n_keys, const bcfgpu_vcf_key *keys /* HOST, sites non-decreasing */,
+                                int32_t n_sites, const bcfgpu_vcf_vec *run /* HOST [n_sites]: off, len as for bcfgpu_call_decode_vcf; idx not read */,
+                                int32_t n_smpl_in, const void *d_text, uint64_t n_text_bytes, const int32_t *col,
+                                const bcfgpu_call_site *d_site, const uint8_t *d_emit,
+                                void *d_buf, uint64_t cap_bytes, uint64_t *d_off /* DEVICE [n_keys+1] */, uint64_t *n_bytes,
+                                uint8_t *status /* HOST [n_keys], out */);
 
 /* One communicator over the contexts of a node, rank i = ctxs[i] (RCCL ncclCommInitAll; every context on its own device;
  * librccl is loaded at this call, a single context needs none). */

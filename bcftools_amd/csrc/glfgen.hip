@@ -7,7 +7,9 @@
 //
 //   phase A, one lane per READ (read-parallel, every lane busy whatever the depths of the cells):
 //     the span is read straight from HBM, four consecutive reads per lane and trip (one 16-byte load of `rd`, one
-//     4-byte load of `epos`), each input byte exactly once.  Per read: the filters (bam2bcf.c:173-194), the quality
+//     4-byte load of `epos`), each input byte exactly once.  A wavefront's trip that lies whole inside its site segment
+//     runs without byte masks, fetch guards and per-read key stores; the ragged ends run the general body.
+//     Per read: the filters (bam2bcf.c:173-194), the quality
 //     arithmetic (:196-203), and everything that only feeds SITE totals -- the I16 sums anno[4..15] (:221-226),
 //     ori_depth, mq0 and the bias-test histograms (:228-252) -- which therefore never needs to know the read's cell:
 //     per-lane partial sums, one reduction per workgroup and site.  What the cell needs of the read is 12 bits, left in
@@ -318,6 +320,17 @@ __device__ __forceinline__ uint32_t nonzero80(uint32_t x) { return (((x & 0x7f7f
 __device__ __forceinline__ uint32_t bytes_of80(uint32_t m) { return m | (m - (m >> 7)); }
 // byte u of x (u a constant)
 __device__ __forceinline__ uint32_t byte_at(uint32_t x, int u) { return (x >> (8 * u)) & 0xffu; }
+// A global load from a wave-uniform address plus a lane's byte offset: the address stays in scalar registers.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <typename T> struct GlobalWord { typedef T type; };
+template <> struct GlobalWord<u32x4> { typedef uint4 type; };
+template <typename T> __device__ __forceinline__ typename GlobalWord<T>::type load_global(const void *base, uint32_t off)
+{
+    typedef const __attribute__((address_space(1))) char *gbytes;
+    typedef const __attribute__((address_space(1))) T *gptr;
+    const T v = *(gptr)((gbytes)base + off);
+    if constexpr (sizeof(T) == 16) return make_uint4(v.x, v.y, v.z, v.w); else return v;
+}
 
 // DEEP = false: the tile, 256 consecutive cells per workgroup.  A cell with more pileup entries than the LDS key window holds is
 // not worked on here: it is listed (P.deep_*), and the launch that follows (DEEP = true) gives each listed cell a workgroup
@@ -434,7 +447,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
         // ================= phase A: one lane per read =================
         for (int sg = site0; sg <= site_last; ++sg) {            // uniform: the site segments of the workgroup's span
             const long c_lo = max(cell0, (long)sg * S), c_hi = min(cell_end, (long)(sg + 1) * S);
-            const uint32_t rb = max(p_off[c_lo], base), re = min(p_off[c_hi], rlim);
+            // (the same in every lane, but formed by the vector unit: handed to the scalar one, which chooses the trips below)
+            const uint32_t rb = (uint32_t)__builtin_amdgcn_readfirstlane((int)max(p_off[c_lo], base));
+            const uint32_t re = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(p_off[c_hi], rlim));
             if (rb >= re) continue;
             const int ref_base = INDEL ? -1 : (int)P.ref16[sg];
             const uint32_t ref4 = INDEL ? 4u : (uint32_t)nt16_int(ref_base);
@@ -456,7 +471,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
 
             // Four consecutive reads of the lane, `vm4`: 0xff in the bytes of the reads inside [rb, re).  Per-lane control
             // flow only: any lane may run this on its own.
-            auto quad = [&](const uint4 &w4, const uint4 &a4, uint32_t e4, uint32_t vm4, uint32_t &k01, uint32_t &k23) {
+            auto quad = [&](const uint4 &w4, const uint4 &a4, uint32_t e4, uint32_t vm4, uint32_t &k01, uint32_t &k23) __attribute__((always_inline)) {
                 // the rd words as byte planes: baseQ, mapQ, flags (nt16 | rev << 4 | sclip << 5 | DEL << 6 | SKIP << 7), min_dist
                 const uint32_t t0 = perm(w4.y, w4.x, 0x05010400u), t1 = perm(w4.y, w4.x, 0x07030602u);
                 const uint32_t t2 = perm(w4.w, w4.z, 0x05010400u), t3 = perm(w4.w, w4.z, 0x07030602u);
@@ -557,6 +572,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
             };
 
             const uint32_t g0 = rb & ~3u;
+            const uint32_t key0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)abase);   // (for the scalar unit, like rb and re)
             uint4 w4n = make_uint4(0, 0, 0, 0), a4n = make_uint4(0, 0, 0, 0);
             uint32_t e4n = 0;
             auto fetch = [&](uint32_t i4) {
@@ -576,24 +592,59 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
                     w4n = make_uint4(t4[0], t4[1], t4[2], t4[3]); a4n = make_uint4(x4[0], x4[1], x4[2], x4[3]);
                 }
             };
-            fetch(g0 + 4u * tid);
-            for (uint32_t i4 = g0 + 4u * tid; i4 < re; i4 += 4u * WG) {
+            // A trip: the wavefront's 256 consecutive reads from `first` on, the lane's four from first + l4; the next trip
+            // of the wavefront is 4 * WG reads on.  `first` and everything the trips are chosen by is wave-uniform.
+            uint32_t l4 = 4u * (uint32_t)(tid & 63);
+            uint32_t first = g0 + 256u * (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
+            // A FULL trip has all its 256 reads inside [rb, re), and the loads for the trip behind it (reads past `re`, may be)
+            // lie inside the tile's arrays: full_lo <= first <= full_hi.  It needs no byte mask, stores its keys with one
+            // 8-byte store a lane, and loads without a guard, from a scalar base and a lane offset that stays the same.
+            const bool fulls = re >= 1u * WG && n_reads_tot >= 5u * WG;
+            const uint32_t full_lo = fulls ? rb : 0xffffffffu, full_hi = fulls ? min(re - 1u * WG, n_reads_tot - 5u * WG) : 0u;
+            auto fetch_full = [&](uint32_t at, uint4 &w, uint4 &a, uint32_t &e) {
+                // (the lane offset as a value of this trip: widened to 64 bits once, outside the loop, it is no longer seen to
+                // be a 32-bit offset from a scalar base, and the address is formed by the lane)
+                asm volatile("" : "+v"(l4)); uint32_t l16 = 4u * l4;
+                w = load_global<u32x4>(p_rd + at, l16);
+                if (want_epos) e = load_global<uint32_t>(p_epos + at, l4);
+                if (INDEL) a = load_global<u32x4>(p_aux + at, l16);
+            };
+            fetch(first + l4);
+            while (first < re) {
+                if (first >= full_lo && first <= full_hi) {
+                    do {
+                        uint16_t *kq = s_key + (first - key0);
+                        const uint4 w4 = w4n, a4 = a4n;
+                        const uint32_t e4 = e4n;
+                        uint32_t k01, k23;
+                        fetch_full(first + 4u * WG, w4n, a4n, e4n);
+                        quad(w4, a4, e4, 0xffffffffu, k01, k23);
+                        *reinterpret_cast<uint2*>(kq + l4) = make_uint2(k01, k23);
+                        first += 4u * WG;
+                    } while (first <= full_hi);
+                    continue;
+                }
+                // every other trip: a ragged end of the segment, the tile's last reads
+                const uint32_t i4 = first + l4;
                 const uint4 w4 = w4n, a4 = a4n;
                 const uint32_t e4 = e4n;
                 fetch(i4 + 4u * WG);                             // the next trip's loads fly while this one is worked on
-                // the reads of [i4, i4 + 4) inside [rb, re): bytes lo .. hi-1 (i4 >= g0 = rb & ~3, so lo <= 3)
-                const uint32_t lo = rb > i4 ? rb - i4 : 0u, hi = min(re - i4, 4u);
-                const uint32_t vm4 = (0xffffffffu << (8 * lo)) & (hi == 4u ? 0xffffffffu : ~(0xffffffffu << (8 * hi)));
-                uint32_t k01, k23;
-                quad(w4, a4, e4, vm4, k01, k23);
-                const uint32_t ko = i4 - abase;
-                if (vm4 == 0xffffffffu) {                        // the four reads inside the segment: one 8-byte LDS store
-                    *reinterpret_cast<uint2*>(s_key + ko) = make_uint2(k01, k23);
-                } else {                                         // a lane at a ragged end of the segment
-                    const uint32_t kv[4] = { k01 & 0xffffu, k01 >> 16, k23 & 0xffffu, k23 >> 16 };
-                    #pragma unroll
-                    for (int u = 0; u < 4; ++u) if ((vm4 >> (8 * u)) & 1) s_key[ko + u] = (uint16_t)kv[u];
+                if (i4 < re) {
+                    // the reads of [i4, i4 + 4) inside [rb, re): bytes lo .. hi-1 (i4 >= g0 = rb & ~3, so lo <= 3)
+                    const uint32_t lo = rb > i4 ? rb - i4 : 0u, hi = min(re - i4, 4u);
+                    const uint32_t vm4 = (0xffffffffu << (8 * lo)) & (hi == 4u ? 0xffffffffu : ~(0xffffffffu << (8 * hi)));
+                    uint32_t k01, k23;
+                    quad(w4, a4, e4, vm4, k01, k23);
+                    uint16_t *kq = s_key + (first - key0) + l4;    // the lane's four keys
+                    if (vm4 == 0xffffffffu) {                    // the four reads inside the segment: one 8-byte LDS store
+                        *reinterpret_cast<uint2*>(kq) = make_uint2(k01, k23);
+                    } else {                                     // a lane at a ragged end of the segment
+                        const uint32_t kv[4] = { k01 & 0xffffu, k01 >> 16, k23 & 0xffffu, k23 >> 16 };
+                        #pragma unroll
+                        for (int u = 0; u < 4; ++u) if ((vm4 >> (8 * u)) & 1) kq[u] = (uint16_t)kv[u];
+                    }
                 }
+                first += 4u * WG;
             }
             // ---- the segment's site totals ----
             // LDS mode: every lane adds its partial sums and counts to its own column of the slot's [value][pcol] table (no
@@ -926,7 +977,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(GLF_WAVES, G
     // ---- flush the workgroup's histograms and site totals ----
     if (LDS_HIST) {
         __syncthreads();
-        const int nslot = min(P.hist_slots, P.n_sites - site0);
+        int nsite = P.n_sites;                                   // (formed here: the same count from the kernel's top is one more value
+        asm volatile("" : "+s"(nsite));                          // alive through every round)
+        const int nslot = min(P.hist_slots, nsite - site0);
         if (PACKED) flush_packed(false);
         else {                                                   // a deep cell's site: plain counters in the global layout
             int *g = P.hist + (long)site0 * H_SIZE;

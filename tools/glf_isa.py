@@ -7,9 +7,11 @@ Build the listing with the Makefile's options for glfgen.hip, e.g. in a scratch 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off $(make -s print-flags-glfgen) --save-temps -c glfgen.hip
 (or --cuda-device-only -S -o <listing>).
 
-Phase A's loop is taken from LLVM's loop annotations in the listing ("; =>This Inner Loop Header", "in Loop: Header=BBx",
-"Parent Loop BBx"): the innermost loop whose blocks (nested loops included) hold the byte-plane sums (v_dot4_u32_u8 /
-v_dot2_u32_u16) and no double-precision instruction.  Printed per block of that loop, in listing order: the vector ALU
+Phase A's loops are taken from LLVM's loop annotations in the listing ("; =>This Inner Loop Header", "in Loop: Header=BBx",
+"Parent Loop BBx"): the loops whose blocks (nested loops included) hold the byte-plane sums (v_dot4_u32_u8 /
+v_dot2_u32_u16) and no double-precision instruction.  The smallest one that stores single keys (a ragged end of a segment) is
+the general loop; the smallest one that does not is the full-trip loop, which lies inside it and is reported first, with its
+trips a pass (a key store a trip) and the instructions a full trip must not need.  Printed per block of that loop, in listing order: the vector ALU
 instructions (v_*, which is what SQ_INSTS_VALU counts), v_readlane / v_writelane among them, LDS and global/flat memory
 instructions, and the block's IR name.  The totals count every block once (a static count: rare blocks such as the
 tile-tail fetch or the diff-read sums are included); reads per trip: 4 per lane.
@@ -117,20 +119,40 @@ def main():
         if not cand:
             print("  phase-A loop not found")
             continue
-        _, loop, mem = min(cand, key=lambda c: c[0])
-        tot = dict(v=0, rl=0, wl=0, ds=0, gl=0)
-        print("  phase-A loop: header %s, %d blocks" % (loop, len(mem)))
-        for b in mem:
-            ins = b["ins"]
-            v = [i for i in ins if i.startswith("v_")]
-            c = dict(v=len(v), rl=sum(i.startswith("v_readlane") for i in v), wl=sum(i.startswith("v_writelane") for i in v),
-                     ds=sum(i.startswith("ds_") for i in ins), gl=sum(i.startswith(("global_", "buffer_", "flat_")) for i in ins))
-            for key in tot:
-                tot[key] += c[key]
-            print("    %-10s v_*=%3d readlane=%2d writelane=%2d ds=%2d mem=%2d  %s" % (
-                b["lab"], c["v"], c["rl"], c["wl"], c["ds"], c["gl"], b["name"][:60]))
-        print("  loop total (static, every block once): v_*=%d readlane=%d writelane=%d ds=%d mem=%d" % (
-            tot["v"], tot["rl"], tot["wl"], tot["ds"], tot["gl"]))
+        # the general loop stores single keys at a ragged end (ds_write_b16; the DEEP forms keep their keys in global memory:
+        # global_store_short); the full-trip loop inside it stores whole quads only, and its blocks are not counted again
+        ragged = lambda c: any(i.startswith(("ds_write_b16", "global_store_short", "flat_store_short")) for b in c[2] for i in b["ins"])
+        full = min([c for c in cand if not ragged(c)], key=lambda c: c[0], default=None)
+        gen = min([c for c in cand if ragged(c)], key=lambda c: c[0], default=None)
+        _, loop, mem = gen or full
+        inner = {id(b) for b in full[2]} if full and gen else set()
+        def report(tag, loop, mem, trips):
+            tot = dict(v=0, rl=0, wl=0, ds=0, gl=0)
+            print("  %s: header %s, %d blocks" % (tag, loop, len(mem)))
+            for b in mem:
+                ins = b["ins"]
+                v = [i for i in ins if i.startswith("v_")]
+                c = dict(v=len(v), rl=sum(i.startswith("v_readlane") for i in v), wl=sum(i.startswith("v_writelane") for i in v),
+                         ds=sum(i.startswith("ds_") for i in ins), gl=sum(i.startswith(("global_", "buffer_", "flat_")) for i in ins))
+                for key in tot:
+                    tot[key] += c[key]
+                print("    %-10s v_*=%3d readlane=%2d writelane=%2d ds=%2d mem=%2d  %s" % (
+                    b["lab"], c["v"], c["rl"], c["wl"], c["ds"], c["gl"], b["name"][:60]))
+            print("  loop total (static, every block once): v_*=%d readlane=%d writelane=%d ds=%d mem=%d" % (
+                tot["v"], tot["rl"], tot["wl"], tot["ds"], tot["gl"]))
+            return tot
+        if full and gen:
+            fmem = full[2]
+            fins = [i for b in fmem for i in b["ins"]]
+            # trips a pass: a trip stores its keys once (8 bytes a lane)
+            trips = max(1, cnt(fins, "ds_write_b64", "global_store_dwordx2", "flat_store_dwordx2"))
+            tot = report("phase-A full-trip loop", full[1], fmem, trips)
+            movs = sum(bool(re.match(r"v_mov_b32\S*\s+v\d+, v\d+$", i)) for i in fins)
+            print("  full trips a pass: %d, v_* a trip: %.1f; register copies (v_mov_b32 v, v)=%d flat_load=%d v_lshl_add_u64=%d ds_write_b16=%d" % (
+                trips, tot["v"] / trips, movs, cnt(fins, "flat_load"), cnt(fins, "v_lshl_add_u64"), cnt(fins, "ds_write_b16")))
+            report("phase-A general loop (without the full-trip loop's blocks)", loop, [b for b in mem if id(b) not in inner], 1)
+        else:
+            report("phase-A loop", loop, mem, 1)
         phase_b(bl, parent, {id(b) for b in mem})
         straight_line(bl, parent, loop)
 

@@ -184,6 +184,19 @@ class VcfVec(C.Structure):
 VCF_VEC = [("off", "<u8"), ("len", "<u4"), ("idx", "<i4")]
 VCFDEC_START_BYTES = 4 << 20        # BCFGPU_VCFDEC_START_BYTES: the bound on the workspace of bcfgpu_call_decode_vcf's column offsets
 
+# bcfgpu_call_constrain: the modes (BCFGPU_CALS_NUMBER_*) and the bound on n_in / n_out
+CALS_NUMBER_G, CALS_NUMBER_R = 0, 1
+CALS_MAX_PLANES = 1 << 20
+
+
+class CalsSite(C.Structure):
+    """bcfgpu_cals_site: one record of bcfgpu_call_constrain -- the alleles of the constrained record, the unseen allele before the
+    rewrite, whether the record changes, new allele -> original allele (32 bytes)."""
+    _fields_ = [("n_new", C.c_int32), ("unseen", C.c_int32), ("changed", C.c_int32), ("amap", C.c_int32 * 5)]
+
+
+CALS_SITE = [("n_new", "<i4"), ("unseen", "<i4"), ("changed", "<i4"), ("amap", "<i4", (5,))]
+
 BCF_KEY_MAX_WIDTH = 255
 
 
@@ -310,6 +323,7 @@ PROTOTYPES = {
                                          C.c_int32, C.c_void_p]),
     "bcfgpu_call_decode_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(VcfVec), C.POINTER(C.c_int32),
                                          C.c_int32, C.c_void_p]),
+    "bcfgpu_call_constrain": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CalsSite), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "bcfgpu_call_remap_bcf": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(BcfKey), C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bcfgpu_call_encode_vcf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CallOut), C.c_int32, C.POINTER(VcfField), C.c_int32, C.c_void_p,

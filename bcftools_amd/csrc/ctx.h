@@ -105,13 +105,15 @@ enum WsSlot : int {
     // bcfgpu_call_decode_vcf's), the error word
     WS_COMPACT_VCFKEY_JOBS = 187, WS_COMPACT_VCFKEY_COL = 188, WS_COMPACT_VCFKEY_WORD = 189, WS_COMPACT_VCFKEY_STATUS = 190,
     WS_COMPACT_VCFKEY_RUNS = 191, WS_COMPACT_VCFKEY_START = 192, WS_COMPACT_VCFKEY_ERR = 193,
+    // bcfgpu_call_constrain (calsmap.hip): the uploaded copy of the sites' descriptors
+    WS_COMPACT_CALS_SITE = 194,
 
     // bcfgpu_errmod_plan[_visit].  Kept: DrawState::bits, read by the next bcfgpu_mpileup / bcfgpu_pipeline on each tile
     WS_DRAW_BITS_SNP = 136, WS_DRAW_BITS_INDEL = 137,
     //   scratch for one call
     WS_DRAW_VISIT = 132, WS_DRAW_ENT = 138, WS_DRAW_CTR = 139, WS_DRAW_COLS = 140, WS_DRAW_IDX_OFF = 141, WS_DRAW_IDX = 142,
 
-    WS_COUNT = WS_COMPACT_VCFKEY_ERR + 1      // one past the highest slot
+    WS_COUNT = WS_COMPACT_CALS_SITE + 1     // one past the highest slot
 };
 
 // the kept slots (see above): what each holds stays valid from the call that writes it until a call include/bcfgpu.h names

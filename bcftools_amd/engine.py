@@ -468,6 +468,24 @@ class Context:
             self.release(bufs)
         return out
 
+    def constrain_planes(self, planes, site, n_out, mode=abi.CALS_NUMBER_G):
+        """bcfgpu_call_constrain: the planes of `call -C alleles` records in their targets' alleles.  planes: np.int32
+        [n_sites, n_in, n_smpl] as decode_bcf / decode_vcf return them, uploaded here; site: an array of abi.CALS_SITE; mode:
+        abi.CALS_NUMBER_G (PL) or abi.CALS_NUMBER_R (AD / QS).  Returns np.int32 [n_sites, n_out, n_smpl]."""
+        planes = np.ascontiguousarray(planes, np.int32)
+        d = np.ascontiguousarray(site, dtype=abi.CALS_SITE)
+        n, n_in, S = planes.shape
+        assert len(d) == n and S == self.cfg.n_smpl
+        out = np.zeros((n, n_out, S), np.int32)
+        bufs = [self.to_device(planes.reshape(-1).view(np.uint8)), self.buf(out.nbytes)]
+        try:
+            check(self.L.bcfgpu_call_constrain(self.h, mode, n, d.ctypes.data_as(C.POINTER(abi.CalsSite)), n_in, bufs[0].ptr, n_out, bufs[1].ptr))
+            if out.nbytes:
+                bufs[1].download(out)
+        finally:
+            self.release(bufs)
+        return out
+
     def remap_call_bcf(self, indiv, keys, n_smpl_in, site, col=None, emit=None, cap_bytes=None):
         """bcfgpu_call_remap_bcf: the integer pass-through FORMAT keys of call records as BCF2 key blocks.  indiv: the input records'
         per-sample blocks (bytes or np.uint8) and site: the call's site records (a host array of abi.CallSite layout), both uploaded

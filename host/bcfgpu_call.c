@@ -2,7 +2,7 @@
  *  include/bcfgpu.h: the record loop of main_vcfcall (vcfcall.c:1089-1148) with mcall() on the device.
  *
  *      bcfgpu_call [-v] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]]
- *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-parse] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] <in.vcf>
+ *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-parse] [--device-alleles] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] <in.vcf>
  *          -S: the samples to keep, in that order: NAME [PLOIDY|SEX] per line, or a PED file (vcfcall.c:202-344)
  *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c)
  *          -G: sample groups with their own allele frequencies, '-' = every sample alone, or NAME GROUP lines
@@ -11,14 +11,24 @@
  *          -a: FORMAT/GQ and FORMAT/GP on called variant records (mcall.c:1618-1623)
  *          --device-input: BCF input is not turned into text and back: the records' per-sample blocks go to the device as the file
  *              holds them and bcfgpu_call_decode_bcf makes the PL (and, with -G, AD / QS) planes there; the sample columns become
- *              text only for the records that are written.  Takes effect on BCF input without -C alleles and without -g (both read
- *              the samples' values on the host); in any other run the option does nothing.  The same output either way.
+ *              text only for the records that are written.  Takes effect on BCF input without -C alleles (but see --device-alleles) and
+ *              without -g (both read the samples' values on the host); in any other run the option does nothing.  The same output either way.
  *          --device-parse: the same for VCF text input (plain, bgzipped or on a pipe): a line is split at its first nine tabs only, the
  *              rest of it -- the sample columns, from their tab on -- goes to the device as text and bcfgpu_call_decode_vcf parses the PL
  *              (and, with -G, AD / QS) planes there; a record's columns are split on the host only when the record is written.  Takes
- *              effect on text input without -C alleles and without -g; in any other run the option does nothing, and it may stand
+ *              effect on text input without -C alleles (but see --device-alleles) and without -g; in any other run the option does nothing, and it may stand
  *              beside --device-input (each acts on its own kind of input).  Stricter than the host's atoi: a PL / AD / QS value that is
  *              not '.' or [+-]?[0-9]+ inside int32 is "malformed VCF".  The same output either way.
+ *          --device-alleles: with -C alleles -T targets, where --device-input (BCF in) or --device-parse (text in) is given and would act
+ *              but for -C alleles: that option takes effect.  The host keeps the head of the rewrite -- the pairing with a target, amap,
+ *              REF / ALT, INFO/QS, the -i lines -- and runs it on the record's first nine columns; the samples' bytes or text go to the
+ *              device untouched, the decoders make planes of the input records' shape there, and bcfgpu_call_constrain gathers them into
+ *              the planes mcall() reads (PL through pl_map with the unseen allele standing in; with -G the tag's planes through amap).
+ *              A written record's sample text, where the host still forms it, comes from the input's own bytes or text: PL is printed from
+ *              the planes, the other Number=R keys of a changed record go through amap first, then als_map.  --device-records,
+ *              --device-keys and --device-text act as without -C alleles, but a Number=R key other than PL of a changed record is the
+ *              host's (--device-keys: no job; --device-text: the record's columns are formed on the host): those kernels apply als_map to
+ *              the input's own vector.  In any other run the option does nothing.  The same output either way.
  *          --device-records: with -O u|b the records' GT, PL and GQ do not come down as planes to be printed and parsed back: after the
  *              calls bcfgpu_call_encode_bcf turns them into BCF2 key blocks in HBM, for the records that are written only, and the host
  *              downloads the site records, the bytes and one offset per record and key.  A record is then its head and
@@ -59,7 +69,8 @@
  *          --timing: lines on stderr: the seconds (reading records, building the planes on the host, uploads and device stages,
  *              writing records), how many records' planes were decoded on the device, and how many records' FORMAT blocks were
  *              encoded there; with --device-parse given, also how many records' planes were parsed on the device; with --device-keys given, also how many pass-through key blocks were made on the device and on the host;
- *              with --device-text given, also how many records' sample columns were formatted on the device and on the host
+ *              with --device-text given, also how many records' sample columns were formatted on the device and on the host;
+ *              with --device-alleles given, also how many records' planes were constrained on the device and how many were taken as they were
  *
  *  Host: VCF text in, what mcall() reads from a record (alleles, FORMAT/PL, INFO/QS, INFO/I16) packed into the planes of
  *  bcfgpu_call_in, one bcfgpu_mcall over all records, then what mcall.c:1627-1681 does to the record: alleles trimmed with
@@ -83,8 +94,10 @@
  * with --device-parse: line = the first nine columns, the sample columns' text (from the ninth tab on) = ilen bytes at ioff */
 typedef struct { char *line; char **fld; int nfld; char **als; int nals, unseen, pl_idx, ad_idx; uint8_t *ploidy;
                  size_t ioff, ilen; int n_fmt, nkeys; vio_indiv_key *keys;
-                 int *kjob, nkjob; } rec_t;     /* --device-keys, a written record: key i's job of bcfgpu_call_remap_bcf (text input: of
+                 int *kjob, nkjob;              /* --device-keys, a written record: key i's job of bcfgpu_call_remap_bcf (text input: of
                                                  * bcfgpu_call_parse_keys_vcf), or -1 (the host's); nkjob entries, one a FORMAT key */
+                 int nori, unseen_in, changed, amap[BCFGPU_MAX_ALLELES]; } rec_t;   /* --device-alleles: the input record's allele count and unseen
+                                                 * allele, whether -C alleles changes it, new allele -> original allele (bcfgpu_cals_site) */
 
 typedef struct { char chrom[256]; int from, to, ploidy; char sex[64]; } preg_t;
 
@@ -228,28 +241,61 @@ static void flush_region(const char *chrom, long beg0, long end0)
 
 typedef struct { char *p; size_t o, cap; } obuf_t;              /* the line constrain_line writes */
 static void outf(obuf_t *b, const char *fmt, ...) { va_list ap; va_start(ap, fmt); b->o += (size_t)vsnprintf(b->p + b->o, b->cap - b->o, fmt, ap); va_end(ap); }
-/* The record `line` (S_in sample columns) in the alleles of target t: a new malloc'ed line, the same line when nothing
- * changes, or NULL when mcall() would return -2 (the site is skipped).  *unseen: in/out. */
-static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *unseen_io)
+/* -C alleles, the head of the rewrite: what needs the record's first nine columns and the target alone (mcall.c:1271-1331, :1372-1379) --
+ * amap (new allele -> original allele), the new alleles, whether anything changes */
+typedef struct { int nori, nals, unseen, changed, amap[8]; const char *als[8]; char *unseen_al; } chead_t;
+/* f: the record's columns, alts: its ALT alleles; 0, or -1 when mcall() would return -2 (the site is skipped, mcall.c:1294-1303) */
+static int constrain_head(char **f, char **alts, int nalt, const tgt_t *t, int unseen, chead_t *h)
 {
     if (t->nals > 5) DIE("Maximum accepted number of alleles is 5\n");
-    char *c = strdup(line); int nf; char **f = split(c, '\t', &nf);
-    int nalt = 0; char *altc = strdup(f[4]), **alts = split(altc, ',', &nalt);
-    if (!strcmp(f[4], ".")) nalt = 0;
-    const int nori = 1 + nalt, unseen = *unseen_io;
     vcmp_t vc;
     if (vcmp_set_ref(&vc, f[3], t->als[0]) < 0) DIE("The reference alleles are not compatible at %s:%s\n", f[0], f[1]);
-    int amap[8], nals = 1, has_new = 0; const char *als[8];
-    amap[0] = 0; als[0] = t->als[0];
+    int nals = 1, has_new = 0;
+    h->nori = 1 + nalt; h->unseen = unseen; h->unseen_al = NULL;
+    h->amap[0] = 0; h->als[0] = t->als[0];
     for (int i = 1; i < t->nals; ++i) {
         const int j = vcmp_find_allele(&vc, alts, nalt, t->als[i]);
-        if (j + 1 == unseen) { free(alts); free(altc); free(f); free(c); return NULL; }   /* mcall.c:1294-1303 */
-        if (j >= 0) amap[nals] = j + 1; else { amap[nals] = unseen >= 0 ? unseen : nori - 1; has_new = 1; }
-        als[nals++] = t->als[i];
+        if (j + 1 == unseen) return -1;                                                   /* mcall.c:1294-1303 */
+        if (j >= 0) h->amap[nals] = j + 1; else { h->amap[nals] = unseen >= 0 ? unseen : h->nori - 1; has_new = 1; }
+        h->als[nals++] = t->als[i];
     }
-    char *unseen_al = NULL;
-    if (unseen) { amap[nals] = unseen; unseen_al = strdup(unseen == 0 ? f[3] : alts[unseen - 1]); als[nals++] = unseen_al; }
-    if (!has_new && nals == nori) { free(unseen_al); free(alts); free(altc); free(f); free(c); return strdup(line); }
+    if (unseen) { h->amap[nals] = unseen; h->unseen_al = strdup(unseen == 0 ? f[3] : alts[unseen - 1]); h->als[nals++] = h->unseen_al; }
+    h->nals = nals; h->changed = has_new || nals != h->nori;
+    return 0;
+}
+/* the first nine columns of a changed record: REF and ALT are the target's, INFO/QS follows the alleles (absent alleles: 0) */
+static void constrained_columns(obuf_t *ob, char **f, const chead_t *h)
+{
+    const int nals = h->nals;
+    outf(ob, "%s\t%s\t%s\t%s\t", f[0], f[1], f[2], h->als[0]);
+    if (nals == 1) outf(ob, "."); else for (int i = 1; i < nals; ++i) outf(ob, "%s%s", i > 1 ? "," : "", h->als[i]);
+    outf(ob, "\t%s\t%s\t", f[5], f[6]);
+    int ni; char *info = strdup(f[7]), **iv = split(info, ';', &ni);
+    for (int i = 0; i < ni; ++i) {
+        if (i) outf(ob, ";");
+        if (!strncmp(iv[i], "QS=", 3)) {
+            int nq; char *qc = strdup(iv[i] + 3), **qv = split(qc, ',', &nq);
+            outf(ob, "QS=");
+            for (int k = 0; k < nals; ++k) outf(ob, "%s%.9g", k ? "," : "", h->amap[k] < nq ? (double)(float)atof(qv[h->amap[k]]) : 0.);
+            free(qv); free(qc);
+        } else outf(ob, "%s", iv[i]);
+    }
+    free(iv); free(info);
+    outf(ob, "\t%s", f[8]);
+}
+/* a Number=R token in the new alleles: new[k] = old[amap[k]], '.' where the token has no such value; a '.' token is left alone */
+static void constrained_numberR(obuf_t *ob, const char *tok, const int *amap, int nals)
+{
+    if (!strcmp(tok, ".")) { outf(ob, "."); return; }
+    int nv; char *vc2 = strdup(tok), **vv = split(vc2, ',', &nv);
+    for (int a = 0; a < nals; ++a) outf(ob, "%s%s", a ? "," : "", amap[a] < nv ? vv[amap[a]] : ".");
+    free(vv); free(vc2);
+}
+/* the sample columns of a changed record (mcall.c:1332-1371, :1380-1413): PL gathered through pl_map, the unseen allele standing in for
+ * the alleles mpileup did not see; the Number=R keys through amap.  With --device-alleles bcfgpu_call_constrain does this on the planes */
+static void constrained_samples(obuf_t *ob, char **f, const chead_t *h, int S_in)
+{
+    const int nals = h->nals, unseen = h->unseen; const int *amap = h->amap;
     int pl_map[64], npl = 0;
     for (int i = 0; i < nals; ++i) for (int j = 0; j <= i; ++j) pl_map[npl++] = gt_index(amap[i], amap[j]);
     /* FORMAT keys */
@@ -264,28 +310,9 @@ static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *uns
         sc[s] = strdup(f[9 + s]); sv[s] = split(sc[s], ':', &snv[s]);
         if (ipl < snv[s]) { int w = 1; for (const char *q = sv[s][ipl]; *q; ++q) w += *q == ','; if (w > width) width = w; }
     }
-    const size_t cap = strlen(line) * 4 + 4096 + (size_t)S_in * (size_t)npl * 12;
-    obuf_t ob = { malloc(cap), 0, cap };
-    outf(&ob, "%s\t%s\t%s\t%s\t", f[0], f[1], f[2], als[0]);
-    if (nals == 1) outf(&ob, "."); else for (int i = 1; i < nals; ++i) outf(&ob, "%s%s", i > 1 ? "," : "", als[i]);
-    outf(&ob, "\t%s\t%s\t", f[5], f[6]);
-    {   /* INFO: QS follows the alleles (absent alleles: 0) */
-        int ni; char *info = strdup(f[7]), **iv = split(info, ';', &ni);
-        for (int i = 0; i < ni; ++i) {
-            if (i) outf(&ob, ";");
-            if (!strncmp(iv[i], "QS=", 3)) {
-                int nq; char *qc = strdup(iv[i] + 3), **qv = split(qc, ',', &nq);
-                outf(&ob, "QS=");
-                for (int k = 0; k < nals; ++k) outf(&ob, "%s%.9g", k ? "," : "", amap[k] < nq ? (double)(float)atof(qv[amap[k]]) : 0.);
-                free(qv); free(qc);
-            } else outf(&ob, "%s", iv[i]);
-        }
-        free(iv); free(info);
-    }
-    outf(&ob, "\t%s", f[8]);
     int32_t *ori = malloc((size_t)width * 4);
     for (int s = 0; s < S_in; ++s) {
-        outf(&ob, "\t");
+        outf(ob, "\t");
         for (int w = 0; w < width; ++w) ori[w] = BCFGPU_INT32_VECTOR_END;
         if (ipl < snv[s]) {
             int np; char *pc = strdup(sv[s][ipl]), **pv = split(pc, ',', &np);
@@ -293,7 +320,7 @@ static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *uns
             free(pv); free(pc);
         } else ori[0] = BCFGPU_INT32_MISSING;
         for (int k = 0; k < nk; ++k) {
-            if (k) outf(&ob, ":");
+            if (k) outf(ob, ":");
             if (k == ipl) {
                 int printed = 0;
                 for (int g = 0; g < npl; ++g) {
@@ -307,21 +334,41 @@ static char *constrain_line(const char *line, const tgt_t *t, int S_in, int *uns
                     }
                     if (g == 0 && v == BCFGPU_INT32_VECTOR_END) v = BCFGPU_INT32_MISSING;
                     if (v == BCFGPU_INT32_VECTOR_END) break;
-                    if (printed++) outf(&ob, ",");
-                    if (v == BCFGPU_INT32_MISSING) outf(&ob, "."); else outf(&ob, "%d", v);
+                    if (printed++) outf(ob, ",");
+                    if (v == BCFGPU_INT32_MISSING) outf(ob, "."); else outf(ob, "%d", v);
                 }
-            } else if (k < snv[s] && is_numberR(fmtR, n_fmtR, keys[k], strlen(keys[k])) && strcmp(sv[s][k], ".")) {
-                int nv; char *vc2 = strdup(sv[s][k]), **vv = split(vc2, ',', &nv);      /* Number=R: new[k] = old[als_map[k]] */
-                for (int a = 0; a < nals; ++a) outf(&ob, "%s%s", a ? "," : "", amap[a] < nv ? vv[amap[a]] : ".");
-                free(vv); free(vc2);
-            } else outf(&ob, "%s", k < snv[s] ? sv[s][k] : ".");
+            } else if (k < snv[s] && is_numberR(fmtR, n_fmtR, keys[k], strlen(keys[k]))) constrained_numberR(ob, sv[s][k], amap, nals);      /* Number=R: new[k] = old[als_map[k]] */
+            else outf(ob, "%s", k < snv[s] ? sv[s][k] : ".");
         }
     }
     free(ori);
     for (int s = 0; s < S_in; ++s) { free(sv[s]); free(sc[s]); }
-    free(sv); free(snv); free(sc); free(keys); free(fmt); free(unseen_al); free(alts); free(altc); free(f); free(c);
-    *unseen_io = unseen ? nals - 1 : unseen;
-    return ob.p;
+    free(sv); free(snv); free(sc); free(keys); free(fmt);
+}
+/* The record `line` (n_smp sample columns) in the alleles of target t: a new malloc'ed line, the same line when nothing changes, or
+ * NULL when mcall() would return -2 (the site is skipped).  *unseen: in/out.  n_smp is the input's sample count, or 0 with
+ * --device-alleles: the line is the first nine columns, the head alone is rewritten, and *kept (when not NULL) takes what the device
+ * needs to constrain the planes (amap, the original allele count, the unseen allele before the rewrite, whether anything changes). */
+static char *constrain_line(const char *line, const tgt_t *t, int n_smp, int *unseen_io, chead_t *kept)
+{
+    char *c = strdup(line); int nf; char **f = split(c, '\t', &nf);
+    int nalt = 0; char *altc = strdup(f[4]), **alts = split(altc, ',', &nalt);
+    if (!strcmp(f[4], ".")) nalt = 0;
+    chead_t h; char *res = NULL;
+    if (constrain_head(f, alts, nalt, t, *unseen_io, &h) == 0) {
+        if (kept) { *kept = h; kept->unseen_al = NULL; }
+        if (!h.changed) res = strdup(line);
+        else {
+            const size_t cap = strlen(line) * 4 + 4096 + (size_t)n_smp * (size_t)(h.nals * (h.nals + 1) / 2) * 12;
+            obuf_t ob = { malloc(cap), 0, cap };
+            constrained_columns(&ob, f, &h);
+            constrained_samples(&ob, f, &h, n_smp);
+            *unseen_io = h.unseen ? h.nals - 1 : h.unseen;
+            res = ob.p;
+        }
+    }
+    free(h.unseen_al); free(alts); free(altc); free(f); free(c);
+    return res;
 }
 
 /* next_line (vcfcall.c:501-605): the target of this record, or -1 when the record is not to be called */
@@ -419,7 +466,7 @@ static int unwanted_site(const char *line, int acgt_only, int skip_kind)
 
 /* ---- the state of a run, stage by stage ---- */
 typedef struct {                                                /* the command line */
-    int varonly, out_tags, keepalt, dev_in, dev_parse, parse_given, dev_rec, dev_keys, keys_given, dev_text, text_given, want_timing;
+    int varonly, out_tags, keepalt, dev_in, dev_parse, parse_given, dev_rec, dev_keys, keys_given, dev_text, text_given, dev_als, als_given, want_timing;
     int acgt_only, skip_kind;                                   /* vcfcall.c:937 (CF_ACGT_ONLY is the default); -V: 1 = snps, 2 = indels */
     const char *tgt_file, *smpl_file, *smpl_list, *ploidy_file, *ploidy_alias, *grp_arg, *grp_tag, *out_path, *in_path;
     double prior; char out_mode, prior_an_tag[64], prior_ac_tag[64];
@@ -431,7 +478,8 @@ typedef struct { preg_t *reg; int n; char last_sex[64]; } ploidy_t;
  * columns; a sample's ploidy ("0", "1", "2") or sex name; -G: the group of every sample */
 typedef struct { int S, S_in, *col; char **names, (*spec)[64]; int32_t *grp; int ngrp; } smap_t;
 /* the records that are called; --device-input: their per-sample blocks, back to back (--device-parse: their sample columns' text); -i: where the last record lay */
-typedef struct { rec_t *rec; int n, cap, ngmax, namax; unsigned char *ibuf; size_t ibuf_l, ibuf_m; char *prev_chrom; long prev_pos0; } recs_t;
+typedef struct { rec_t *rec; int n, cap, ngmax, namax; unsigned char *ibuf; size_t ibuf_l, ibuf_m; char *prev_chrom; long prev_pos0;
+                 int ngin, nain, n_changed; } recs_t;           /* --device-alleles: the genotypes / alleles of the widest input record; the records -C alleles changes */
 /* what mcall() reads from the records: PL planes (missing / vector_end kept), QS, I16.
  * --device-input: no host PL / AD planes; per record where the PL vector (and the -G tag's) lies in the byte buffer.
  * --device-parse: likewise; per record where its columns lie in the byte buffer and the key's place in the FORMAT column */
@@ -483,6 +531,7 @@ static int parse_options(int argc, char **argv, opt_t *o)
         else if (!strcmp(argv[1], "--device-records")) { o->dev_rec = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-keys")) { o->dev_keys = o->keys_given = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--device-text")) { o->dev_text = o->text_given = 1; ++argv; --argc; }
+        else if (!strcmp(argv[1], "--device-alleles")) { o->dev_als = o->als_given = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "--timing")) { o->want_timing = 1; ++argv; --argc; }
         else if (!strcmp(argv[1], "-C") && argc > 3) { if (strcmp(argv[2], "alleles")) DIE("-C: only `alleles` is supported\n"); cals = 1; argv += 2; argc -= 2; }
         else if (!strcmp(argv[1], "-T") && argc > 3) { o->tgt_file = argv[2]; argv += 2; argc -= 2; }
@@ -529,7 +578,8 @@ static int parse_options(int argc, char **argv, opt_t *o)
     }
     if (o->gv_n && o->varonly) DIE("The two options cannot be combined: --variants-only and --gvcf\n");       /* vcfcall.c:1085 */
     if (o->gv_n && cals) DIE("-g with -C alleles is not supported\n");
-    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-parse] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"
+    if (argc != 2) { fprintf(stderr, "usage: bcfgpu_call [-v] [-M] [-V snps|indels] [-t|-r REGIONS] [-T|-R FILE] [-g INT,...] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]] [-F AN,AC] [-a GQ,GP] [-A] [-P theta] [-C alleles -T targets.tab [-i]] [--device-input] [--device-parse] [--device-alleles] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] [-o out] in.vcf|in.bcf\n"
+        "       --device-alleles acts with -C alleles where --device-input (BCF in) or --device-parse (VCF text in) is given: that option then takes effect\n"
         "       --device-text acts with -O v|z where --device-input (BCF in) or --device-parse (VCF text in) is in effect\n"
         "       --device-keys acts with -O u|b where --device-records and --device-input (BCF in) or --device-parse (VCF text in) are in effect\n"); return 2; }
     o->in_path = argv[1]; return 0;
@@ -582,8 +632,9 @@ static vio_file *open_input(opt_t *o, vio_hdr **hdr)
     vio_file *fin = vio_open_read(o->in_path);               /* VCF, bgzipped VCF or BCF (hts_open of vcfcall.c) */
     if (!fin) DIE("%s\n", vio_error());
     if (!(*hdr = vio_read_hdr(fin))) DIE("%s\n", vio_error());
-    o->dev_in = o->dev_in && vio_is_bcf(fin) && !cals && !o->gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
-    o->dev_parse = o->dev_parse && !vio_is_bcf(fin) && !cals && !o->gv_n;   /* the same two, for the same reasons, on text input */
+    o->dev_in = o->dev_in && vio_is_bcf(fin) && (!cals || o->dev_als) && !o->gv_n;      /* -C alleles rewrites a record's PL, -g reads every record's DP: on the host */
+    o->dev_parse = o->dev_parse && !vio_is_bcf(fin) && (!cals || o->dev_als) && !o->gv_n;   /* the same two, for the same reasons, on text input */
+    o->dev_als = o->dev_als && cals && (o->dev_in || o->dev_parse);     /* ... unless --device-alleles has the device constrain the planes it decodes */
     o->dev_rec = o->dev_rec && (o->out_mode == 'u' || o->out_mode == 'b') && !o->gv_n;    /* key blocks go into BCF records; -g's block lines read gt on the host */
     o->dev_keys = o->dev_keys && (o->dev_in || o->dev_parse) && o->dev_rec;      /* the input's bytes or text in HBM and key blocks to splice: both ends on the device */
     o->dev_text = o->dev_text && (o->dev_in || o->dev_parse) && (o->out_mode == 'v' || o->out_mode == 'z');   /* the input's bytes or text in HBM, text records to write */
@@ -624,17 +675,18 @@ static int unseen_allele(char **alts, int nalt)
     for (int i = 0; i < nalt; ++i) { const char *a = alts[i]; if (a[0] == 'X' || (a[0] == '<' && (a[1] == 'X' || a[1] == '*') && a[2] == '>')) return 1 + i; }
     return 0;
 }
-/* -C alleles: pair the record with a target, rewrite it.  The line to call (malloc'ed), or NULL: the record is passed over */
-static char *pair_with_target(const opt_t *o, const char *buf, int S_in, recs_t *R)
+/* -C alleles: pair the record with a target, rewrite it.  The line to call (malloc'ed), or NULL: the record is passed over.
+ * --device-alleles: buf is the first nine columns (n_smp = 0), the head alone is rewritten and *kept says how the planes follow */
+static char *pair_with_target(const opt_t *o, const char *buf, int n_smp, recs_t *R, chead_t *kept)
 {
     char *owned = NULL, *c2 = strdup(buf); int nf2; char **f2 = split(c2, '\t', &nf2);
-    if (nf2 != 9 + S_in) DIE("malformed VCF\n");
+    if (nf2 != 9 + n_smp) DIE("malformed VCF\n");
     int nalt2 = 0; char *ac = strdup(f2[4]), **av = split(ac, ',', &nalt2);
     if (!strcmp(f2[4], ".")) nalt2 = 0;
     const int pos2 = atoi(f2[1]), ti = pick_target(f2[0], pos2, f2[3], av, nalt2);
     if (ti >= 0) {
         tgt[ti].used = 1; int un = unseen_allele(av, nalt2);
-        owned = constrain_line(buf, &tgt[ti], S_in, &un);
+        owned = constrain_line(buf, &tgt[ti], n_smp, &un, kept);
         if (owned && unwanted_site(owned, o->acgt_only, o->skip_kind)) { free(owned); owned = NULL; }   /* (the skipped record flushes no targets either: vcfcall.c:1095-1099 come before tgt_flush) */
         if (owned && insert_missed) {                    /* tgt_flush (vcfcall.c:426-455) */
             const long p0 = pos2 - 1;
@@ -681,7 +733,7 @@ static void record_ploidy(rec_t *r, const ploidy_t *P, const smap_t *M)
 /* the read loop: the records that are called, split into fields; closes the input */
 static void read_records(const opt_t *o, const ploidy_t *P, const smap_t *M, vio_file *fin, vio_hdr *hdr, recs_t *R)
 {
-    memset(R, 0, sizeof *R); R->ngmax = 1;
+    memset(R, 0, sizeof *R); R->ngmax = R->ngin = R->nain = 1;
     const int S_in = M->S_in;
     char *buf = NULL; size_t bufcap = 0; int rrc;
     if (cals) { if (!o->tgt_file) DIE("-C alleles needs -T targets\n"); tgt_parse(o->tgt_file); }
@@ -692,20 +744,30 @@ static void read_records(const opt_t *o, const ploidy_t *P, const smap_t *M, vio
         if (rrc <= 0) break;
         if (!strlen(buf)) continue;
         char *use = buf, *owned = NULL;
-        if (cals) { if (!(use = owned = pair_with_target(o, buf, S_in, R))) continue; }
+        const char *smp = NULL;                                  /* --device-parse: the ninth tab, where the sample columns start */
+        if (o->dev_parse) {
+            smp = buf;
+            for (int t = 0; t < 9 && smp; ++t) smp = strchr(smp + (t > 0), '\t');
+            if (!smp) DIE("malformed VCF\n");
+        }
+        chead_t kept; memset(&kept, 0, sizeof kept);
+        if (cals && o->dev_als) {                                /* the head alone is paired and rewritten; the samples' bytes or text stay as they are */
+            char *head = smp ? strndup(buf, (size_t)(smp - buf)) : buf;
+            use = owned = pair_with_target(o, head, 0, R, &kept);
+            if (smp) free(head);
+            if (!use) continue;
+        }
+        else if (cals) { if (!(use = owned = pair_with_target(o, buf, S_in, R, NULL))) continue; }
         else if (unwanted_site(use, o->acgt_only, o->skip_kind)) continue;
         if (R->n == R->cap) { R->cap = R->cap ? 2 * R->cap : 1024; R->rec = realloc(R->rec, (size_t)R->cap * sizeof *R->rec); }
         if (cals) push_event(0, R->n);
         rec_t *r = &R->rec[R->n++];
-        const char *smp = NULL;                                  /* --device-parse: the ninth tab, where the sample columns start */
-        if (o->dev_parse) {
-            smp = use;
-            for (int t = 0; t < 9 && smp; ++t) smp = strchr(smp + (t > 0), '\t');
-            if (!smp) DIE("malformed VCF\n");
-        }
-        r->line = smp ? strndup(use, (size_t)(smp - use)) : strdup(use);
+        r->line = smp && !o->dev_als ? strndup(use, (size_t)(smp - use)) : strdup(use);
         r->fld = split(r->line, '\t', &r->nfld);
         r->keys = NULL; r->nkeys = 0; r->kjob = NULL; r->nkjob = 0;
+        r->nori = kept.nori; r->unseen_in = kept.unseen; r->changed = kept.changed;
+        for (int i = 0; i < BCFGPU_MAX_ALLELES; ++i) r->amap[i] = i < kept.nals ? kept.amap[i] : 0;
+        if (o->dev_als) { R->n_changed += r->changed; if (r->nori * (r->nori + 1) / 2 > R->ngin) R->ngin = r->nori * (r->nori + 1) / 2; if (r->nori > R->nain) R->nain = r->nori; }
         if (smp) {                                               /* the columns join the byte buffer as they are */
             const size_t l_smp = strlen(smp);
             if (R->ibuf_l + l_smp > R->ibuf_m) { R->ibuf_m = (R->ibuf_l + l_smp) * 2 + (1 << 20); R->ibuf = realloc(R->ibuf, R->ibuf_m); if (!R->ibuf) DIE("out of memory\n"); }
@@ -866,9 +928,32 @@ static void decode_text_planes(bcfgpu_ctx *ctx, int n, int S_in, const void *d_t
     if (rc == BCFGPU_E_ARG) DIE("malformed VCF\n");
     if (rc) DIE("bcfgpu_call_decode_vcf: %s (%d)\n", bcfgpu_last_error(), rc);
 }
+/* --device-alleles: the planes the decoders made in the input records' alleles (n_in a site, at d_in) become the planes mcall() reads,
+ * in the targets' alleles (n_out a site); the input-shape planes are freed.  numberR: the -G tag's planes (a tag the header does not
+ * declare Number=R stays as it is, as on the host) */
+static int32_t *constrain_planes(bcfgpu_ctx *ctx, const recs_t *R, int S, int numberR, int follows, int n_in, int32_t *d_in, int n_out)
+{
+    void *dp = NULL;
+    bcfgpu_cals_site *cs = calloc((size_t)R->n + 1, sizeof *cs);
+    if (!cs) DIE("out of memory\n");
+    for (int k = 0; k < R->n; ++k) {
+        const rec_t *r = &R->rec[k];
+        cs[k].n_new = r->nals; cs[k].unseen = r->unseen_in; cs[k].changed = r->changed && follows;
+        for (int i = 0; i < BCFGPU_MAX_ALLELES; ++i) cs[k].amap[i] = r->amap[i];
+    }
+    CHECK(bcfgpu_malloc(ctx, (size_t)R->n * n_out * S * 4 + 16, &dp));
+    const int rc = bcfgpu_call_constrain(ctx, numberR ? BCFGPU_CALS_NUMBER_R : BCFGPU_CALS_NUMBER_G, R->n, cs, n_in, d_in, n_out, dp);
+    if (rc) DIE("bcfgpu_call_constrain: %s (%d)\n", bcfgpu_last_error(), rc);
+    CHECK(bcfgpu_free(ctx, d_in));
+    free(cs);
+    return dp;
+}
 static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, const hplanes_t *H, dev_t *D)
 {
     const rec_t *recs = R->rec; const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_rec = o->dev_rec || o->dev_text;
+    /* --device-alleles: the decoders write planes of the input records' shape, bcfgpu_call_constrain those of the constrained records */
+    const int ngin = o->dev_als ? R->ngin : ngmax, nain = o->dev_als ? R->nain : namax;
+    const int tag_is_R = o->grp_tag && is_numberR(fmtR, n_fmtR, o->grp_tag, strlen(o->grp_tag));
     memset(D, 0, sizeof *D);
     bcfgpu_cfg cfg; memset(&cfg, 0, sizeof cfg);
     cfg.device = 0; cfg.n_smpl = S; cfg.max_sites = n; cfg.max_reads = 64;
@@ -880,22 +965,26 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
         void *dp = NULL;
         D->d_indiv = dev_upload(ctx, R->ibuf, R->ibuf_l);
         const int32_t *cmap = o->smpl_file ? (const int32_t *)M->col : NULL;     /* without -S / -s called sample s is input sample s */
-        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4 + 16, &dp)); D->d_plin = dp;
-        CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_pl, cmap, ngmax, D->d_plin));
+        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngin * S * 4 + 16, &dp)); D->d_plin = dp;
+        CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_pl, cmap, ngin, D->d_plin));
+        if (o->dev_als) D->d_plin = constrain_planes(ctx, R, S, 0, 1, ngin, D->d_plin, ngmax);
         if (H->want_ad) {
-            CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); D->d_ad = dp;
-            CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_ad, cmap, namax, D->d_ad));
+            CHECK(bcfgpu_malloc(ctx, (size_t)n * nain * S * 4 + 16, &dp)); D->d_ad = dp;
+            CHECK(bcfgpu_call_decode_bcf(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->vec_ad, cmap, nain, D->d_ad));
+            if (o->dev_als) D->d_ad = constrain_planes(ctx, R, S, 1, tag_is_R, nain, D->d_ad, namax);
         }
         if (!o->dev_keys && !o->dev_text) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
     } else if (o->dev_parse) {                                   /* the columns' text goes up once and is parsed there */
         void *dp = NULL;
         D->d_indiv = dev_upload(ctx, R->ibuf, R->ibuf_l);
         const int32_t *cmap = o->smpl_file ? (const int32_t *)M->col : NULL;
-        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngmax * S * 4 + 16, &dp)); D->d_plin = dp;
-        decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_pl, cmap, ngmax, D->d_plin);
+        CHECK(bcfgpu_malloc(ctx, (size_t)n * ngin * S * 4 + 16, &dp)); D->d_plin = dp;
+        decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_pl, cmap, ngin, D->d_plin);
+        if (o->dev_als) D->d_plin = constrain_planes(ctx, R, S, 0, 1, ngin, D->d_plin, ngmax);
         if (H->want_ad) {
-            CHECK(bcfgpu_malloc(ctx, (size_t)n * namax * S * 4 + 16, &dp)); D->d_ad = dp;
-            decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_ad, cmap, namax, D->d_ad);
+            CHECK(bcfgpu_malloc(ctx, (size_t)n * nain * S * 4 + 16, &dp)); D->d_ad = dp;
+            decode_text_planes(ctx, n, M->S_in, D->d_indiv, R->ibuf_l, H->txt_ad, cmap, nain, D->d_ad);
+            if (o->dev_als) D->d_ad = constrain_planes(ctx, R, S, 1, tag_is_R, nain, D->d_ad, namax);
         }
         if (!o->dev_keys && !o->dev_text) { CHECK(bcfgpu_free(ctx, D->d_indiv)); D->d_indiv = NULL; }
     } else {
@@ -1016,6 +1105,7 @@ static void parse_key_blocks(const opt_t *o, const smap_t *M, recs_t *R, const h
             if (i == r->pl_idx || i >= BCFGPU_VCF_REWRITE_MAX_KEYS || !strcmp(keys[i], "GT")) continue;
             const int id = vio_hdr_fmt_id(hdr, keys[i]);
             if (id < 0 || vio_hdr_fmt_type(hdr, id) != VIO_TYPE_INT) continue;
+            if (r->changed && is_numberR(fmtR, n_fmtR, keys[i], strlen(keys[i]))) continue;      /* --device-alleles: the key follows amap first: the host's */
             if ((size_t)B->n_pjob == cap_job) { cap_job = cap_job ? 2 * cap_job : 4096; job = realloc(job, cap_job * sizeof *job); if (!job) DIE("out of memory\n"); }
             bcfgpu_vcf_key *j = &job[B->n_pjob];
             memset(j, 0, sizeof *j);
@@ -1057,6 +1147,7 @@ static void encode_key_blocks(const opt_t *o, const smap_t *M, recs_t *R, const 
             if (q->type < 0 || q->type > 3 || q->width < 0 || q->width > BCFGPU_BCF_KEY_MAX_WIDTH) continue;
             const int id = vio_hdr_fmt_id(hdr, q->id);
             if (id < 0) continue;
+            if (r->changed && is_numberR(fmtR, n_fmtR, q->id, strlen(q->id))) continue;          /* --device-alleles: the key follows amap first: the host's */
             if ((size_t)B->n_pjob == cap_job) { cap_job = cap_job ? 2 * cap_job : 4096; job = realloc(job, cap_job * sizeof *job); if (!job) DIE("out of memory\n"); }
             bcfgpu_bcf_key *j = &job[B->n_pjob];
             j->off = r->ioff + q->off; j->site = k; j->key_id = id; j->type = q->type; j->width = q->width; j->nals = r->nals;
@@ -1116,6 +1207,7 @@ static void encode_text_columns(const opt_t *o, const smap_t *M, const recs_t *R
             const vio_indiv_key *q = &r->keys[i];
             if (!strcmp(q->id, "GT")) ok = 0;
             else if (i != r->pl_idx && (q->type < 0 || q->type > 3 || q->width < 0 || q->width > BCFGPU_BCF_KEY_MAX_WIDTH)) ok = 0;
+            else if (i != r->pl_idx && r->changed && is_numberR(fmtR, n_fmtR, q->id, strlen(q->id))) ok = 0;      /* --device-alleles: a key that follows amap first */
         }
         if (ok) {
             if (n_f + BCFGPU_VCF_MAX_FIELDS > cap_f) { cap_f = cap_f ? 2 * cap_f : 4096; fld = realloc(fld, cap_f * sizeof *fld); if (!fld) DIE("out of memory\n"); }
@@ -1176,6 +1268,7 @@ static void rewrite_text_columns(const opt_t *o, const smap_t *M, const recs_t *
         int nk; char *fmt = strdup(r->fld[8]), **keys = split(fmt, ':', &nk);
         int ok = !(called && D->d_gp) && nk <= BCFGPU_VCF_REWRITE_MAX_KEYS;
         for (int i = 0; ok && i < nk; ++i) if (!strcmp(keys[i], "GT")) ok = 0;
+        for (int i = 0; ok && r->changed && i < nk; ++i) if (i != r->pl_idx && is_numberR(fmtR, n_fmtR, keys[i], strlen(keys[i]))) ok = 0;   /* --device-alleles: a key that follows amap first */
         if (ok) {
             w->n_fmt = (int16_t)nk; w->pl_idx = r->pl_idx;
             for (int i = 0; i < nk; ++i) if (is_numberR(fmtR, n_fmtR, keys[i], strlen(keys[i]))) w->r_mask |= 1ull << i;
@@ -1349,6 +1442,14 @@ static void print_sample_text(const writer_t *W, int k, const fmt_t *F, const ch
                 if (v == BCFGPU_INT32_MISSING) fputc('.', LN); else fprintf(LN, "%d", v);
             }
             if (!printed) fputc('.', LN);
+        } else if (i < nv && r->changed && is_numberR(fmtR, n_fmtR, F->keys[i], strlen(F->keys[i]))) {
+            /* --device-alleles: the column is the input's own; the key goes through amap first (the sample part of the rewrite), then als_map */
+            const size_t cap = BCFGPU_MAX_ALLELES * (strlen(vals[i]) + 2) + 8;
+            obuf_t ob = { malloc(cap), 0, cap };
+            constrained_numberR(&ob, vals[i], r->amap, r->nals);
+            if (nf++) fputc(':', LN);
+            if (nn != r->nals) print_numberR(ob.p, c->als_map, r->nals, nn); else fputs(ob.p, LN);
+            free(ob.p);
         } else if (i < nv && nn != r->nals && is_numberR(fmtR, n_fmtR, F->keys[i], strlen(F->keys[i]))) {
             if (nf++) fputc(':', LN);
             print_numberR(vals[i], c->als_map, r->nals, nn);
@@ -1520,6 +1621,7 @@ int main(int argc, char **argv)
     if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device input: %d records' planes decoded on the device\n", o.dev_in ? R.n : 0);
     if (o.want_timing) fprintf(stderr, "[bcfgpu_call] device records: %d records' FORMAT blocks encoded on the device\n", B.n_enc);
     if (o.want_timing && o.parse_given) fprintf(stderr, "[bcfgpu_call] device parse: %d records' planes parsed on the device\n", o.dev_parse ? R.n : 0);
+    if (o.want_timing && o.als_given) fprintf(stderr, "[bcfgpu_call] device alleles: %d records' planes constrained on the device, %d taken as they were\n", o.dev_als ? R.n_changed : 0, o.dev_als ? R.n - R.n_changed : 0);
     if (o.want_timing && o.keys_given) fprintf(stderr, "[bcfgpu_call] device keys: %ld pass-through key blocks made on the device, %ld on the host\n", B.n_pjob, B.n_phost);
     if (o.want_timing && o.text_given) fprintf(stderr, "[bcfgpu_call] device text: %ld records' sample columns formatted on the device, %ld on the host\n", B.n_tdev, B.n_thost);
     bcfgpu_destroy(D.ctx);

@@ -34,6 +34,8 @@
  *                                           per-sample block behind them: FORMAT/PL and AD / QS of BCF records as the planes of bcfgpu_call_in
  *    bcfgpu_call_decode_vcf              <- the vcf_parse_format / bcf_get_format_int32 pair behind the same two calls (mcall.c:1444, :1475) on VCF
  *                                           text input: FORMAT/PL and AD / QS of a record's sample columns as the planes of bcfgpu_call_in
+ *    bcfgpu_call_constrain               <- the per-sample part of mcall_constrain_alleles (mcall.c:1332-1371 the PL gather through pl_map,
+ *                                           :1380-1413 the Number=R tags): the planes of `call -C alleles` records in their targets' alleles
  *    bcfgpu_call_remap_bcf               <- mcall_trim_and_update_numberR (mcall.c:1196-1265), bcf_subset's sample choice and the writer's
  *                                           typed-value encoder, for the integer FORMAT keys a call record passes through (AD, DP, SP, ...)
  *    bcfgpu_call_encode_vcf              <- the same three and the text vcf_format writes for them: the sample columns of a call record, the
@@ -771,6 +773,38 @@ typedef struct {
 } bcfgpu_vcf_vec;
 int  bcfgpu_call_decode_vcf(bcfgpu_ctx *ctx, int32_t n_sites, int32_t n_smpl_in, const void *d_text, uint64_t n_text_bytes,
                             const bcfgpu_vcf_vec *vec, const int32_t *col, int32_t n_planes, int32_t *d_out);
+
+/* `call -C alleles`: the planes of n_sites records re-expressed in the alleles of their targets (calsmap.hip) -- the per-sample part of
+ * mcall_constrain_alleles: mcall.c:1332-1371 (FORMAT/PL gathered through pl_map, the unseen allele standing in for the alleles mpileup
+ * did not see) and mcall.c:1380-1413 (the Number=R tags through als_map), as host/bcfgpu_call.c constrain_line() prints the values and
+ * build_planes() parses them back.
+ *   mode     BCFGPU_CALS_NUMBER_G: a value per genotype (PL); BCFGPU_CALS_NUMBER_R: a value per allele (AD, or QS for -G)
+ *   site     HOST [n_sites]: the descriptor of each record
+ *   d_in     DEVICE [n_sites][n_in][cfg.n_smpl]: the planes as bcfgpu_call_decode_bcf / _vcf write them, in the record's own alleles
+ *   d_out    DEVICE [n_sites][n_out][cfg.n_smpl]: the planes bcfgpu_call_in.pl / .ad want; must not overlap d_in
+ * Per site and sample, with in(j) = plane j of the sample for j < n_in and VECTOR_END otherwise, gt(a,b) = the genotype index of the
+ * alleles a and b in either order, and amap entries above 65535 counting as 65535:
+ *   changed == 0 (both modes): out[g] = in(g) for g < n_out.
+ *   NUMBER_G, changed: for g = i(i+1)/2 + j, j <= i < n_new: m = gt(amap[i], amap[j]), v = in(m); when v is MISSING and unseen >= 0, with
+ *     (ia, ib) the alleles of m: ko = gt(ia, unseen); if in(ko) is MISSING ko = gt(ib, unseen); if still MISSING ko = gt(unseen, unseen);
+ *     v = in(ko).  At g == 0 VECTOR_END becomes MISSING.  From the first g whose v is VECTOR_END on, every plane is VECTOR_END (the text is
+ *     cut there); the planes n_new(n_new+1)/2 .. n_out-1 are VECTOR_END.
+ *   NUMBER_R, changed: with nv = the planes before the sample's first VECTOR_END: a sample whose vector is the single value MISSING ('.', or
+ *     no such key) stays MISSING, then VECTOR_END; otherwise out[a] = amap[a] < nv ? in(amap[a]) : MISSING for a < n_new, VECTOR_END behind.
+ * BCFGPU_E_ARG, with nothing written, for NULL pointers, n_in or n_out outside 1 .. BCFGPU_CALS_MAX_PLANES, an n_new outside 1..5, a
+ * negative amap entry among the first n_new, a changed site whose n_new(n_new+1)/2 (NUMBER_R: n_new) values do not fit n_out,
+ * overlapping buffers or an unknown mode.  n_sites == 0 is valid.  Runs on the context's stream and synchronises it. */
+#define BCFGPU_CALS_NUMBER_G   0
+#define BCFGPU_CALS_NUMBER_R   1
+#define BCFGPU_CALS_MAX_PLANES (1 << 20)
+typedef struct {
+    int32_t n_new;      /* the alleles of the constrained record, 1..5 */
+    int32_t unseen;     /* the record's unseen-allele index before the rewrite (0: none; < 0: no fallback) */
+    int32_t changed;    /* 0: the record stays as it is */
+    int32_t amap[BCFGPU_MAX_ALLELES];   /* new allele -> original allele, >= 0; the entries from n_new on are not read */
+} bcfgpu_cals_site;
+int  bcfgpu_call_constrain(bcfgpu_ctx *ctx, int32_t mode, int32_t n_sites, const bcfgpu_cals_site *site,
+                           int32_t n_in, const int32_t *d_in, int32_t n_out, int32_t *d_out);
 
 /* The caller's own records: FORMAT/GT, the trimmed FORMAT/PL and FORMAT/GQ of every call record as BCF2 bytes, made on the planes
  * bcfgpu_mcall / bcfgpu_pipeline left in HBM (bcfcallenc.hip) -- what bcf_update_genotypes and bcf_update_format_int32 (mcall.c:1158-1194,

@@ -4,7 +4,8 @@
  *      bcfgpu_call [-v] [-S samples.txt | -s NAME,...] [--ploidy-file file | --ploidy GRCh37|GRCh38|X|Y|1] [-G -|groups.txt [--group-samples-tag TAG]]
  *                  [-F AN_TAG,AC_TAG] [-a GQ,GP] [--device-input] [--device-parse] [--device-alleles] [--device-records] [--device-keys] [--device-text] [--timing] [-O v|z|u|b] <in.vcf>
  *          -S: the samples to keep, in that order: NAME [PLOIDY|SEX] per line, or a PED file (vcfcall.c:202-344)
- *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c)
+ *          --ploidy-file: CHROM FROM TO SEX PLOIDY lines, '*' = default for the sex (ploidy.c).  The definition also sets the prior's
+ *              allele count: ploidy_max() of it times the samples (vcfcall.c:652-656) -- one a sample with --ploidy 1, else two
  *          -G: sample groups with their own allele frequencies, '-' = every sample alone, or NAME GROUP lines
  *              (mcall.c:258-345); the frequencies come from FORMAT/QS or FORMAT/AD (--group-samples-tag)
  *          -F: INFO tags holding AN and AC of a prior population (mcall.c:1499-1520)
@@ -472,8 +473,9 @@ typedef struct {                                                /* the command l
     double prior; char out_mode, prior_an_tag[64], prior_ac_tag[64];
     int32_t gv_range[16]; int gv_n;                             /* -g INT,...: gvcf_init (gvcf.c:47-73) */
 } opt_t;
-/* ploidy definition (ploidy.c): regions per sex, '*' lines = the sex's default; the last sex named is the default sex */
-typedef struct { preg_t *reg; int n; char last_sex[64]; } ploidy_t;
+/* ploidy definition (ploidy.c): regions per sex, '*' lines = the sex's default; the last sex named is the default sex;
+ * max: ploidy_max() of the definition -- the prior counts max * samples alleles (vcfcall.c:652-656, mcall.c:396-416) */
+typedef struct { preg_t *reg; int n, max; char last_sex[64]; } ploidy_t;
 /* the samples called, S of the input's S_in: output sample s = input column col[s] (bcf_subset with -S); the names of the input
  * columns; a sample's ploidy ("0", "1", "2") or sex name; -G: the group of every sample */
 typedef struct { int S, S_in, *col; char **names, (*spec)[64]; int32_t *grp; int ngrp; } smap_t;
@@ -587,6 +589,7 @@ static int parse_options(int argc, char **argv, opt_t *o)
 static void load_ploidy(opt_t *o, ploidy_t *P)
 {
     memset(P, 0, sizeof *P); char *alias_text = NULL;
+    P->max = 2;                                                  /* no definition given: `0 0 / 1 1 / 2 2` (vcfcall.c:1071) */
     if (o->ploidy_alias) {
         /* --ploidy ALIAS: the definitions `call` carries with it (vcfcall.c:138-199), in the format of a --ploidy-file: the
          * haploid stretches of the human sex chromosomes outside the pseudo-autosomal regions and the mitochondrion, by assembly;
@@ -625,6 +628,16 @@ static void load_ploidy(opt_t *o, ploidy_t *P)
             strcpy(P->last_sex, sx);
         }
     fclose(pf);
+    /* ploidy_max() (ploidy.c:109-110, 122-131, 259-262): the largest ploidy of any line, default lines included, or the definition's
+     * own default if that is larger -- the default of the sex named "*" where the definition has one, else 2.  So `* * * * 1` alone
+     * gives 1, `* * * M 1` with `* * * F 1` gives 2.  (Not reproduced: a region line of the sex "*" without a `* * * *` line, which
+     * leaves the reference's default at -1.) */
+    int dflt = 2, max = -1;
+    for (int i = 0; i < P->n; ++i) {
+        if (P->reg[i].ploidy > max) max = P->reg[i].ploidy;
+        if (P->reg[i].from < 0 && !strcmp(P->reg[i].chrom, "*") && !strcmp(P->reg[i].sex, "*")) dflt = P->reg[i].ploidy;
+    }
+    P->max = dflt > max ? dflt : max;
 }
 /* the input and its header; which of the device options take effect in this run */
 static vio_file *open_input(opt_t *o, vio_hdr **hdr)
@@ -948,7 +961,7 @@ static int32_t *constrain_planes(bcfgpu_ctx *ctx, const recs_t *R, int S, int nu
     free(cs);
     return dp;
 }
-static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, const hplanes_t *H, dev_t *D)
+static void call_on_device(const opt_t *o, const ploidy_t *P, const smap_t *M, const recs_t *R, const hplanes_t *H, dev_t *D)
 {
     const rec_t *recs = R->rec; const int n = R->n, S = M->S, ngmax = R->ngmax, namax = R->namax, dev_rec = o->dev_rec || o->dev_text;
     /* --device-alleles: the decoders write planes of the input records' shape, bcfgpu_call_constrain those of the constrained records */
@@ -957,7 +970,8 @@ static void call_on_device(const opt_t *o, const smap_t *M, const recs_t *R, con
     memset(D, 0, sizeof *D);
     bcfgpu_cfg cfg; memset(&cfg, 0, sizeof cfg);
     cfg.device = 0; cfg.n_smpl = S; cfg.max_sites = n; cfg.max_reads = 64;
-    cfg.min_baseQ = 13; cfg.capQ = 60; cfg.call_theta = o->prior; cfg.call_flag = (o->varonly ? BCFGPU_CALL_VARONLY : 0) | (o->keepalt ? BCFGPU_CALL_KEEPALT : 0); cfg.n_grp = M->ngrp; cfg.ploidy_max = 2;
+    cfg.min_baseQ = 13; cfg.capQ = 60; cfg.call_theta = o->prior; cfg.call_flag = (o->varonly ? BCFGPU_CALL_VARONLY : 0) | (o->keepalt ? BCFGPU_CALL_KEEPALT : 0); cfg.n_grp = M->ngrp;
+    cfg.ploidy_max = P->max;                                     /* the prior's allele count is ploidy_max * S, whatever the samples' own ploidies */
     cfg.output_tags = o->out_tags;
     CHECK(bcfgpu_create(&cfg, &D->ctx)); bcfgpu_ctx *ctx = D->ctx;
     D->d_nals = dev_upload(ctx, H->nals, (size_t)n * 4); D->d_unseen = dev_upload(ctx, H->unseen, (size_t)n * 4);
@@ -1591,7 +1605,7 @@ int main(int argc, char **argv)
     const double t1 = now_s();
     build_planes(&o, &M, &R, &H);
     const double t_planes = now_s() - t1, t2 = now_s();
-    call_on_device(&o, &M, &R, &H, &D);
+    call_on_device(&o, &P, &M, &R, &H, &D);
     double t_dev = now_s() - t2, t_enc = 0.;
     const double t3 = now_s();
     output_header(&o, &M, hdr);

@@ -156,7 +156,9 @@ typedef struct {
     int32_t output_tags;   /* BCFGPU_CALL_FMT_GQ | BCFGPU_CALL_FMT_GP | BCFGPU_CALL_FMT_PV4 */
     int32_t n_grp;         /* number of -G sample groups; <=1: one pooled group */
     int32_t grp_tag_is_qs; /* -G with FORMAT/QS (1) or FORMAT/AD (0) as frequency source */
-    int32_t ploidy_max;    /* ploidy_max(args->ploidy) used for the prior's allele count (vcfcall.c:654-655, mcall.c:397-405); 0 -> 2 */
+    int32_t ploidy_max;    /* ploidy_max(args->ploidy): the prior counts ploidy_max * n_smpl alleles whatever the samples' own
+                            * ploidies are (vcfcall.c:652-656, mcall.c:396-416).  It is the largest ploidy of the definition's lines
+                            * or its default if that is larger (ploidy.c:259-262): 2 without a definition, 1 for `--ploidy 1`.  0 -> 2 */
 } bcfgpu_cfg;
 
 /* one tile of pileup columns (device pointers) */

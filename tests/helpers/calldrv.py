@@ -34,6 +34,18 @@ def ploidy_query(pl, chrom, pos1, sex):
     return pl["dflt"].get(sex, 2)
 
 
+def ploidy_max(pl):
+    """ploidy_max() of a parsed definition (ploidy.c:109-110, 122-131, 259-262): the largest ploidy of any line, default lines
+    included, or the definition's own default if that is larger -- the default of the sex named '*' where there is one, else 2.
+    No definition: 2 (the built-in `0 0 / 1 1 / 2 2`, vcfcall.c:1071).  The prior counts ploidy_max * samples alleles
+    (vcfcall.c:652-656, mcall.c:396-416).  Not reproduced: a region line of the sex '*' without a `* * * *` line, which leaves the
+    reference's default at -1."""
+    if pl is None:
+        return 2
+    dflt = pl["dflt"].get("*", 2)
+    return max([dflt] + [r[4] for r in pl["regs"]] + list(pl["dflt"].values()))
+
+
 def parse_samples_file(path):
     """vcfcall.c:270-344 incl. PED (vcfcall.c:202-262): returns [(name, spec)] spec = '0'|'1'|'2' or a sex name."""
     lines = [l.rstrip("\n") for l in open(path) if l.strip() and not l.startswith("#")]
@@ -63,11 +75,13 @@ def fmt_gt(a, b):
 
 
 def run_call(vcf, engine, call_flag=0, output_tags=0, theta=1.1e-3, samples=None, ploidy=None,
-             groups=None, grp_tag="AD", prior=None, recs=None):
+             groups=None, grp_tag="AD", prior=None, recs=None, ploidy_max=None):
     """Returns the list of CalledRec that `bcftools call -m` would print.
 
     samples: [(name, spec)] (-S); ploidy: parsed --ploidy-file; groups: {sample: group} or '-' (-G);
-    prior: (AN_tag, AC_tag) (-F); recs: the records to call instead of vcf.recs (helpers/cals.py: -C alleles).
+    prior: (AN_tag, AC_tag) (-F); recs: the records to call instead of vcf.recs (helpers/cals.py: -C alleles);
+    ploidy_max: cfg.ploidy_max, the prior's alleles per sample (None: 2, as before -- the reference's value is
+    ploidy_max(ploidy) above).
     """
     names = vcf.samples
     if samples is None:
@@ -101,6 +115,8 @@ def run_call(vcf, engine, call_flag=0, output_tags=0, theta=1.1e-3, samples=None
         grp, ngrp = None, 1
 
     cfg = abi.default_cfg(S, call_theta=theta, call_flag=call_flag, output_tags=output_tags, n_grp=ngrp)
+    if ploidy_max is not None:
+        cfg.ploidy_max = ploidy_max
 
     # select candidate records and their per-site ploidy vectors
     cand = []
@@ -210,6 +226,11 @@ def _int_list(s):
     return [abi.INT32_MISSING if x == "." else int(x) for x in s.split(",")]
 
 
+def qual_tol(want, qual_rtol=2e-5):
+    """How far a QUAL may lie from the printed QUAL `want` (six significant digits in the text)."""
+    return max(qual_rtol * abs(want), 1e-4 if abs(want) > 1e-3 else 1e-6)
+
+
 def compare_with_golden(called, sub_names, gold, qual_rtol=2e-5, check_tags=()):
     """Field-by-field comparison of CalledRec list with a golden VCF (Vcf object). Raises AssertionError."""
     assert gold.samples == sub_names, (gold.samples, sub_names)
@@ -222,7 +243,7 @@ def compare_with_golden(called, sub_names, gold, qual_rtol=2e-5, check_tags=()):
             assert c.qual_missing, where
         else:
             assert not c.qual_missing, where
-            tol = max(qual_rtol * abs(g.qual), 1e-4 if abs(g.qual) > 1e-3 else 1e-6)
+            tol = qual_tol(g.qual, qual_rtol)
             assert abs(c.qual - g.qual) <= tol, (where, c.qual, g.qual)
         if "AC" in g.info:
             assert c.ac == g.info_ints("AC"), (where, c.ac, g.info["AC"])

@@ -167,7 +167,7 @@ def test_device_input_on_a_cohort_past_one_wavefront(cohort, args, n_smpl):
     recs = [ln.split(b"\t") for ln in text.splitlines() if not ln.startswith(b"#")]
     assert count >= 200 and 0 < len(recs) <= count and all(len(r) == 9 + n_smpl for r in recs)
     assert len(recs) < count or "-v" not in args
-    if "--ploidy" in args:                                       # haploid genotypes (no variant of this cohort survives haploid calling: every record is kept instead)
+    if "--ploidy" in args:                                       # haploid genotypes (no variant of this cohort survives haploid calling, also with the prior counting 70 alleles, not 140: every record is kept instead)
         assert all(b"/" not in c.split(b":")[0] for r in recs for c in r[9:])
     if "GQ" in args:
         assert any(r[8].endswith(b":GP:GQ") for r in recs)

@@ -610,9 +610,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(COMB_WAVES, 
         const double p = (double)nr / S;
         const double q = (double)nr / M;
         const double log2 = log(2.0);
-        // The per-sample term depends only on the sample's alt-read count oi (0..510), and most samples of a site share a
-        // handful of values: count the samples per oi (zeros by ballot, the rest by LDS atomics), then evaluate the
-        // log/exp expression once per occurring count.  (The sum is tree-reduced and compared with a tolerance anyway.)
+        // The per-sample term depends only on the sample's alt-read count oi, and most samples of a site share a handful
+        // of values: count the samples per oi (zeros by ballot, 1..511 by LDS atomics into the table; 512 and more go term
+        // by term), then evaluate the log/exp expression once per occurring count.  (The sum is tree-reduced and compared
+        // with a tolerance anyway.)
         int *s_oc = reinterpret_cast<int*>(s_stage);           // [512]
         for (int i = tid; i < 512; i += WG) s_oc[i] = 0;
         __syncthreads();

@@ -132,9 +132,11 @@ def stats_of(h):
 
 
 def twin_stats(tile):
-    """{statistic: float32[n_sites]} from the twin."""
+    """{statistic: float32[n_sites]} from the twin: STATS, and seg_bias from the cells' DP4 (sgb_twin)."""
     per = [stats_of(site_hists(tile, s)) for s in range(tile.n_sites)]
-    return {k: np.array([p[k] for p in per], np.float32) for k in STATS}
+    out = {k: np.array([p[k] for p in per], np.float32) for k in STATS}
+    out["seg_bias"] = twin_seg_bias(tile)
+    return out
 
 
 def cell_dp4(tile):
@@ -152,6 +154,66 @@ def cell_dp4(tile):
     k = diff.astype(np.int64) * 2 + f["rev"]
     cnt = np.bincount(cell * 4 + k, minlength=n * S * 4).reshape(n, S, 4)
     return cnt.transpose(0, 2, 1)
+
+
+def _log(x):
+    return math.log(x) if x > 0 else -math.inf if x == 0 else math.nan
+
+
+def _exp(x):
+    try:
+        return math.exp(x)
+    except OverflowError:
+        return math.inf
+
+
+def _logsumexp2(a, b):
+    return _log(1 + _exp(b - a)) + a if a > b else _log(1 + _exp(a - b)) + b
+
+
+def sgb_twin(anno, oi, n_smpl, clamp_hi=True, clamp_lo=True):
+    """calc_SegBias (bam2bcf.c:494-530) in Python doubles, the per-sample terms added with math.fsum: (the value, the
+    condition number sum |term| / |sum term|).  anno: the site's DP4 totals; oi: a sample's ALT reads, None for a sample
+    that is left out of the sum (a model of a mistake; so are clamp_hi / clamp_lo = False, M without its clamps)."""
+    nr = int(anno[2] + anno[3])
+    if not nr:
+        return math.inf, 0.0
+    n = int(n_smpl)
+    avg_dp = int((anno[0] + anno[1] + nr) / n)
+    M = float(math.floor(nr / avg_dp + 0.5)) if avg_dp else math.inf
+    if M > n:
+        M = float(n) if clamp_hi else M
+    elif M == 0 and clamp_lo:
+        M = 1.0
+    f = M / 2. / n
+    p = nr / n
+    q = nr / M if M else math.inf
+    log2 = math.log(2.0)
+    zero = _log(2 * f * (1 - f) * _exp(-q) + f * f * _exp(-2 * q) + (1 - f) * (1 - f)) + p
+    terms = []
+    for o in oi:
+        if o is None:
+            continue
+        o = int(o)
+        terms.append(_logsumexp2(_log(2 * (1 - f)), _log(f) + o * log2 - q) + (_log(f) + o * _log(q / p) - q + p) if o else zero)
+    if not all(math.isfinite(t) for t in terms):
+        return sum(terms), math.inf
+    tot = math.fsum(terms)
+    return tot, (math.fsum(abs(t) for t in terms) / abs(tot) if tot else math.inf)
+
+
+def twin_seg_bias(tile):
+    """seg_bias of every site as the float32 the site struct holds, from cell_dp4.  An indel site without a read of an indel
+    type has no ALT allele: the record is dropped (bam2bcf.c:611) and every field of its site struct is 0."""
+    d = cell_dp4(tile)
+    out = np.zeros(tile.n_sites, np.float32)
+    for s in range(tile.n_sites):
+        anno = d[s].sum(axis=1)
+        if tile.is_indel and not (anno[2] + anno[3]):
+            continue
+        with np.errstate(over="ignore"):
+            out[s] = np.float32(sgb_twin(anno, d[s, 2] + d[s, 3], tile.n_smpl)[0])
+    return out
 
 
 def twin_sp(tile):
@@ -348,11 +410,11 @@ SP_TABLES = (
 
 
 def _tile_of_sites(n_smpl, sites):
-    """sites: a list of dicts of equal-length per-read arrays smpl, bq, mq, alt, rev, epos."""
+    """sites: a list of dicts of equal-length per-read arrays smpl, bq, mq, alt, rev, epos and, if not 20 throughout, tail."""
     rd, ep, cnt = [], [], []
     for s in sites:
         o = np.argsort(s["smpl"], kind="stable")
-        rd.append(_pack(s["bq"][o], s["mq"][o], np.where(s["alt"][o], NT_C, NT_A), s["rev"][o]))
+        rd.append(_pack(s["bq"][o], s["mq"][o], np.where(s["alt"][o], NT_C, NT_A), s["rev"][o], s["tail"][o] if "tail" in s else 20))
         ep.append(s["epos"][o])
         cnt.append(np.bincount(s["smpl"], minlength=n_smpl))
     off = np.r_[0, np.cumsum(np.concatenate(cnt))]

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def _assert_twin(got, tile):
     tw = ss.twin_stats(tile)
-    for k in ss.STATS:
+    for k in ss.STATS + ("seg_bias",):
         g, w = got.site[k].astype(np.float64), tw[k].astype(np.float64)
         assert np.array_equal(np.isinf(g), np.isinf(w)), k
         m = ~np.isinf(w)

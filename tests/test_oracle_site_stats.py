@@ -22,6 +22,10 @@ def _check_twin(tile, want):
     tw = ss.twin_stats(tile)
     for k in ss.STATS:
         assert _bits_equal(tw[k], want.site[k]), (k, tw[k], want.site[k])
+    # (SGB: the twin adds the terms with math.fsum, the oracle in sample order)
+    sgb, w = tw["seg_bias"].astype(np.float64), want.site["seg_bias"].astype(np.float64)
+    assert np.array_equal(np.isinf(sgb), np.isinf(w))
+    np.testing.assert_allclose(w[~np.isinf(w)], sgb[~np.isinf(w)], rtol=ss.RTOL, atol=0, err_msg="seg_bias")
     np.testing.assert_array_equal(ss.twin_sp(tile), want.sp)
     np.testing.assert_array_equal(ss.cell_dp4(tile), want.dp4.astype(np.int64))
 
